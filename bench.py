@@ -10,7 +10,10 @@ image), via libvo.so (hand-written HIP, gfx950).  One step = one batch of
 when WORLD_SIZE is unset) each rank processes its own frames: weak scaling, no
 data-path collective; value = all frames / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run sets up,
+warms up, times exactly --steps steps once, writes the last step's results with
+--dump-outputs DIR, and prints the line.  Everything below is measured with --full only
+(which also takes the median of --runs timed runs as `value`): `h2d`,
 `roofline` (dominant kernel, HIP-event durations measured in this process)
 and `cpu_baseline` (the CPU oracle on a bounded sample, rank 0 at N=1).
 `full_path` additionally times the full per-frame path (BASELINE configs[2]/[3]:
@@ -59,12 +62,21 @@ TRAFFIC_FILE = max(ROOT.glob("profiles/r*_pmc_traffic.json"), key=_traffic_key,
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="timed steps per run (--batch frames each: 5120 frames per run at 256)")
-    ap.add_argument("--runs", type=int, default=5, help="timed runs of --steps steps; value = the median run (SURVEY §8d)")
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (--batch frames each: 5120 frames at 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure everything else the line can hold: --runs timed runs, "
+                         "the H2D copy, per-kernel and roofline figures, the KITTI-00 full path, the 1920x1080 "
+                         "configuration and the CPU baseline (a plain run times --steps steps once and reports that)")
+    ap.add_argument("--runs", type=int, default=5,
+                    help="with --full: timed runs of --steps steps; value = the median run (SURVEY §8d).  A plain run "
+                         "times exactly --steps steps, once")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (keypoints, descriptors, stereo "
+                         "matches: what a caller fetches after vo_sift_match_batch_dev) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=256, help="stereo frames per step (library maximum VO_MAX_BATCH = 512)")
     ap.add_argument("--cpu-frames", type=int, default=32, help="frames in the CPU-oracle baseline sample")
-    ap.add_argument("--cpu-threads", type=int, default=16, help="host threads for the CPU baseline (the box's share)")
+    ap.add_argument("--cpu-threads", type=int, default=16, help="worker processes that render the inputs, and host threads of the CPU baseline")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--concurrency", type=int, default=0, help="forked streams per batch (0: library default)")
@@ -126,6 +138,75 @@ def feature_traffic(fmodel, kt, kt_iso, profile_steps, B):
             "traffic_source": str(TRAFFIC_FILE.relative_to(ROOT)) if TRAFFIC_FILE.exists() else None,
             "note": "per call of --batch frames; PMC of the kernels the traffic file holds (FETCH_SIZE calibrated at 1/2 of "
                     "the 128-B line bytes for these access shapes, profiles/r06_c_fetch_calib.txt)"}
+
+
+def _render_chunk(first, n):
+    from r7020e_visual_odometry_amd import synthetic as syn
+    return syn.independent_pairs(n, ROWS, COLS, first=first, px_per_cell=syn.BENCH_PX_PER_CELL)
+
+
+def render_pairs(n, first, procs):
+    """The step's inputs, syn.independent_pairs(n, first=first), rendered by `procs` worker
+    processes (every pair depends on its seed alone, so the arrays do not depend on `procs`;
+    threads share the interpreter lock for part of the work, and the set-up of a plain run is
+    mostly this).  The workers are forked before this process touches the GPU and never do."""
+    procs = max(1, min(procs, os.cpu_count() or 1, n))
+    if procs == 1:
+        return _render_chunk(first, n)
+    import multiprocessing as mp
+    cuts = [n * i // procs for i in range(procs + 1)]
+    with mp.get_context("fork").Pool(procs) as pool:
+        parts = pool.starmap(_render_chunk, [(first + a, b - a) for a, b in zip(cuts[:-1], cuts[1:])])
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+DUMP_FRAMES = 8              # frames whose keypoints, descriptors and matches --dump-outputs writes in full
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, B, out_dir):
+    """--dump-outputs: the results of the last vo_sift_match_batch_dev call as a caller fetches
+    them (vo_fetch_keypoints, vo_fetch_stereo_pairs), as float .npy files.  The per-frame counts
+    cover every frame of the batch; keypoints, descriptors and matches are written for a fixed
+    sample of DUMP_FRAMES frames (default_rng(0), the same frames in every run of one --batch),
+    which keeps the files far below DUMP_MAX_BYTES at ~2k keypoints per image."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    sample = np.sort(np.random.default_rng(0).choice(B, size=min(DUMP_FRAMES, B), replace=False))
+    counts = np.zeros((B, 3), np.float64)                      # keypoints left, right; stereo matches
+    for f in range(B):
+        if f in sample:
+            continue
+        counts[f] = [len(ctx.fetch_keypoints(2 * f + s, descriptors=False)[0]) for s in (0, 1)] + \
+                    [len(ctx.fetch_stereo_pairs(f))]
+    kp_rows, desc_rows, pair_rows = [], [], []
+    fields = ("x", "y", "size", "angle", "response", "octave", "layer", "scale")
+    budget = DUMP_MAX_BYTES - counts.nbytes - 8 * len(sample) - 1024 * 5       # .npy headers
+    written = []
+    for f in sample:
+        rows = []
+        for s in (0, 1):
+            k, d = ctx.fetch_keypoints(2 * int(f) + s)
+            counts[f, s] = len(k)
+            rows.append((np.column_stack([np.full(len(k), f, np.float32), np.full(len(k), s, np.float32)] +
+                                         [k[n].astype(np.float32) for n in fields]), d.astype(np.float32)))
+        p = ctx.fetch_stereo_pairs(int(f))
+        counts[f, 2] = len(p)
+        pr = np.column_stack([np.full(len(p), f, np.float32), p.astype(np.float32)])
+        budget -= sum(a.nbytes + b.nbytes for a, b in rows) + pr.nbytes
+        if budget < 0 and written:                             # far more keypoints than expected: a shorter sample
+            continue
+        written.append(f)
+        kp_rows += [a for a, _ in rows]
+        desc_rows += [b for _, b in rows]
+        pair_rows.append(pr)
+    arrays = {"counts": counts,                                # [frame] -> n_left, n_right, n_stereo
+              "sample_frames": np.asarray(written, np.float64),
+              "keypoints": np.concatenate(kp_rows),            # frame, side (0 left, 1 right), then `fields`
+              "descriptors": np.concatenate(desc_rows),        # row for row with `keypoints`
+              "stereo_pairs": np.concatenate(pair_rows)}       # frame, left index, right index
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 def sequence_leg(args, torch, rank, world, local, dist, barrier, max_over_ranks, gather_over_ranks):
@@ -314,6 +395,11 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("RANK", "0")
         os.environ.setdefault("WORLD_SIZE", "1")
+    B = args.batch
+    # synthetic pairs: rank r renders frames [r*B, (r+1)*B) (seed 0x5EED0000 + frame); texture
+    # cell of 15 px puts the oracle at ~2000 keypoints per image (2000 +- 200).
+    # Rendered before the first GPU call of this process (render_pairs forks its workers)
+    L, R = render_pairs(B, rank * B, args.cpu_threads)
     torch.cuda.set_device(local)
     dist = None
     if world > 1 or force_dist:
@@ -343,11 +429,6 @@ def main():
 
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE {world}; reporting {world}", file=sys.stderr)
-    B = args.batch
-    # synthetic pairs: rank r renders frames [r*B, (r+1)*B) (seed 0x5EED0000 + frame); texture
-    # cell of 15 px puts the oracle at ~2000 keypoints per image (2000 +- 200)
-    L, R = syn.independent_pairs(B, ROWS, COLS, first=rank * B, px_per_cell=syn.BENCH_PX_PER_CELL,
-                                 threads=args.cpu_threads)
     d_l = torch.from_numpy(L).to(f"cuda:{local}")
     d_r = torch.from_numpy(R).to(f"cuda:{local}")
     torch.cuda.synchronize()
@@ -365,10 +446,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # --runs timed runs of exactly --steps steps each, every run bracketed by a barrier +
-    # synchronize and reduced max-over-ranks; value = the median run (median of 5)
+    # a plain run: one timed run of exactly --steps steps.  --full: --runs timed runs of --steps
+    # steps each, value = the median run (median of 5).  Every run is bracketed by a
+    # barrier + synchronize and reduced max-over-ranks
     run_s = []
-    for _ in range(max(1, args.runs)):
+    for _ in range(max(1, args.runs) if args.full else 1):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -384,6 +466,32 @@ def main():
     timed_runs = {"n": len(run_s), "steps_per_run": args.steps, "frames_per_run": frames,
                   "ms_per_step": [round(x / args.steps * 1e3, 4) for x in run_s],
                   "value_median": fps, "value_min": frames / max(run_s), "value_max": frames / min(run_s)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, B, args.dump_outputs)                # the last timed step's results, still in the context
+
+    kp = np.mean([s[0] + s[1] for s in stats]) / 2
+    st = np.mean([s[2] for s in stats])
+    line = {
+        "metric": "stereo frames/sec @1242x375 (SIFT detect+describe x2 + stereo matchFeatures)",
+        "value": fps, "unit": "stereo frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "ms_per_64_frames": ms_per_step * 64 / B, "timed_runs": timed_runs,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (i8 MFMA for exact descriptor dot products)", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: SIFT detect+describe + BF match on 1242x375 synthetic stereo, "
+                               "~2k keypoints/image", "frames_per_step_per_gpu": B, "rows": ROWS, "cols": COLS,
+                   "mean_keypoints_per_image": float(kp), "mean_stereo_matches": float(st),
+                   "parallelism": f"frames sharded over {world} GPU(s)",
+                   "process_group": dist.get_backend() if dist is not None else None},
+    }
+    if not args.full:
+        # the plain run ends here; the H2D, per-kernel, roofline, full-path, 1920x1080 and CPU
+        # figures below take runs of their own (--full)
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(line), file=json_out, flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # H2D of one batch of u8 pairs (pinned host -> HBM), reported beside `value` (which starts
     # from resident inputs): the PCIe-inclusive rate if the frames came from the host each step
@@ -551,24 +659,7 @@ def main():
                "single_thread": {"value": n1 / dt1, "cores": 1, "sample": f"{n1} pairs, {dt1:.1f} s"}}
 
     if rank == 0:
-        kp = np.mean([s[0] + s[1] for s in stats]) / 2
-        st = np.mean([s[2] for s in stats])
-        line = {
-            "metric": "stereo frames/sec @1242x375 (SIFT detect+describe x2 + stereo matchFeatures)",
-            "value": fps, "unit": "stereo frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_per_64_frames": ms_per_step * 64 / B, "timed_runs": timed_runs, "h2d": h2d_line,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (i8 MFMA for exact descriptor dot products)", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: SIFT detect+describe + BF match on 1242x375 synthetic stereo, "
-                                   "~2k keypoints/image", "frames_per_step_per_gpu": B, "rows": ROWS, "cols": COLS,
-                       "mean_keypoints_per_image": float(kp), "mean_stereo_matches": float(st),
-                       "parallelism": f"frames sharded over {world} GPU(s)",
-                       "process_group": dist.get_backend() if dist is not None else None},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "full_path": full,
-            "large": large,
-        }
+        line.update({"h2d": h2d_line, "roofline": roof, "cpu_baseline": cpu, "full_path": full, "large": large})
         print(json.dumps(line), file=json_out, flush=True)
     if dist is not None:
         dist.destroy_process_group()

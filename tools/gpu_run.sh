@@ -28,18 +28,18 @@ for st in $STEPS; do
     timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
     tail -1 $O/smoke.log ;;
   bench)
-    timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+    timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
     python3 -c "import json;d=json.load(open('$O/bench.json'));r=d['roofline'];t=d['timed_runs'];print('bench',round(d['value']),round(d['ms_per_step'],3),t['ms_per_step'],r['kernel'],round(r['frac'],3),'h2d',round(d['h2d']['ms_per_step'],3));print('full',round(d['full_path']['value']),'large',round(d['large']['value']),'cpu',d['cpu_baseline']['value'])" ;;
   distbench)
-    VO_BENCH_FORCE_DIST=1 timeout -k 10 600 python3 bench.py --no-cpu --large-batch 0 > $O/distbench.json 2> $O/distbench.err \
+    VO_BENCH_FORCE_DIST=1 timeout -k 10 600 python3 bench.py --full --no-cpu --large-batch 0 > $O/distbench.json 2> $O/distbench.err \
       || { tail -20 $O/distbench.err; exit 1; }
     python3 -c "import json;d=json.loads([l for l in open('$O/distbench.json') if l.startswith('{')][0]);f=d['full_path'];print('distbench',d['config']['process_group'],round(d['value']),'full',round(f['value']),f['landmark_rows'],f['accuracy']['ate_rmse_m'])" ;;
   kprof)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kprof -o k -- python3 bench.py --steps 10 --runs 1 --warmup 2 --no-cpu --seq-frames 0 --large-batch 0 > $O/kprof_bench.json 2> $O/kprof.err
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kprof -o k -- python3 bench.py --full --steps 10 --runs 1 --warmup 2 --no-cpu --seq-frames 0 --large-batch 0 > $O/kprof_bench.json 2> $O/kprof.err
     find $O/kprof -name "*kernel_trace.csv" -delete
     echo kprof-done ;;
   seqprof)
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/seqprof -o k -- python3 bench.py --steps 2 --runs 1 --warmup 1 --no-cpu --large-batch 0 > $O/seqprof_bench.json 2> $O/seqprof.err
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/seqprof -o k -- python3 bench.py --full --steps 2 --runs 1 --warmup 1 --no-cpu --large-batch 0 > $O/seqprof_bench.json 2> $O/seqprof.err
     find $O/seqprof -name "*kernel_trace.csv" -delete
     echo seqprof-done ;;
   probe:*)
@@ -52,7 +52,7 @@ for st in $STEPS; do
     tail -5 $O/${b%.py}.txt ;;
   rehearse2)
     # two ranks on this box's one GPU over gloo (the 8-GPU node runs nccl = RCCL): per-rank loop and tail
-    VO_BENCH_BACKEND=gloo VO_BENCH_SAME_GPU=1 timeout -k 10 600 python3 bench.py --gpus 2 --no-cpu --large-batch 0 > $O/rehearse2.json 2> $O/rehearse2.err \
+    VO_BENCH_BACKEND=gloo VO_BENCH_SAME_GPU=1 timeout -k 10 600 python3 bench.py --full --gpus 2 --no-cpu --large-batch 0 > $O/rehearse2.json 2> $O/rehearse2.err \
       || { tail -20 $O/rehearse2.err; exit 1; }
     python3 -c "import json;d=json.loads([l for l in open('$O/rehearse2.json') if l.startswith('{')][0]);f=d['full_path'];print('rehearse2',d['n_gpus'],round(f['value']),f['landmark_rows'],f['accuracy']['ate_rmse_m'],f['per_rank_ms'])" ;;
   content_pmc)
@@ -70,7 +70,7 @@ for st in $STEPS; do
     v=${st#abfull:}
     for var in default ${v//,/ } default; do
       if [ $var = default ]; then unset VO_LIBPATH; else export VO_LIBPATH=$GRAFT_REPO_ROOT/tools/variants/$var/libvo.so; fi
-      timeout -k 10 300 python3 bench.py --no-cpu --large-batch 0 > $O/abf_$var.json 2>/dev/null || { echo "$var failed"; exit 1; }
+      timeout -k 10 300 python3 bench.py --full --no-cpu --large-batch 0 > $O/abf_$var.json 2>/dev/null || { echo "$var failed"; exit 1; }
       python3 -c "import json;d=json.load(open('$O/abf_$var.json'));f=d['full_path'];k=f['kernel_ms_per_step'];print('$var',round(d['value'],1),round(d['ms_per_step'],3),'full',round(f['value'],1),'refine',d['roofline']['kernel_ms_per_step'].get('k_refine'),k.get('k_refine'),'msac',k.get('k_msac'),k.get('k_msac_gen'))"
     done
     unset VO_LIBPATH ;;
@@ -116,7 +116,7 @@ for st in $STEPS; do
   batch:*)
     b=${st#batch:}
     for bb in 64 $b 64; do
-      timeout -k 10 300 python3 bench.py --no-cpu --seq-frames 0 --large-batch 0 --batch $bb > $O/batch_$bb.json 2>/dev/null || { echo "batch $bb failed"; exit 1; }
+      timeout -k 10 300 python3 bench.py --full --no-cpu --seq-frames 0 --large-batch 0 --batch $bb > $O/batch_$bb.json 2>/dev/null || { echo "batch $bb failed"; exit 1; }
       python3 -c "import json;d=json.load(open('$O/batch_$bb.json'));print('batch',$bb,round(d['value'],1),round(d['ms_per_step'],3))"
     done ;;
   attr)
