@@ -13,6 +13,8 @@
  *   vo_sift                detectSIFTFeatures + extractFeatures(...,"SIFT")
  *                          VO.m:79-84
  *   vo_match               matchFeatures(F1, F2)  VO.m:87,283,293,311,323
+ *   vo_match_ex /          [indexPairs, matchMetric] = matchFeatures(F1, F2,
+ *   vo_match_f32_ex        'Unique', u, 'MatchThreshold', t, 'MaxRatio', r)
  *   vo_track               find_remaining_points  VO.m:280-334 (4 matches +
  *                          gathers), fused on device
  *   vo_triangulate         triangulate(x1, x2, P1, P2)  VO.m:113-116,
@@ -167,6 +169,36 @@ int vo_match(vo_ctx* ctx, const uint8_t* F1, int n1, const uint8_t* F2, int n2,
  * u8 rows there.  Non-integer or out-of-range values -> VO_ERR_ARG.  Same results as vo_match. */
 int vo_match_f32(vo_ctx* ctx, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2,
                  int col_major, uint32_t* pairs, int capacity, int* n_pairs);
+
+/* matchFeatures(F1, F2, 'MatchThreshold', t, 'MaxRatio', r, 'Unique', u) with the second
+ * output: [indexPairs, matchMetric].
+ *  - match_threshold in (0, 25] percent.  MATLAB allows up to 100; libvo stops at 25, where the
+ *    SSD threshold 0.04f * 25 is exactly 1.0f: every accepted pair then has a cosine >= 0.5, the
+ *    range in which SSD = 2 - 2c is exact and strictly decreasing, which the cosine-domain ranking
+ *    of the match kernels relies on.  Larger values return VO_ERR_ARG.
+ *  - max_ratio in (0, 1].
+ *  - unique = 1 is the toolbox's findUniqueIndices rule (the forward-backward check): for every
+ *    F2 row j, back(j) = the F1 row with the smallest SSD over ALL F1 rows (not only the accepted
+ *    ones), the lowest row on ties; an accepted pair (i, j) is kept iff back(j) == i.
+ *  - reserved must be 0. */
+typedef struct {
+    float   match_threshold;   /* percent, (0, 25] */
+    float   max_ratio;         /* (0, 1] */
+    int32_t unique;            /* 0 | 1 */
+    int32_t reserved;          /* 0 */
+} vo_match_opts;
+void vo_default_match_opts(vo_match_opts* o);            /* 1.0, 0.6, 0, 0 */
+
+/* vo_match / vo_match_f32 with options and matchMetric.  opts == NULL: the context's
+ * vo_match_params, unique 0 -- the pairs are then exactly vo_match's / vo_match_f32's.  metric
+ * (may be NULL) receives [capacity] floats: metric[k] is the SSD of pair k, the value the
+ * thresholds were applied to (u8-valued rows: 2 - 2c of the exact-integer path; general single
+ * features: the float SSD).  Errors as vo_match: VO_ERR_CAPACITY, empty sets allowed, refused
+ * while step batches are pending. */
+int vo_match_ex(vo_ctx* ctx, const uint8_t* F1, int n1, const uint8_t* F2, int n2, const vo_match_opts* opts,
+                uint32_t* pairs, float* metric, int capacity, int* n_pairs);
+int vo_match_f32_ex(vo_ctx* ctx, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                    const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs);
 
 /* find_remaining_points (VO.m:280-334) on device.  old = previous frame's
  * stereo-aligned set (n_old rows, left/right row-aligned); cur = current

@@ -9,8 +9,10 @@
  *
  *   [loc, scale, ori, metric, desc, octave, layer] = vo_mex('sift', I)
  *        detectSIFTFeatures + extractFeatures(..,"Method","SIFT")        VO.m:79-84
- *   indexPairs = vo_mex('match', F1, F2)
+ *   [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...)
  *        matchFeatures(F1, F2)                                   VO.m:87,283,293,311,323
+ *        and its options 'Unique', 'MatchThreshold', 'MaxRatio' (names case-insensitive; 'Method',
+ *        'Metric', 'Prenormalized' only at their defaults; anything else: vo:matchFeatures:options)
  *   X = vo_mex('triangulate', x1, x2, P1, P2)
  *        triangulate                              VO.m:113-116, CreateLandmarksFromFeatures.m:7
  *   [A, inliers, status] = vo_mex('estworldpose', imagePoints, worldPoints, K, opts)
@@ -194,23 +196,106 @@ static void cmd_sift(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     mxFree(d);
 }
 
+/* vo_match_f32_ex through a weak reference: a gateway linked with a libvo that lacks the entry
+ * still loads and serves matchFeatures(F1, F2); options and the second output then raise
+ * vo:matchFeatures:options. */
+extern __typeof__(vo_match_f32_ex) vo_match_f32_ex __attribute__((weak));
+
+static void bad_option(const char* why, const char* name)
+{
+    mexErrMsgIdAndTxt("vo:matchFeatures:options", "matchFeatures: %s '%s' (libvo implements Unique, MatchThreshold in (0, 25], "
+                      "MaxRatio in (0, 1] and the defaults of Method, Metric and Prenormalized)", why, name);
+}
+
+static int same_nocase(const char* a, const char* b)
+{
+    for (; *a && *b; ++a, ++b) {
+        const int x = (*a >= 'A' && *a <= 'Z') ? *a + 32 : *a, y = (*b >= 'A' && *b <= 'Z') ? *b + 32 : *b;
+        if (x != y) return 0;
+    }
+    return *a == *b;
+}
+
+/* real scalar of class logical / double / single (with any_numeric: also uint8, int32, uint32) */
+static int scalar_value(const mxArray* a, int any_numeric, double* v)
+{
+    if (mxIsComplex(a) || mxGetM(a) != 1 || mxGetN(a) != 1) return 0;
+    switch (mxGetClassID(a)) {
+    case mxDOUBLE_CLASS: *v = mxGetDoubles(a)[0]; return 1;
+    case mxSINGLE_CLASS: *v = (double)mxGetSingles(a)[0]; return 1;
+    case mxLOGICAL_CLASS: if (!any_numeric) return 0; *v = mxGetLogicals(a)[0] ? 1.0 : 0.0; return 1;
+    case mxUINT8_CLASS: if (!any_numeric) return 0; *v = (double)mxGetUint8s(a)[0]; return 1;
+    case mxINT32_CLASS: if (!any_numeric) return 0; *v = (double)mxGetInt32s(a)[0]; return 1;
+    case mxUINT32_CLASS: if (!any_numeric) return 0; *v = (double)mxGetUint32s(a)[0]; return 1;
+    default: return 0;
+    }
+}
+
+/* matchFeatures' name-value pairs prhs[3..]: 1 if one of Unique / MatchThreshold / MaxRatio is
+ * given (then *o holds them over the defaults).  Method, Metric and Prenormalized are accepted
+ * only where they restate the default; anything else raises vo:matchFeatures:options. */
+static int match_options(int nrhs, const mxArray* prhs[], vo_match_opts* o)
+{
+    int given = 0;
+    o->match_threshold = 1.0f; o->max_ratio = 0.6f; o->unique = 0; o->reserved = 0;
+    if ((nrhs - 3) % 2) bad_option("a name without a value after", "features2");
+    for (int k = 3; k < nrhs; k += 2) {
+        char name[32], text[32];
+        double v = 0.0;
+        const mxArray* val = prhs[k + 1];
+        if (!mxIsChar(prhs[k]) || mxGetString(prhs[k], name, sizeof name)) bad_option("option name is not a short string:", "?");
+        if (same_nocase(name, "Unique")) {
+            if (!scalar_value(val, 1, &v)) bad_option("not a logical or numeric scalar:", name);
+            o->unique = v != 0.0;
+            given = 1;
+        } else if (same_nocase(name, "MatchThreshold") || same_nocase(name, "MaxRatio")) {
+            if (!scalar_value(val, 0, &v)) bad_option("not a double or single scalar:", name);
+            if (same_nocase(name, "MaxRatio")) o->max_ratio = (float)v; else o->match_threshold = (float)v;
+            given = 1;
+        } else if (same_nocase(name, "Method") || same_nocase(name, "Metric")) {
+            const char* dflt = same_nocase(name, "Method") ? "Exhaustive" : "SSD";
+            if (!mxIsChar(val) || mxGetString(val, text, sizeof text) || !same_nocase(text, dflt))
+                bad_option("only the default is implemented for", name);
+        } else if (same_nocase(name, "Prenormalized")) {
+            if (!scalar_value(val, 1, &v) || v != 0.0) bad_option("only the default is implemented for", name);
+        } else {
+            bad_option("unknown option", name);
+        }
+    }
+    return given;
+}
+
+/* [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...) */
 static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
 {
-    (void)nlhs;
-    need_args(nrhs, 3, "match");
+    if (nrhs < 3) need_args(nrhs, 3, "match");
+    if (nlhs > 2) mexErrMsgIdAndTxt("vo:matchFeatures:options", "matchFeatures returns at most [indexPairs, matchMetric]");
     for (int k = 1; k <= 2; ++k)
         if (mxGetM(prhs[k]) > 0) need_real(prhs[k], mxSINGLE_CLASS, -1, VO_DESC_LEN, k == 1 ? "features1" : "features2");
+    vo_match_opts opts;
+    const int ex = match_options(nrhs, prhs, &opts) || nlhs > 1;
+    if (ex && !vo_match_f32_ex)
+        mexErrMsgIdAndTxt("vo:matchFeatures:options", "this libvo has no vo_match_f32_ex: matchFeatures(F1, F2) with the default "
+                          "options and one output only");
     need_ctx(0, 0);
     const int n1 = (int)mxGetM(prhs[1]), n2 = (int)mxGetM(prhs[2]);
     int P = 0;
     uint32_t* pr = (uint32_t*)mxMalloc(sizeof(uint32_t) * 2 * ((size_t)n1 + 1));
+    float* mt = (float*)mxMalloc(sizeof(float) * ((size_t)n1 + 1));
     /* N x 128 single exactly as extractFeatures returned it: col_major = 1, ld = N */
-    check(vo_match_f32(g_ctx, n1 ? mxGetSingles(prhs[1]) : NULL, n1, n1 ? n1 : 1, n2 ? mxGetSingles(prhs[2]) : NULL, n2,
-                       n2 ? n2 : 1, 1, pr, n1 + 1, &P));
+    const float* f1 = n1 ? mxGetSingles(prhs[1]) : NULL;
+    const float* f2 = n2 ? mxGetSingles(prhs[2]) : NULL;
+    if (ex) check(vo_match_f32_ex(g_ctx, f1, n1, n1 ? n1 : 1, f2, n2, n2 ? n2 : 1, 1, &opts, pr, mt, n1 + 1, &P));
+    else check(vo_match_f32(g_ctx, f1, n1, n1 ? n1 : 1, f2, n2, n2 ? n2 : 1, 1, pr, n1 + 1, &P));
     plhs[0] = mxCreateNumericMatrix(P, 2, mxUINT32_CLASS, mxREAL);
     uint32_t* o = mxGetUint32s(plhs[0]);
     for (int i = 0; i < P; ++i) { o[i] = pr[2 * i]; o[(size_t)P + i] = pr[2 * i + 1]; }
+    if (nlhs > 1) {
+        plhs[1] = mxCreateNumericMatrix(P, 1, mxSINGLE_CLASS, mxREAL);      /* matchMetric */
+        memcpy(mxGetSingles(plhs[1]), mt, sizeof(float) * (size_t)P);
+    }
     mxFree(pr);
+    mxFree(mt);
 }
 
 static void cmd_triangulate(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])

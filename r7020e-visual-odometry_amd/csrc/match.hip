@@ -107,7 +107,10 @@ __device__ __forceinline__ v4i load_frag(const uint8_t* row, int off)
 #endif
 // NB: 32-row F1 sub-blocks per wave (MP_ROWS * NB rows per workgroup); NB = 2 runs two
 // independent MFMA chains per tile on the same F2 fragments (half the LDS reads per MFMA)
-template <int NB>
+// SWAP: the job's row side is the spec's F2 and its column side the spec's F1 (the backward pass
+// of Unique): the two multiplies of c keep the spec's operand order, (dot * inv|F1|) * inv|F2|,
+// so the backward values are the forward pass's bit for bit
+template <int NB, bool SWAP = false>
 __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_partial(const MatchJob* __restrict__ jobs, int n_jobs,
                                                        MatchTop2* __restrict__ partial, int row_cap, int n_chunks_cap)
 {
@@ -231,7 +234,8 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
                         // c = ((float)dot * inv|a|) * inv|b|, two columns at once as packed f32 muls
                         const vo_f2 fp = vo_f2{(float)(accv[sb][4 * q + i] + rk1[sb] + ck4[i]),
                                                (float)(accv[sb][4 * q + i + 1] + rk1[sb] + ck4[i + 1])};
-                        const vo_f2 cp = (fp * vo_f2{ina1[sb], ina1[sb]}) * vo_f2{ib4[i], ib4[i + 1]};
+                        const vo_f2 cp = SWAP ? (fp * vo_f2{ib4[i], ib4[i + 1]}) * vo_f2{ina1[sb], ina1[sb]}
+                                              : (fp * vo_f2{ina1[sb], ina1[sb]}) * vo_f2{ib4[i], ib4[i + 1]};
                         cv[4 * q + i] = cp.x;
                         cv[4 * q + i + 1] = cp.y;
                     }
@@ -440,6 +444,63 @@ __global__ __launch_bounds__(256) void k_match_finish(const MatchJob* __restrict
     if (tid == 0) cp.list_n[4 * f + st] = n;
 }
 
+// k_match_finish for vo_match_ex: the same merge, MatchThreshold / MaxRatio and ascending-F1
+// placement, plus matchMetric (the accepted pair's SSD, bs) and, with `unique`, the toolbox's
+// findUniqueIndices rule: an accepted pair (r, j) is kept iff r is the best F1 row of column j
+// over ALL F1 rows, lowest row on ties.  `back` holds the backward pass's partials (F2 rows x F1
+// chunks, k_match_partial<1, true>): their values are the forward c(i, j) bit for bit, and an
+// accepted pair has c >= 0.5 (MatchThreshold <= 25), where argmax c (lowest index) is argmin SSD
+// (lowest index).  With unique == 0 the pairs are exactly k_match_finish's.
+__global__ __launch_bounds__(256) void k_match_finish_unique(const MatchJob* __restrict__ jobs, const MatchTop2* __restrict__ partial,
+                                                             const MatchTop2* __restrict__ back, int row_cap, int n_chunks_cap,
+                                                             float T, float max_ratio, int unique, float* __restrict__ metric)
+{
+    __shared__ uint32_t wsum[4];
+    const int jb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const MatchJob J = jobs[jb];
+    const int n1 = job_rows(J.n1, row_cap), n2 = job_rows(J.n2, row_cap);
+    const int nch = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK, nchb = (n1 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
+    const MatchTop2* P = partial + (size_t)jb * n_chunks_cap * row_cap;
+    const MatchTop2* PB = back + (size_t)jb * n_chunks_cap * row_cap;
+    float* M = metric + (size_t)jb * row_cap;
+    uint32_t base = 0;
+    for (int r0 = 0; r0 < n1; r0 += 256) {                       // block-uniform
+        const int r = r0 + tid;
+        int acc = -1;
+        float bs = 0.0f;
+        if (r < n1) {
+            float b = -INFINITY, s = -INFINITY;
+            int i = -1;
+            for (int c = 0; c < nch; ++c) {
+                const MatchTop2 m = P[(size_t)c * row_cap + r];
+                top2c_merge(b, i, s, m.best, m.idx, m.second);
+            }
+            bs = 2.0f - 2.0f * b;
+            const float ss = 2.0f - 2.0f * s;                    // SSD of best / second best
+            acc = (i >= 0 && bs <= T && (bs / ss) <= max_ratio) ? i : -1;
+            if (unique && acc >= 0) {
+                float bb = -INFINITY, sb = -INFINITY;
+                int bi = -1;
+                for (int c = 0; c < nchb; ++c) {
+                    const MatchTop2 m = PB[(size_t)c * row_cap + acc];
+                    top2c_merge(bb, bi, sb, m.best, m.idx, m.second);
+                }
+                if (bi != r) acc = -1;
+            }
+        }
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(acc >= 0);
+        if (lane == 0) wsum[wid] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = base;
+        for (int w = 0; w < wid; ++w) before += wsum[w];
+        const uint32_t pos = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (acc >= 0 && pos < (uint32_t)J.cap) { gst(J.out_i + pos, r); gst(J.out_j + pos, acc); gst(M + pos, bs); }
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();                                          // wsum reused by the next tile
+    }
+    if (tid == 0) gst(J.out_n, (int)(base < (uint32_t)J.cap ? base : (uint32_t)J.cap));
+}
+
 // Descriptor metadata for externally supplied descriptors (vo_match on host data).
 __global__ void k_desc_meta(const uint8_t* __restrict__ desc, DescMeta* __restrict__ meta, int n)
 {
@@ -473,6 +534,31 @@ void match_free(MatchBuffers& b)
     b = MatchBuffers();
 }
 
+hipError_t match_ex_alloc(MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back)
+{
+    MatchExBuffers n;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&n.job_back, sizeof(MatchJob))) == hipSuccess &&
+        (e = hipMalloc((void**)&n.partial_back, sizeof(MatchTop2) * (size_t)b.n_chunks * b.row_cap)) == hipSuccess &&
+        (e = hipMalloc((void**)&n.metric, sizeof(float) * b.row_cap)) == hipSuccess &&
+        (e = hipMalloc((void**)&n.back, sizeof(int) * b.row_cap)) == hipSuccess &&
+        (e = hipMemcpy(n.job_back, &job_back, sizeof(MatchJob), hipMemcpyHostToDevice)) == hipSuccess) {
+        x = n;
+        return hipSuccess;
+    }
+    match_ex_free(n);
+    return e;
+}
+
+void match_ex_free(MatchExBuffers& x)
+{
+    hipFree(x.job_back);
+    hipFree(x.partial_back);
+    hipFree(x.metric);
+    hipFree(x.back);
+    x = MatchExBuffers();
+}
+
 MatchBuffers match_view(const MatchBuffers& b, int k0)
 {
     MatchBuffers v = b;
@@ -483,9 +569,6 @@ MatchBuffers match_view(const MatchBuffers& b, int k0)
     return v;
 }
 
-#ifndef VO_MATCH_FINISH
-#define VO_MATCH_FINISH 1         // 0: k_match_merge + k_match_compact (+ k_compose) as separate launches
-#endif
 void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, const vo_match_params& p, hipStream_t s,
                   const MatchCompose* compose)
 {
@@ -528,6 +611,21 @@ void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, con
 void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, const vo_match_params& p, hipStream_t s)
 {
     match_launch(b, d_jobs, n_jobs, p, s, nullptr);
+}
+
+// vo_match_ex: one job with explicit thresholds, matchMetric and (optionally) Unique.  The
+// forward partials go to b's slot 0 as in match_launch; with `unique` the backward job (the same
+// two descriptor sets with the sides exchanged) runs the SWAP instantiation into x.partial_back.
+void match_launch_ex(const MatchBuffers& b, const MatchJob* d_job, const MatchExBuffers& x, const vo_match_params& p, int unique,
+                     hipStream_t s)
+{
+    VO_LAUNCH_NAMED("k_match_partial", k_match_partial<1>, dim3(VO_STEREO_GRID), dim3(256), 0, s, d_job, 1, b.partial, b.row_cap,
+                    b.n_chunks);
+    if (unique)
+        VO_LAUNCH_NAMED("k_match_partial_back", (k_match_partial<1, true>), dim3(VO_STEREO_GRID), dim3(256), 0, s,
+                        (const MatchJob*)x.job_back, 1, x.partial_back, b.row_cap, b.n_chunks);
+    VO_LAUNCH(k_match_finish_unique, dim3(1), dim3(256), 0, s, d_job, (const MatchTop2*)b.partial,
+              (const MatchTop2*)x.partial_back, b.row_cap, b.n_chunks, p.match_threshold * 0.04f, p.max_ratio, unique, x.metric);
 }
 
 // single-precision descriptor matrix (MATLAB's extractFeatures output: n x 128 single, integer
@@ -627,6 +725,66 @@ void match_f32_launch(const float* F1, int n1, int ld1, const float* F2, int n2,
     if (n2 > 0) VO_LAUNCH(k_f32_norm, dim3((n2 + 255) / 256), dim3(256), 0, s, F2, n2, ld2, col_major, 1, BT);
     VO_LAUNCH(k_match_f32, dim3(std::min(n1, 8192)), dim3(64), 0, s, A, n1, BT, n2, p.match_threshold * 0.04f, p.max_ratio,
               res);
+}
+
+// k_match_f32 for vo_match_f32_ex: the same scores and top-2 per row; besides the accepted column
+// (res, as k_match_f32 writes it) it stores the row's best SSD (best: matchMetric) and the best
+// column regardless of the thresholds (arg: the backward pass of Unique).  Outputs may be null.
+__global__ __launch_bounds__(64) void k_match_f32_ex(const float* __restrict__ A, int n1, const float* __restrict__ BT, int n2,
+                                                     float T, float max_ratio, int* __restrict__ res, int* __restrict__ arg,
+                                                     float* __restrict__ best_out)
+{
+    __shared__ float a[VO_DESC_LEN];
+    const int lane = threadIdx.x;
+    for (int i = blockIdx.x; i < n1; i += gridDim.x) {
+        a[lane] = A[(size_t)i * VO_DESC_LEN + lane];
+        a[lane + 64] = A[(size_t)i * VO_DESC_LEN + lane + 64];
+        __syncthreads();
+        float best = INFINITY, second = INFINITY;
+        int bidx = -1;
+        for (int j = lane; j < n2; j += 64) {
+            float ssd = 0.0f;
+            for (int k = 0; k < VO_DESC_LEN; ++k) {
+                const float d = a[k] - BT[(size_t)k * n2 + j];
+                ssd = fmaf(d, d, ssd);
+            }
+            if (ssd < best) { second = best; best = ssd; bidx = j; }
+            else if (ssd < second) second = ssd;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const float b2 = __shfl_xor(best, off), s2 = __shfl_xor(second, off);
+            const int i2 = __shfl_xor(bidx, off);
+            const float ns = fminf(fminf(second, s2), fmaxf(best, b2));
+            if (i2 >= 0 && (bidx < 0 || b2 < best || (b2 == best && i2 < bidx))) { best = b2; bidx = i2; }
+            second = ns;
+        }
+        if (lane == 0) {
+            if (res) res[i] = (bidx >= 0 && best <= T && best / second <= max_ratio) ? bidx : -1;
+            if (arg) arg[i] = bidx;
+            if (best_out) best_out[i] = best;
+        }
+        __syncthreads();
+    }
+}
+
+// vo_match_f32_ex on general features: the forward pass as match_f32_launch plus the metric; with
+// `unique`, A and BT are then rewritten with the sides exchanged (stream order) and the same
+// kernel gives back[j], the best F1 row of every F2 row -- the fmaf chain of (a_k - b_k)^2 is
+// symmetric in its operands, so these are the forward scores.
+void match_f32_launch_ex(const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, float* A, float* BT,
+                         int* res, float* best, int* back, const vo_match_params& p, int unique, hipStream_t s)
+{
+    if (n1 <= 0) return;
+    VO_LAUNCH(k_f32_norm, dim3((n1 + 255) / 256), dim3(256), 0, s, F1, n1, ld1, col_major, 0, A);
+    if (n2 > 0) VO_LAUNCH(k_f32_norm, dim3((n2 + 255) / 256), dim3(256), 0, s, F2, n2, ld2, col_major, 1, BT);
+    VO_LAUNCH(k_match_f32_ex, dim3(std::min(n1, 8192)), dim3(64), 0, s, (const float*)A, n1, (const float*)BT, n2,
+              p.match_threshold * 0.04f, p.max_ratio, res, (int*)nullptr, best);
+    if (!unique || n2 <= 0) return;
+    VO_LAUNCH(k_f32_norm, dim3((n2 + 255) / 256), dim3(256), 0, s, F2, n2, ld2, col_major, 0, A);
+    VO_LAUNCH(k_f32_norm, dim3((n1 + 255) / 256), dim3(256), 0, s, F1, n1, ld1, col_major, 1, BT);
+    VO_LAUNCH(k_match_f32_ex, dim3(std::min(n2, 8192)), dim3(64), 0, s, (const float*)A, n2, (const float*)BT, n1, 0.0f, 0.0f,
+              (int*)nullptr, back, (float*)nullptr);
 }
 
 void desc_meta_launch(const uint8_t* desc, DescMeta* meta, int n, hipStream_t s)

@@ -109,6 +109,7 @@ struct vo_ctx {
     float* d_fa = nullptr;
     float* d_fbt = nullptr;
     int* d_fres = nullptr;
+    MatchExBuffers mx;               // vo_match_ex / vo_match_f32_ex (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     GeomBuffers gb;
@@ -178,6 +179,7 @@ void vo_default_sift_params(vo_sift_params* p)
     p->upsample = 1; p->max_keypoints = 16384;
 }
 void vo_default_match_params(vo_match_params* p) { p->match_threshold = 1.0f; p->max_ratio = 0.6f; }
+void vo_default_match_opts(vo_match_opts* o) { o->match_threshold = 1.0f; o->max_ratio = 0.6f; o->unique = 0; o->reserved = 0; }
 void vo_default_ransac_params(vo_ransac_params* p)
 {
     p->max_num_trials = 1000; p->confidence = 99.0; p->max_reprojection_error = 1.0; p->seed = 0x5EED;
@@ -240,6 +242,7 @@ static void destroy_buffers(vo_ctx* c)
     hipFree(c->d_img); hipFree(c->d_cm); hipFree(c->d_fd[0]); hipFree(c->d_fd[1]); hipFree(c->d_fm[0]); hipFree(c->d_fm[1]);
     hipFree(c->d_ff[0]); hipFree(c->d_ff[1]); hipFree(c->d_bad);
     hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
+    match_ex_free(c->mx);
     hipFree(c->d_fn); hipFree(c->d_mi); hipFree(c->d_mj); hipFree(c->d_mn);
     hipFree(c->d_lmX); hipFree(c->d_lmkeep); hipFree(c->d_lmw_pose); hipFree(c->d_lmw_off);
     c->d_lmX = nullptr; c->d_lmkeep = nullptr; c->d_lmw_pose = nullptr; c->d_lmw_off = nullptr;
@@ -585,14 +588,16 @@ int vo_match(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, ui
     return match_staged(c, n1, n2, pairs, capacity, n_pairs, "vo_match");
 }
 
-int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
-                 uint32_t* pairs, int capacity, int* n_pairs)
+// vo_match_f32 / vo_match_f32_ex: check the arguments, copy both matrices to the device as they
+// lie (d_ff) and pack them to u8 rows (d_fd); *bad = 1 if some value is not an integer in [0, 255]
+static int stage_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, int* bad,
+                     const char* who)
 {
     if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2) || (col_major != 0 && col_major != 1))
-        return fail(c, VO_ERR_ARG, "vo_match_f32: bad arguments");
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
     if ((n1 && ld1 < (col_major ? n1 : VO_DESC_LEN)) || (n2 && ld2 < (col_major ? n2 : VO_DESC_LEN)))
-        return fail(c, VO_ERR_ARG, "vo_match_f32: leading dimension too small");
-    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match_f32: more rows than max_keypoints");
+        return fail(c, VO_ERR_ARG, "%s: leading dimension too small", who);
+    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
     BEGIN_CALL(c);
     HIPC(c, hipMemsetAsync(c->d_bad, 0, sizeof(int), c->stream));
     const float* src[2] = {F1, F2};
@@ -601,31 +606,43 @@ int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, i
         if (!n[s]) continue;
         // the matrix as it lies in host memory (MATLAB: n x 128 column-major, ld = n), one copy
         const size_t elems = col_major ? (size_t)ld[s] * (VO_DESC_LEN - 1) + n[s] : (size_t)ld[s] * (n[s] - 1) + VO_DESC_LEN;
-        if (elems > (size_t)c->sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "vo_match_f32: matrix exceeds staging");
+        if (elems > (size_t)c->sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "%s: matrix exceeds staging", who);
         HIPC(c, hipMemcpyAsync(c->d_ff[s], src[s], sizeof(float) * elems, hipMemcpyHostToDevice, c->stream));
         pack_f32_desc_launch(c->d_ff[s], n[s], ld[s], col_major, c->d_fd[s], c->d_bad, c->stream);
     }
+    HIPC(c, hipMemcpyAsync(bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+// the general-float path's buffers (normalised F1, transposed F2, per-row result)
+static int f32_buffers(vo_ctx* c, const char* who)
+{
+    if (c->d_fa && c->d_fbt && c->d_fres) return VO_OK;
+    // all three or none: a failed allocation leaves the context without any of them, so the
+    // next call allocates again instead of launching on a null buffer
+    const size_t fb = sizeof(float) * (size_t)c->sb.kp_cap * VO_DESC_LEN;
+    float* fa = nullptr; float* fbt = nullptr; int* fres = nullptr;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&fa, fb)) != hipSuccess || (e = hipMalloc((void**)&fbt, fb)) != hipSuccess ||
+        (e = hipMalloc((void**)&fres, sizeof(int) * c->sb.kp_cap)) != hipSuccess) {
+        hipFree(fa); hipFree(fbt); hipFree(fres);
+        return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
+    c->d_fa = fa; c->d_fbt = fbt; c->d_fres = fres;
+    return VO_OK;
+}
+
+int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                 uint32_t* pairs, int capacity, int* n_pairs)
+{
     int bad = 0;
-    HIPC(c, hipMemcpyAsync(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    int rc = finish(c);
+    int rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, "vo_match_f32");
     if (rc) return rc;
     // u8-valued rows (libvo / SIFT descriptors, what VO.m passes): the exact-integer spec of the
     // hot path; any other single features: the float SSD spec (match_f32_launch)
     if (!bad) return match_staged(c, n1, n2, pairs, capacity, n_pairs, "vo_match_f32");
-    if (!c->d_fa || !c->d_fbt || !c->d_fres) {
-        // all three or none: a failed allocation leaves the context without any of them, so the
-        // next call allocates again instead of launching on a null buffer
-        const size_t fb = sizeof(float) * (size_t)c->sb.kp_cap * VO_DESC_LEN;
-        float* fa = nullptr; float* fbt = nullptr; int* fres = nullptr;
-        hipError_t e;
-        if ((e = hipMalloc((void**)&fa, fb)) != hipSuccess || (e = hipMalloc((void**)&fbt, fb)) != hipSuccess ||
-            (e = hipMalloc((void**)&fres, sizeof(int) * c->sb.kp_cap)) != hipSuccess) {
-            hipFree(fa); hipFree(fbt); hipFree(fres);
-            return fail(c, VO_ERR_HIP, "vo_match_f32: %s", hipGetErrorString(e));
-        }
-        hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
-        c->d_fa = fa; c->d_fbt = fbt; c->d_fres = fres;
-    }
+    if ((rc = f32_buffers(c, "vo_match_f32")) != VO_OK) return rc;
     match_f32_launch(c->d_ff[0], n1, ld1, c->d_ff[1], n2, ld2, col_major, c->d_fa, c->d_fbt, c->d_fres, c->mp, c->stream);
     std::vector<int> res((size_t)n1 + 1);
     if (n1) HIPC(c, hipMemcpyAsync(res.data(), c->d_fres, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
@@ -639,6 +656,119 @@ int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, i
     }
     if (n_pairs) *n_pairs = P;
     if (P > capacity) return fail(c, VO_ERR_CAPACITY, "vo_match_f32: %d pairs exceed capacity %d", P, capacity);
+    return VO_OK;
+}
+
+// ---- matchFeatures with options: explicit thresholds, matchMetric, Unique -------------------
+// opts == NULL: the context's parameters, unique 0
+static int match_opts_resolve(vo_ctx* c, const vo_match_opts* o, vo_match_params* p, int* unique, const char* who)
+{
+    *p = c->mp;
+    *unique = 0;
+    if (!o) return VO_OK;
+    if (!(o->match_threshold > 0.0f && o->match_threshold <= 25.0f))
+        return fail(c, VO_ERR_ARG, "%s: MatchThreshold %g outside (0, 25]", who, (double)o->match_threshold);
+    if (!(o->max_ratio > 0.0f && o->max_ratio <= 1.0f))
+        return fail(c, VO_ERR_ARG, "%s: MaxRatio %g outside (0, 1]", who, (double)o->max_ratio);
+    if ((o->unique != 0 && o->unique != 1) || o->reserved != 0)
+        return fail(c, VO_ERR_ARG, "%s: unique must be 0 or 1 and reserved 0", who);
+    p->match_threshold = o->match_threshold;
+    p->max_ratio = o->max_ratio;
+    *unique = o->unique;
+    return VO_OK;
+}
+
+static int match_ex_buffers(vo_ctx* c, const char* who)
+{
+    if (c->mx.job_back) return VO_OK;
+    MatchJob J;                                          // the vo_match job with its sides exchanged
+    memset(&J, 0, sizeof(J));
+    J.d1 = c->d_fd[1]; J.m1 = c->d_fm[1]; J.n1 = c->d_fn + 1;
+    J.d2 = c->d_fd[0]; J.m2 = c->d_fm[0]; J.n2 = c->d_fn;
+    const hipError_t e = match_ex_alloc(c->mx, c->mb, J);
+    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return VO_OK;
+}
+
+// match_staged with options: d_fd[0] (n1 rows) / d_fd[1] (n2 rows) are staged; inside a call
+static int match_staged_ex(vo_ctx* c, int n1, int n2, const vo_match_params& p, int unique, uint32_t* pairs, float* metric,
+                           int capacity, int* n_pairs, const char* who)
+{
+    int rc = match_ex_buffers(c, who);
+    if (rc) return rc;
+    int nn[2] = {n1, n2};
+    HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
+    desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
+    desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
+    match_launch_ex(c->mb, c->d_jobs + job_single(c), c->mx, p, unique, c->stream);
+    int P = 0;
+    HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    rc = finish(c);
+    if (rc) return rc;
+    if (n_pairs) *n_pairs = P;
+    const int m = std::min(P, capacity);
+    if (m > 0 && pairs) {
+        std::vector<int> ii(m), jj(m);
+        HIPC(c, hipMemcpy(ii.data(), c->d_mi, sizeof(int) * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(jj.data(), c->d_mj, sizeof(int) * m, hipMemcpyDeviceToHost));
+        for (int k = 0; k < m; ++k) { pairs[2 * k] = (uint32_t)ii[k] + 1; pairs[2 * k + 1] = (uint32_t)jj[k] + 1; }
+    }
+    if (m > 0 && metric) HIPC(c, hipMemcpy(metric, c->mx.metric, sizeof(float) * m, hipMemcpyDeviceToHost));
+    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
+    return VO_OK;
+}
+
+int vo_match_ex(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, const vo_match_opts* opts, uint32_t* pairs,
+                float* metric, int capacity, int* n_pairs)
+{
+    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "vo_match_ex: bad arguments");
+    vo_match_params p;
+    int unique = 0;
+    int rc = match_opts_resolve(c, opts, &p, &unique, "vo_match_ex");
+    if (rc) return rc;
+    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match_ex: more rows than max_keypoints");
+    BEGIN_CALL(c);
+    if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    return match_staged_ex(c, n1, n2, p, unique, pairs, metric, capacity, n_pairs, "vo_match_ex");
+}
+
+int vo_match_f32_ex(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                    const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs)
+{
+    if (!c) return fail(c, VO_ERR_ARG, "vo_match_f32_ex: bad arguments");
+    vo_match_params p;
+    int unique = 0;
+    int rc = match_opts_resolve(c, opts, &p, &unique, "vo_match_f32_ex");
+    if (rc) return rc;
+    int bad = 0;
+    if ((rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, "vo_match_f32_ex")) != VO_OK) return rc;
+    if (!bad) {
+        BEGIN_CALL(c);
+        return match_staged_ex(c, n1, n2, p, unique, pairs, metric, capacity, n_pairs, "vo_match_f32_ex");
+    }
+    if ((rc = f32_buffers(c, "vo_match_f32_ex")) != VO_OK || (rc = match_ex_buffers(c, "vo_match_f32_ex")) != VO_OK) return rc;
+    BEGIN_CALL(c);
+    match_f32_launch_ex(c->d_ff[0], n1, ld1, c->d_ff[1], n2, ld2, col_major, c->d_fa, c->d_fbt, c->d_fres, c->mx.metric,
+                        c->mx.back, p, unique, c->stream);
+    std::vector<int> res((size_t)n1 + 1), back((size_t)n2 + 1);
+    std::vector<float> best((size_t)n1 + 1);
+    if (n1) HIPC(c, hipMemcpyAsync(res.data(), c->d_fres, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
+    if (n1) HIPC(c, hipMemcpyAsync(best.data(), c->mx.metric, sizeof(float) * n1, hipMemcpyDeviceToHost, c->stream));
+    if (unique && n1 && n2) HIPC(c, hipMemcpyAsync(back.data(), c->mx.back, sizeof(int) * n2, hipMemcpyDeviceToHost, c->stream));
+    rc = finish(c);
+    if (rc) return rc;
+    int P = 0;
+    for (int i = 0; i < n1; ++i) {
+        if (res[i] < 0 || (unique && back[res[i]] != i)) continue;
+        if (P < capacity) {
+            if (pairs) { pairs[2 * P] = (uint32_t)i + 1; pairs[2 * P + 1] = (uint32_t)res[i] + 1; }
+            if (metric) metric[P] = best[i];
+        }
+        ++P;
+    }
+    if (n_pairs) *n_pairs = P;
+    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "vo_match_f32_ex: %d pairs exceed capacity %d", P, capacity);
     return VO_OK;
 }
 

@@ -253,6 +253,11 @@ struct MatchBuffers {
                                      // columns in one chunk, match -10 % isolated, full path +1.3 %, r06_y)
 #endif
 
+#ifndef VO_MATCH_FINISH
+#define VO_MATCH_FINISH 1            // 1: k_match_finish (merge + compact, and a tracking step's index composition, in one
+                                     // launch); 0: k_match_merge + k_match_compact (+ k_compose) as separate launches
+#endif
+
 hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap);
 // View whose job slot 0 is slot k0 of b (partial-result rows of jobs k0, k0+1, ...).
 MatchBuffers match_view(const MatchBuffers& b, int k0);
@@ -272,6 +277,24 @@ void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, con
                   hipStream_t s, const MatchCompose* compose);
 void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, const vo_match_params& p,
                   hipStream_t s);
+// vo_match_ex / vo_match_f32_ex (explicit thresholds, matchMetric, Unique): what they need beyond
+// MatchBuffers, allocated by the first such call.  job_back is the single job with its two sides
+// exchanged, partial_back its partial slot [n_chunks][row_cap] (rows = F2, chunks over F1),
+// metric the accepted pairs' SSD in output order (u8 path) or per F1 row (float path), back the
+// float path's best F1 row per F2 row.
+struct MatchExBuffers {
+    MatchJob* job_back = nullptr;
+    MatchTop2* partial_back = nullptr;
+    float* metric = nullptr;
+    int* back = nullptr;
+};
+hipError_t match_ex_alloc(MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back);   // all or nothing
+void match_ex_free(MatchExBuffers& x);
+// d_job: the job (device); its partials use b's slot 0 as in match_launch(b, d_job, 1, ...)
+void match_launch_ex(const MatchBuffers& b, const MatchJob* d_job, const MatchExBuffers& x, const vo_match_params& p, int unique,
+                     hipStream_t s);
+void match_f32_launch_ex(const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, float* A, float* BT,
+                         int* res, float* best, int* back, const vo_match_params& p, int unique, hipStream_t s);
 void desc_meta_launch(const uint8_t* desc, DescMeta* meta, int n, hipStream_t s);
 void pack_f32_desc_launch(const float* F, int n, int ld, int col_major, uint8_t* out, int* bad, hipStream_t s);
 // matchFeatures on general single features (not u8-valued): normalised rows A [n1][128], F2

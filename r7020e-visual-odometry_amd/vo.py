@@ -53,6 +53,10 @@ class MatchParams(C.Structure):
     _fields_ = [("match_threshold", C.c_float), ("max_ratio", C.c_float)]
 
 
+class MatchOpts(C.Structure):
+    _fields_ = [("match_threshold", C.c_float), ("max_ratio", C.c_float), ("unique", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RansacParams(C.Structure):
     _fields_ = [("max_num_trials", C.c_int32), ("confidence", C.c_double),
                 ("max_reprojection_error", C.c_double), ("seed", C.c_uint32)]
@@ -94,7 +98,7 @@ EXPORTS = [
     "vo_kernel_times", "vo_set_frame_index", "vo_set_concurrency",
     "vo_set_landmark_frame", "vo_get_landmark_rows", "vo_landmarks_to_world", "vo_match_f32",
     "vo_sift_ex", "vo_step_batch_ex", "vo_chain_poses", "vo_landmarks_to_world_frames", "vo_landmarks_world_dev",
-    "vo_fetch_candidate_counts",
+    "vo_fetch_candidate_counts", "vo_default_match_opts", "vo_match_ex", "vo_match_f32_ex",
 ]
 
 # the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the experimental kernels kept
@@ -142,6 +146,11 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_step_batch_ex.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(StepOut)]
     L.vo_match_f32.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int, C.c_int, C.c_int,
                                P(C.c_uint32), C.c_int, P(C.c_int)]
+    L.vo_default_match_opts.argtypes = [P(MatchOpts)]
+    L.vo_match_ex.argtypes = [vp, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(MatchOpts), P(C.c_uint32), P(C.c_float),
+                              C.c_int, P(C.c_int)]
+    L.vo_match_f32_ex.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int, C.c_int, C.c_int, P(MatchOpts),
+                                  P(C.c_uint32), P(C.c_float), C.c_int, P(C.c_int)]
     L.vo_track.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int,
                            P(C.c_uint32), C.c_int, P(C.c_int)]
     L.vo_triangulate.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double)]
@@ -289,20 +298,37 @@ class Context:
         return kps[: n.value].copy(), desc[: n.value].copy()
 
     # ---- matchFeatures ----
-    def match(self, F1: np.ndarray, F2: np.ndarray) -> np.ndarray:
+    def _match_opts(self, unique, match_threshold, max_ratio) -> MatchOpts:
+        """The options of vo_match_ex / vo_match_f32_ex; an omitted threshold is the context's."""
+        return MatchOpts(self.match_params.match_threshold if match_threshold is None else match_threshold,
+                         self.match_params.max_ratio if max_ratio is None else max_ratio, int(bool(unique)), 0)
+
+    def match(self, F1: np.ndarray, F2: np.ndarray, *, unique: bool = False, match_threshold: float | None = None,
+              max_ratio: float | None = None, return_metric: bool = False):
+        """matchFeatures(F1, F2) on uint8 descriptors.  The keywords are matchFeatures' Unique,
+        MatchThreshold (percent, (0, 25]) and MaxRatio ((0, 1]); return_metric=True returns
+        (pairs, matchMetric) -- vo_match_ex.  Without keywords: vo_match."""
         F1 = np.ascontiguousarray(F1, np.uint8)
         F2 = np.ascontiguousarray(F2, np.uint8)
         cap = max(F1.shape[0], 1)
         pairs = np.zeros((cap, 2), np.uint32)
         n = C.c_int(0)
-        self._check(self.lib.vo_match(self.h, _p(F1, C.c_uint8), F1.shape[0], _p(F2, C.c_uint8), F2.shape[0],
-                                      _p(pairs, C.c_uint32), cap, C.byref(n)))
-        return pairs[: n.value].copy()
+        if not unique and match_threshold is None and max_ratio is None and not return_metric:
+            self._check(self.lib.vo_match(self.h, _p(F1, C.c_uint8), F1.shape[0], _p(F2, C.c_uint8), F2.shape[0],
+                                          _p(pairs, C.c_uint32), cap, C.byref(n)))
+            return pairs[: n.value].copy()
+        opts = self._match_opts(unique, match_threshold, max_ratio)
+        metric = np.zeros(cap, np.float32)
+        self._check(self.lib.vo_match_ex(self.h, _p(F1, C.c_uint8), F1.shape[0], _p(F2, C.c_uint8), F2.shape[0], C.byref(opts),
+                                         _p(pairs, C.c_uint32), _p(metric, C.c_float), cap, C.byref(n)))
+        return (pairs[: n.value].copy(), metric[: n.value].copy()) if return_metric else pairs[: n.value].copy()
 
-    def match_f32(self, F1: np.ndarray, F2: np.ndarray) -> np.ndarray:
+    def match_f32(self, F1: np.ndarray, F2: np.ndarray, *, unique: bool = False, match_threshold: float | None = None,
+                  max_ratio: float | None = None, return_metric: bool = False):
         """matchFeatures on single-precision n x 128 matrices in their own storage order
         (vo_match_f32): a Fortran-ordered array (MATLAB's layout) goes through without a
-        transpose, a C-ordered one (any row stride) likewise."""
+        transpose, a C-ordered one (any row stride) likewise.  Keywords as for match()
+        (vo_match_f32_ex)."""
         def view(F):
             F = np.asarray(F)
             if F.dtype != np.float32 or F.ndim != 2 or F.shape[1] != 128:
@@ -322,9 +348,15 @@ class Context:
         n = C.c_int(0)
         pa = A.ctypes.data_as(C.POINTER(C.c_float)) if A.shape[0] else None
         pb = B.ctypes.data_as(C.POINTER(C.c_float)) if B.shape[0] else None
-        self._check(self.lib.vo_match_f32(self.h, pa, A.shape[0], la, pb, B.shape[0], lb, order,
-                                          _p(pairs, C.c_uint32), cap, C.byref(n)))
-        return pairs[: n.value].copy()
+        if not unique and match_threshold is None and max_ratio is None and not return_metric:
+            self._check(self.lib.vo_match_f32(self.h, pa, A.shape[0], la, pb, B.shape[0], lb, order,
+                                              _p(pairs, C.c_uint32), cap, C.byref(n)))
+            return pairs[: n.value].copy()
+        opts = self._match_opts(unique, match_threshold, max_ratio)
+        metric = np.zeros(cap, np.float32)
+        self._check(self.lib.vo_match_f32_ex(self.h, pa, A.shape[0], la, pb, B.shape[0], lb, order, C.byref(opts),
+                                             _p(pairs, C.c_uint32), _p(metric, C.c_float), cap, C.byref(n)))
+        return (pairs[: n.value].copy(), metric[: n.value].copy()) if return_metric else pairs[: n.value].copy()
 
     # ---- benchmark workload: SIFT + stereo match of B pairs resident on device ----
     def sift_match_batch_dev(self, d_lefts: int, d_rights: int, B: int, stats: bool = True):
@@ -619,6 +651,9 @@ def extractFeatures(I: np.ndarray, points=None, Method: str = "SIFT"):
     return desc, kps
 
 
-def matchFeatures(features1: np.ndarray, features2: np.ndarray) -> np.ndarray:
-    """matchFeatures defaults (Exhaustive, SSD, MatchThreshold 1, MaxRatio 0.6)."""
-    return _default_ctx(375, 1242).match(features1, features2)
+def matchFeatures(features1: np.ndarray, features2: np.ndarray, *, unique: bool = False, match_threshold: float | None = None,
+                  max_ratio: float | None = None, return_metric: bool = False):
+    """matchFeatures (Exhaustive, SSD; defaults MatchThreshold 1, MaxRatio 0.6, Unique false).
+    Keywords as for Context.match; return_metric=True returns (indexPairs, matchMetric)."""
+    return _default_ctx(375, 1242).match(features1, features2, unique=unique, match_threshold=match_threshold,
+                                         max_ratio=max_ratio, return_metric=return_metric)
