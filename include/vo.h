@@ -10,6 +10,9 @@
  *
  *   entry point            replaces (reference call site)
  *   ---------------------  ---------------------------------------------------
+ *   vo_undistort /         undistortImage(I, intrinsics)  VO.m:75-76 (Brown-Conrady
+ *   vo_undistort_batch_dev remap, bilinear); vo_set_distortion puts it ahead of
+ *   vo_set_distortion      the scale space of the loop-body entries
  *   vo_sift                detectSIFTFeatures + extractFeatures(...,"SIFT")
  *                          VO.m:79-84
  *   vo_match               matchFeatures(F1, F2)  VO.m:87,283,293,311,323
@@ -155,6 +158,43 @@ int vo_sift(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld,
  * transpose on the host; the device transposes).  col_major = 0 is vo_sift. */
 int vo_sift_ex(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld, int col_major,
                vo_keypoint* kps, uint8_t* desc, int capacity, int* n_out);
+
+/* ---- undistortImage (VO.m:75-76) --------------------------------------- */
+/* One camera's cameraIntrinsics: Brown-Conrady radial + tangential distortion.  The arithmetic
+ * is spelled out in vo_spec.h (vo_undistort_pos / vo_undistort_u8): f64 sampling map, bilinear
+ * taps, 0 outside the image, rint back to uint8 -- kitti.undistort bit for bit. */
+typedef struct {
+    double K[9];           /* this camera's intrinsics, row-major, K[1] = skew, K[3] = 0, last row 0 0 1;
+                              principal point in 0-based pixel indices (MATLAB's PrincipalPoint - 1) */
+    double radial[3];      /* k1 k2 k3  (cameraIntrinsics RadialDistortion; k3 = 0 for two) */
+    double tangential[2];  /* p1 p2 */
+} vo_distortion;
+
+/* J = undistortImage(I, intrinsics) for host buffers: OutputView 'same', bilinear, FillValues 0.
+ * rows / cols must be the context's (as for vo_sift_ex); img as vo_sift_ex takes it (col_major,
+ * ld); out has the input's storage order with leading dimension ld_out, and the bytes of each of
+ * its lines beyond cols (beyond rows for column-major storage) are left untouched.  VO_ERR_ARG:
+ * a non-finite coefficient or K entry, fx or fy zero, K[3] non-zero, a last row other than 0 0 1,
+ * mismatched sizes, ld / ld_out too small. */
+int vo_undistort(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld, int col_major,
+                 const vo_distortion* d, uint8_t* out, int ld_out);
+/* The same for B >= 1 tightly packed row-major device frames (rows*cols bytes each) of one
+ * camera, stream-ordered on vo_stream(); d_out must not overlap d_in (VO_ERR_ARG). */
+int vo_undistort_batch_dev(vo_ctx* ctx, const uint8_t* d_in, int B, const vo_distortion* d,
+                           uint8_t* d_out);
+/* VO.m:75-76 inside the loop body: once set, vo_step, vo_step_batch, vo_step_batch_ex,
+ * vo_step_batch_dev, vo_step_submit_dev and vo_sift_match_batch_dev undistort every frame on the
+ * device (one k_undistort launch per batch part, both cameras) ahead of the scale space.  vo_sift /
+ * vo_sift_ex replace detectSIFTFeatures alone and do not.  A NULL side, or one whose five
+ * coefficients are all zero, passes through; with both sides passing through nothing is launched
+ * or allocated and every result is that of a context that never set a distortion.  The first
+ * non-trivial call allocates the rectified frames (2 x max_batch x rows x cols bytes).
+ * VO_ERR_STATE while step batches are pending. */
+int vo_set_distortion(vo_ctx* ctx, const vo_distortion* left, const vo_distortion* right);
+/* Diagnostic (like vo_fetch_gaussian): the undistorted image 2*frame + side of the last batched
+ * call, rows*cols bytes row-major (capacity in bytes).  Synchronises like the other vo_fetch_*
+ * calls.  VO_ERR_STATE when no distortion is set. */
+int vo_fetch_rectified(vo_ctx* ctx, int image, uint8_t* out, int capacity);
 
 /* matchFeatures(F1, F2) on SIFT descriptors (uint8 rows of 128).
  * pairs[capacity][2] 1-based; *n_pairs = matches found. */

@@ -392,4 +392,47 @@ VO_HD int vo_reflect101(int p, int n)
     return p;
 }
 
+/* ------------------------------------------------------------------------ */
+/* undistortImage (VO.m:75-76): Brown-Conrady sampling map, bilinear taps,   */
+/* 0 outside, rint back to u8.  f64 throughout, no contraction; every        */
+/* expression below is kitti.undistort_map / kitti.undistort term by term,   */
+/* in the order Python parses them (k2 * r2 * r2 = (k2 * r2) * r2,           */
+/* 2.0 * p1 * x * y = ((2 * p1) * x) * y).  Pixel indices (u, v) are         */
+/* 0-based (u = column); s is the skew K[0][1].                              */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+    double fx, fy, s, cx, cy;     /* K[0][0], K[1][1], K[0][1], K[0][2], K[1][2] */
+    double k1, k2, k3, p1, p2;    /* radial, tangential */
+} vo_bc_cam;
+
+/* where output pixel (u, v) samples the distorted image */
+VO_HD void vo_undistort_pos(const vo_bc_cam* m, int u, int v, double* us, double* vs)
+{
+    double y = ((double)v - m->cy) / m->fy;
+    double x = ((double)u - m->cx - m->s * y) / m->fx;
+    double r2 = x * x + y * y;
+    double rad = 1.0 + m->k1 * r2 + m->k2 * r2 * r2 + m->k3 * r2 * r2 * r2;
+    double xd = x * rad + 2.0 * m->p1 * x * y + m->p2 * (r2 + 2.0 * x * x);
+    double yd = y * rad + m->p1 * (r2 + 2.0 * y * y) + 2.0 * m->p2 * x * y;
+    *us = m->fx * xd + m->s * yd + m->cx;
+    *vs = m->fy * yd + m->cy;
+}
+
+/* A position outside [-1, cols) x [-1, rows) has no tap inside the image and gives 0; NaN and
+ * +-inf fail the comparisons, so the test is made here, in f64, before any integer conversion. */
+VO_HD int vo_undistort_inside(double us, double vs, int rows, int cols)
+{
+    return us >= -1.0 && us < (double)cols && vs >= -1.0 && vs < (double)rows;
+}
+
+/* the four taps (0.0 for a tap outside the image) at fractions ax = us - floor(us),
+ * ay = vs - floor(vs), summed left to right, rounded half to even and clamped to u8 */
+VO_HD uint8_t vo_undistort_u8(double t00, double t01, double t10, double t11, double ax, double ay)
+{
+    double o = t00 * (1.0 - ax) * (1.0 - ay) + t01 * ax * (1.0 - ay) + t10 * (1.0 - ax) * ay + t11 * ax * ay;
+    o = rint(o);
+    o = o < 0.0 ? 0.0 : (o > 255.0 ? 255.0 : o);
+    return (uint8_t)o;
+}
+
 #endif /* VO_SPEC_H */

@@ -2,11 +2,19 @@
  * vo_mex.c — MATLAB MEX gateway of libvo: the reference-side binding of the drop-in boundary.
  *
  * VO.m calls Computer Vision Toolbox functions; MATLAB resolves a name to the first match on
- * its path, so the `.m` files next to this gateway (detectSIFTFeatures.m, extractFeatures.m,
- * matchFeatures.m, triangulate.m, estworldpose.m, CreateLandmarksFromFeatures.m) shadow the
+ * its path, so the `.m` files next to this gateway (undistortImage.m, detectSIFTFeatures.m,
+ * extractFeatures.m, matchFeatures.m, triangulate.m, estworldpose.m, CreateLandmarksFromFeatures.m) shadow the
  * toolbox and the reference's own CreateLandmarksFromFeatures.m without editing VO.m.  Each
  * calls this one gateway with a command string:
  *
+ *   J = vo_mex('undistort', I, cam, name, value, ...)
+ *        undistortImage(I, intrinsics)                                   VO.m:75-76
+ *        cam = [fx fy cx cy skew k1 k2 k3 p1 p2] (1 x 10 double) with cx, cy as MATLAB's
+ *        PrincipalPoint (1-based: libvo gets cx - 1, cy - 1); an interpolation string and the
+ *        options 'OutputView', 'FillValues' only at their defaults (vo:undistortImage:options)
+ *   vo_mex('distortion', cam_l, cam_r)
+ *        VO.m:75-76 inside the 'step' command: both cameras' cam rows ([] = none), kept for the
+ *        session and applied to every context 'step' creates (vo_set_distortion)
  *   [loc, scale, ori, metric, desc, octave, layer] = vo_mex('sift', I)
  *        detectSIFTFeatures + extractFeatures(..,"Method","SIFT")        VO.m:79-84
  *   [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...)
@@ -46,6 +54,16 @@
 static vo_ctx* g_ctx = NULL;
 static int g_rows = 0, g_cols = 0;
 
+/* vo_undistort / vo_set_distortion through weak references: a gateway linked with a libvo that
+ * lacks them still loads and serves every other command; 'undistort' and 'distortion' then raise
+ * vo:undistortImage:unavailable. */
+extern __typeof__(vo_undistort) vo_undistort __attribute__((weak));
+extern __typeof__(vo_set_distortion) vo_set_distortion __attribute__((weak));
+
+/* the 'distortion' command's cameras, applied to every context of the session */
+static vo_distortion g_dist[2];
+static int g_has_dist[2] = {0, 0};
+
 static void cleanup(void)
 {
     if (g_ctx) vo_destroy(g_ctx);
@@ -77,6 +95,10 @@ static void need_ctx(int rows, int cols)
         g_rows = rows;
         g_cols = cols;
         mexAtExit(cleanup);
+        if ((g_has_dist[0] || g_has_dist[1]) && vo_set_distortion) {
+            const int rc = vo_set_distortion(g_ctx, g_has_dist[0] ? &g_dist[0] : NULL, g_has_dist[1] ? &g_dist[1] : NULL);
+            if (rc != VO_OK) mexErrMsgIdAndTxt("vo:badArgument", "%s", vo_last_error(g_ctx));
+        }
     }
 }
 
@@ -265,6 +287,93 @@ static int match_options(int nrhs, const mxArray* prhs[], vo_match_opts* o)
     return given;
 }
 
+/* cam = [fx fy cx cy skew k1 k2 k3 p1 p2], 1 x 10 double, principal point 1-based (MATLAB's
+ * PrincipalPoint) -> vo_distortion (0-based pixel indices) */
+static void cam_row(const mxArray* a, vo_distortion* d, const char* what)
+{
+    need_real(a, mxDOUBLE_CLASS, 1, 10, what);
+    const double* v = mxGetDoubles(a);
+    memset(d, 0, sizeof(*d));
+    d->K[0] = v[0]; d->K[1] = v[4]; d->K[2] = v[2] - 1.0;
+    d->K[4] = v[1]; d->K[5] = v[3] - 1.0;
+    d->K[8] = 1.0;
+    d->radial[0] = v[5]; d->radial[1] = v[6]; d->radial[2] = v[7];
+    d->tangential[0] = v[8]; d->tangential[1] = v[9];
+}
+
+static void bad_undistort_option(const char* why, const char* name)
+{
+    mexErrMsgIdAndTxt("vo:undistortImage:options", "undistortImage: %s '%s' (libvo implements bilinear interpolation, "
+                      "OutputView 'same' and FillValues 0)", why, name);
+}
+
+/* undistortImage's trailing arguments prhs[3..]: an optional interpolation string ('linear' or
+ * 'bilinear', the default) and name-value pairs, accepted only where they restate the default */
+static void undistort_options(int nrhs, const mxArray* prhs[])
+{
+    char name[32], text[32];
+    int k = 3;
+    if (k < nrhs && mxIsChar(prhs[k]) && !mxGetString(prhs[k], name, sizeof name) &&
+        (same_nocase(name, "linear") || same_nocase(name, "bilinear") || same_nocase(name, "nearest") ||
+         same_nocase(name, "cubic") || same_nocase(name, "bicubic"))) {
+        if (!same_nocase(name, "linear") && !same_nocase(name, "bilinear")) bad_undistort_option("interpolation", name);
+        ++k;
+    }
+    if ((nrhs - k) % 2) bad_undistort_option("a name without a value after", "intrinsics");
+    for (; k < nrhs; k += 2) {
+        double v = 1.0;
+        const mxArray* val = prhs[k + 1];
+        if (!mxIsChar(prhs[k]) || mxGetString(prhs[k], name, sizeof name)) bad_undistort_option("option name is not a short string:", "?");
+        if (same_nocase(name, "OutputView")) {
+            if (!mxIsChar(val) || mxGetString(val, text, sizeof text) || !same_nocase(text, "same"))
+                bad_undistort_option("only the default is implemented for", name);
+        } else if (same_nocase(name, "FillValues")) {
+            if (!scalar_value(val, 1, &v) || v != 0.0) bad_undistort_option("only the default is implemented for", name);
+        } else {
+            bad_undistort_option("unknown option", name);
+        }
+    }
+}
+
+/* J = vo_mex('undistort', I, cam, ...): the column-major uint8 image as it lies */
+static void cmd_undistort(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    (void)nlhs;
+    if (nrhs < 3) need_args(nrhs, 3, "undistort");
+    const mxArray* I = prhs[1];
+    need_real(I, mxUINT8_CLASS, -1, -1, "I");
+    vo_distortion d;
+    cam_row(prhs[2], &d, "intrinsics");
+    undistort_options(nrhs, prhs);
+    if (!vo_undistort)
+        mexErrMsgIdAndTxt("vo:undistortImage:unavailable", "this libvo has no vo_undistort: undistort on the host, or link a newer libvo");
+    const int rows = (int)mxGetM(I), cols = (int)mxGetN(I);
+    need_ctx(rows, cols);
+    plhs[0] = mxCreateNumericMatrix(rows, cols, mxUINT8_CLASS, mxREAL);
+    check(vo_undistort(g_ctx, mxGetUint8s(I), rows, cols, rows, 1, &d, mxGetUint8s(plhs[0]), rows));
+}
+
+/* vo_mex('distortion', cam_l, cam_r): [] (0 x 0) = that camera passes through */
+static void cmd_distortion(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    (void)nlhs;
+    (void)plhs;
+    need_args(nrhs, 3, "distortion");
+    vo_distortion d[2];
+    int has[2];
+    for (int k = 0; k < 2; ++k) {
+        has[k] = mxGetM(prhs[1 + k]) * mxGetN(prhs[1 + k]) != 0;
+        if (has[k]) cam_row(prhs[1 + k], &d[k], k ? "intrinsics_r" : "intrinsics_l");
+    }
+    if (!vo_set_distortion)
+        mexErrMsgIdAndTxt("vo:undistortImage:unavailable", "this libvo has no vo_set_distortion: undistort on the host, or link a newer libvo");
+    if (g_ctx) check(vo_set_distortion(g_ctx, has[0] ? &d[0] : NULL, has[1] ? &d[1] : NULL));
+    for (int k = 0; k < 2; ++k) {
+        g_has_dist[k] = has[k];
+        if (has[k]) g_dist[k] = d[k];
+    }
+}
+
 /* [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...) */
 static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
 {
@@ -430,6 +539,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd))
         mexErrMsgIdAndTxt("vo:nargin", "vo_mex(command, ...): first argument must be a command string");
     if (!strcmp(cmd, "sift")) cmd_sift(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "undistort")) cmd_undistort(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "distortion")) cmd_distortion(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "match")) cmd_match(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "triangulate")) cmd_triangulate(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);

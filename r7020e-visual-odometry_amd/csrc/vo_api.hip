@@ -3,6 +3,7 @@
 #include "vo_internal.h"
 #include "vo_geom.h"
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdarg>
@@ -99,6 +100,14 @@ struct vo_ctx {
     uint8_t* d_img = nullptr;        // image staging [2*max_batch][rows*cols]
     uint8_t* d_cm = nullptr;         // column-major (MATLAB) image staging, allocated on first use
     size_t cm_cap = 0;
+    // vo_set_distortion: the loop-body entries undistort every frame ahead of the scale space
+    // (enqueue_sift_stereo) into d_rect: left frames [0, max_batch), right frames [max_batch,
+    // 2 max_batch), allocated by the first non-trivial call.  One buffer for both buffer sets and
+    // every batch in flight: only the octave-0 base kernels read it, on the stream that writes it.
+    bool ud_on[2] = {false, false};
+    vo_bc_cam ud_cam[2] = {};
+    uint8_t* d_rect = nullptr;
+    int rect_B = 0;                  // frames of the last batched call that went through d_rect
     // vo_match staging
     uint8_t* d_fd[2] = {nullptr, nullptr};
     DescMeta* d_fm[2] = {nullptr, nullptr};
@@ -239,6 +248,8 @@ static void destroy_buffers(vo_ctx* c)
     c->lm_retired.clear();
     geom_free(c->gb);
     hipFree(c->d_py); hipFree(c->d_jobs); hipFree(c->d_pair_i); hipFree(c->d_pair_j); hipFree(c->d_pair_n);
+    hipFree(c->d_rect);
+    c->d_rect = nullptr;
     hipFree(c->d_img); hipFree(c->d_cm); hipFree(c->d_fd[0]); hipFree(c->d_fd[1]); hipFree(c->d_fm[0]); hipFree(c->d_fm[1]);
     hipFree(c->d_ff[0]); hipFree(c->d_ff[1]); hipFree(c->d_bad);
     hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
@@ -554,6 +565,115 @@ int vo_sift(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, vo_keypoi
     return vo_sift_ex(c, img, rows, cols, ld, 0, kps, desc, capacity, n_out);
 }
 
+// ---- undistortImage (VO.m:75-76) -------------------------------------------------------------
+// vo_distortion -> the kernel's camera block; false for a non-finite entry, fx or fy zero, a
+// K[1][0] the model has no term for, or a last row other than 0 0 1.  *trivial: all five
+// coefficients zero (the remap is the identity on u8 frames, kitti.undistort_identity).
+static bool distortion_cam(const vo_distortion* d, vo_bc_cam* m, bool* trivial)
+{
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(d->K[k])) return false;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(d->radial[k])) return false;
+    for (int k = 0; k < 2; ++k) if (!std::isfinite(d->tangential[k])) return false;
+    if (d->K[0] == 0.0 || d->K[4] == 0.0 || d->K[3] != 0.0 || d->K[6] != 0.0 || d->K[7] != 0.0 || d->K[8] != 1.0) return false;
+    m->fx = d->K[0]; m->s = d->K[1]; m->cx = d->K[2]; m->fy = d->K[4]; m->cy = d->K[5];
+    m->k1 = d->radial[0]; m->k2 = d->radial[1]; m->k3 = d->radial[2];
+    m->p1 = d->tangential[0]; m->p2 = d->tangential[1];
+    *trivial = m->k1 == 0.0 && m->k2 == 0.0 && m->k3 == 0.0 && m->p1 == 0.0 && m->p2 == 0.0;
+    return true;
+}
+
+int vo_undistort(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int col_major, const vo_distortion* d,
+                 uint8_t* out, int ld_out)
+{
+    if (!c || !img || !out || !d || rows != c->rows || cols != c->cols || (col_major != 0 && col_major != 1) ||
+        ld < (col_major ? rows : cols) || ld_out < (col_major ? rows : cols))
+        return fail(c, VO_ERR_ARG, "vo_undistort: bad arguments");
+    UndistortSide S;
+    bool trivial = false;
+    if (!distortion_cam(d, &S.cam, &trivial))
+        return fail(c, VO_ERR_ARG, "vo_undistort: intrinsics must be finite with fx, fy != 0, K[1][0] = 0 and a last row 0 0 1");
+    BEGIN_CALL(c);
+    // staging frame 0 = the image (row-major), frame 1 = the result
+    const size_t fs = (size_t)rows * cols;
+    int rc = stage_images(c, img, ld, col_major, 1, c->d_img);
+    if (rc) return rc;
+    S.in = c->d_img; S.out = c->d_img + fs; S.copy = 0; S.pad = 0;
+    undistort_launch(&S, 1, rows, cols, 1, fs, fs, c->stream);
+    if (!col_major) {
+        HIPC(c, hipMemcpy2DAsync(out, ld_out, S.out, cols, cols, rows, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        // back to MATLAB's storage: the row-major result read as a column-major cols x rows
+        // matrix is transposed into the column-major staging (which held the input: >= rows * cols)
+        VO_LAUNCH(k_cm_to_rm_u8, dim3((cols + 31) / 32, (rows + 31) / 32, 1), dim3(256), 0, c->stream, S.out, cols, cols, rows,
+                  c->d_cm);
+        HIPC(c, hipMemcpy2DAsync(out, ld_out, c->d_cm, rows, rows, cols, hipMemcpyDeviceToHost, c->stream));
+    }
+    return finish(c);
+}
+
+int vo_undistort_batch_dev(vo_ctx* c, const uint8_t* d_in, int B, const vo_distortion* d, uint8_t* d_out)
+{
+    if (!c || !d_in || !d_out || !d || B < 1 || B > (1 << 19))
+        return fail(c, VO_ERR_ARG, "vo_undistort_batch_dev: bad arguments");
+    const size_t fs = (size_t)c->rows * c->cols;
+    const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
+    if (po < pi + fs * B && pi < po + fs * B)
+        return fail(c, VO_ERR_ARG, "vo_undistort_batch_dev: d_out overlaps d_in");
+    UndistortSide S;
+    bool trivial = false;
+    if (!distortion_cam(d, &S.cam, &trivial))
+        return fail(c, VO_ERR_ARG, "vo_undistort_batch_dev: intrinsics must be finite with fx, fy != 0, K[1][0] = 0 and a last row 0 0 1");
+    BEGIN_CALL(c, false);
+    S.in = d_in; S.out = d_out; S.copy = 0; S.pad = 0;
+    undistort_launch(&S, 1, c->rows, c->cols, B, fs, fs, c->stream);
+    g_prof = nullptr;                                   // profiling events are collected by vo_kernel_times
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
+    return VO_OK;
+}
+
+int vo_set_distortion(vo_ctx* c, const vo_distortion* left, const vo_distortion* right)
+{
+    if (!c) return VO_ERR_ARG;
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_set_distortion: step batches pending (vo_step_collect first)");
+    const vo_distortion* d[2] = {left, right};
+    vo_bc_cam cam[2];
+    bool on[2] = {false, false};
+    for (int k = 0; k < 2; ++k) {
+        if (!d[k]) continue;
+        bool trivial = false;
+        if (!distortion_cam(d[k], &cam[k], &trivial))
+            return fail(c, VO_ERR_ARG, "vo_set_distortion: %s intrinsics must be finite with fx, fy != 0, K[1][0] = 0 and a last row 0 0 1",
+                        k ? "right" : "left");
+        on[k] = !trivial;
+    }
+    if ((on[0] || on[1]) && !c->d_rect) {
+        hipSetDevice(c->device);
+        HIPC(c, hipMalloc((void**)&c->d_rect, (size_t)2 * c->max_batch * c->rows * c->cols));
+    }
+    for (int k = 0; k < 2; ++k) {
+        c->ud_on[k] = on[k];
+        if (on[k]) c->ud_cam[k] = cam[k];
+    }
+    c->rect_B = 0;
+    return VO_OK;
+}
+
+int vo_fetch_rectified(vo_ctx* c, int image, uint8_t* out, int capacity)
+{
+    if (!c || !out) return fail(c, VO_ERR_ARG, "vo_fetch_rectified: bad arguments");
+    if (!c->ud_on[0] && !c->ud_on[1]) return fail(c, VO_ERR_STATE, "vo_fetch_rectified: no distortion set (vo_set_distortion)");
+    if (image < 0 || image >= 2 * c->rect_B) return fail(c, VO_ERR_ARG, "vo_fetch_rectified: image %d not in the last batched call", image);
+    const size_t fs = (size_t)c->rows * c->cols;
+    if (capacity < 0 || (size_t)capacity < fs) return fail(c, VO_ERR_CAPACITY, "vo_fetch_rectified: capacity %d < %zu", capacity, fs);
+    hipSetDevice(c->device);
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
+    const uint8_t* src = c->d_rect + ((size_t)(image & 1) * c->max_batch + (image >> 1)) * fs;
+    HIPC(c, hipMemcpy(out, src, fs, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
 // matchFeatures on the two staged descriptor sets d_fd[0] (n1 rows) / d_fd[1] (n2 rows)
 static int match_staged(vo_ctx* c, int n1, int n2, uint32_t* pairs, int capacity, int* n_pairs, const char* who)
 {
@@ -846,13 +966,33 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
     HIPC(c, hipStreamWaitEvent(sp, c->ev_done[set], 0));      // set free (its previous features done)
 #endif
     const int o_small = sift_small_octave(c->py);
+    const bool undist = c->ud_on[0] || c->ud_on[1];           // vo_set_distortion
+    if (undist) c->rect_B = B;
     const bool ext_on_st = VO_EXT_SPLIT || VO_SMALL_STREAM != 0;   // the test of octaves 1.. on st
     // scale space on sp; octave 0's extremum test on st as soon as octave 0 is built (beside the
     // scale space of octaves 1..), the other octaves' on st after the scale space (VO_EXT_SPLIT)
     // -- the split that balances the two streams
     for (int p = 0; p < parts; ++p) {
         const int f0 = B * p / parts, nf = B * (p + 1) / parts - f0;
-        ImageSrc src{d_l + f0 * fs, d_r + f0 * fs, fs, c->cols, 0};
+        const uint8_t* pl = d_l + f0 * fs;
+        const uint8_t* pr = d_r + f0 * fs;
+        if (undist) {
+            // VO.m:75-76: the part's frames of both cameras, undistorted into d_rect by one launch.
+            // sp runs it behind the base kernels of every earlier part, call and batch -- the only
+            // readers of d_rect -- so the one buffer serves both sets and all batches in flight.
+            UndistortSide U[2];
+            for (int k = 0; k < 2; ++k) {
+                U[k].cam = c->ud_cam[k];
+                U[k].in = k ? pr : pl;
+                U[k].out = c->d_rect + ((size_t)k * c->max_batch + f0) * fs;
+                U[k].copy = c->ud_on[k] ? 0 : 1;
+                U[k].pad = 0;
+            }
+            undistort_launch(U, 2, c->rows, c->cols, nf, fs, fs, sp);
+            pl = U[0].out;
+            pr = U[1].out;
+        }
+        ImageSrc src{pl, pr, fs, c->cols, 0};
         SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
         sift_enqueue_pyramid(c->py, v, src, 2 * nf, c->sp, sp, c->d_py, c->ev_o0[p]);
         if (VO_SMALL_STREAM == 0) sift_enqueue_small(c->py, v, 2 * nf, sp, c->d_py);

@@ -197,6 +197,21 @@ void sift_enqueue_small(const Pyramid& py, SiftBuffers& b, int n_img, hipStream_
 void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
                            const Pyramid* d_py);
 
+// ---------------------------------------------------------------------------
+// undistortImage (undistort.hip): k_undistort remaps B frames of one or two cameras in one
+// launch.  Side k reads frame f at in + f * in_stride and writes it at out + f * out_stride, both
+// row-major with leading dimension cols; copy = 1 passes the side through unchanged.
+// ---------------------------------------------------------------------------
+#define VO_UD_CHUNK 16            // frames per thread: the f64 map of its pixels is evaluated once per chunk
+struct UndistortSide {
+    vo_bc_cam cam;
+    const uint8_t* in;
+    uint8_t* out;
+    int copy, pad;
+};
+void undistort_launch(const UndistortSide* sides, int n_sides, int rows, int cols, int B, size_t in_stride,
+                      size_t out_stride, hipStream_t s);
+
 // One octave's levels 1..5 + extremum test + next octave base in one pass (octave.hip).
 struct OctArgs {
     float* arena;

@@ -4,9 +4,11 @@
 Mirrors what `VO.m` does around its per-frame loop:
   * sequence layout and loading   -- `VO.m:13-17` (times.txt, image_0/image_1 PNG datastores),
     `VO.m:23-38` (calib.txt: P0/P1 rows read with `readmatrix`, columns 2:13, row-major 3x4);
-  * undistortImage (`VO.m:75-76`): restated (`undistort`), and with the zero-distortion
-    `cameraIntrinsics` of `VO.m:50-51` it is the identity on u8 images (`undistort_identity`
-    checks the sampling map), so frames go to libvo unchanged;
+  * undistortImage (`VO.m:75-76`): restated (`undistort`, the spec of libvo's k_undistort), and
+    with the zero-distortion `cameraIntrinsics` of `VO.m:50-51` it is the identity on u8 images
+    (`undistort_identity` checks the sampling map), so frames go to libvo unchanged; a sequence
+    given per-camera distortion coefficients has libvo undistort every frame on the device
+    (`vo_set_distortion`);
   * trajectory                    -- `VO.m:130-134` (`pose = pose * rel_pose`, `all_poses`),
     written in the KITTI 3x4 row-major pose format;
   * accuracy                      -- `PlotOnMap.m:1-26`: the reference's lagged xz error
@@ -194,10 +196,16 @@ def _read_png(path: Path) -> np.ndarray:
 class KittiSequence:
     """A KITTI odometry sequence in the reference's layout:
     <root>/<seq>/{image_0,image_1}/%06d.png, <root>/<seq>/{calib.txt,times.txt},
-    optional ground truth <root>/poses/<seq>.txt."""
+    optional ground truth <root>/poses/<seq>.txt.  `dist_left` / `dist_right`: a camera's
+    distortion coefficients in `undistort`'s order (k1, k2, p1, p2[, k3]) for a sequence that is
+    not rectified; the driver then sets them on its context (`set_distortion`) and libvo
+    undistorts every frame on the device.  With neither given the calibration must make
+    undistortImage the identity, as KITTI's does."""
     root: Path
     seq: str = "00"
     threads: int = 8
+    dist_left: tuple | None = None
+    dist_right: tuple | None = None
 
     def __post_init__(self):
         self.root = Path(self.root)
@@ -210,8 +218,12 @@ class KittiSequence:
         self.P1, self.P2 = cal["P0"], cal["P1"]          # VO.m's p1 / p2 (left, right)
         first = _read_png(self.left[0])
         self.rows, self.cols = first.shape
+        for coef in (self.dist_left, self.dist_right):
+            if coef is not None and not 4 <= len(coef) <= 5:
+                raise ValueError("distortion coefficients are (k1, k2, p1, p2[, k3])")
         # VO.m:50-51 (zero distortion) makes VO.m:75-76 undistortImage the identity
-        if not undistort_identity(self.P1[:, :3], rows=self.rows, cols=self.cols):
+        if self.dist_left is None and self.dist_right is None and \
+                not undistort_identity(self.P1[:, :3], rows=self.rows, cols=self.cols):
             raise ValueError("undistortImage with these intrinsics is not the identity")
         self.times = read_times(d / "times.txt") if (d / "times.txt").exists() else None
         gt = self.root / "poses" / f"{self.seq}.txt"
@@ -246,6 +258,18 @@ class KittiSequence:
 
     def close(self):
         self._pool.shutdown(wait=True)
+
+
+def set_sequence_distortion(ctx, seq) -> None:
+    """VO.m:75-76 for a sequence with distortion coefficients: both cameras' intrinsics
+    (K = P(:, 1:3), VO.m:35-38) and coefficients to the context (vo_set_distortion).  A sequence
+    without any (KITTI; device-frame tuples) leaves the context as it is."""
+    from . import vo
+    dl, dr = getattr(seq, "dist_left", None), getattr(seq, "dist_right", None)
+    if dl is None and dr is None:
+        return
+    ctx.set_distortion(None if dl is None else vo.distortion_from_kitti(seq.P1[:, :3], dl),
+                       None if dr is None else vo.distortion_from_kitti(seq.P2[:, :3], dr))
 
 
 def _pipelined(ctx, batches, dev, on_collect=None, depth: int | None = None) -> list:
@@ -304,6 +328,7 @@ def run(seq: KittiSequence, batch: int = 16, stop: int | None = None, device: in
     own = ctx is None
     if own:
         ctx = vo.Context(seq.rows, seq.cols, batch, device=device, calib=vo.calib_from(seq.P1, seq.P2))
+    set_sequence_distortion(ctx, seq)
     hook = None
     if viz_dir is not None:
         from . import viz
@@ -362,6 +387,7 @@ def run_shard(seq, rank: int, world: int, batch: int = 16, device: int | None = 
         rows, cols = (seq[0].shape[1], seq[0].shape[2]) if on_device else (seq.rows, seq.cols)
         ctx = vo.Context(rows, cols, batch, device=device, calib=vo.calib_from(seq_calib(seq)[0], seq_calib(seq)[1]))
     ctx.reset()
+    set_sequence_distortion(ctx, seq)
     ctx.set_landmark_frame(True)
     ctx.set_frame_index(h)
     src = device_batches(seq[0], seq[1], batch, h, e) if on_device else seq.batches(batch, h, e)

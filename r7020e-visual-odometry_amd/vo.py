@@ -5,6 +5,7 @@ The reference (VO.m) calls MathWorks toolbox functions; this module exposes
 the same names with the same argument meaning and error behaviour, each
 running on the MI355X through libvo.so:
 
+    undistortImage                         VO.m:75-76
     detectSIFTFeatures / extractFeatures   VO.m:79-84
     matchFeatures                          VO.m:87,283,293,311,323
     find_remaining_points                  VO.m:280-334
@@ -36,6 +37,7 @@ VO_ERR_NO_CONSENSUS = -4
 VO_ERR_CAPACITY = -5
 VO_ERR_STATE = -6
 STEP_DEPTH = 3            # VO_STEP_DEPTH: batches vo_step_submit_dev keeps in flight
+UNDISTORT_CHUNK = 16      # VO_UD_CHUNK (csrc/vo_internal.h): frames per k_undistort thread
 
 
 class VOError(RuntimeError):
@@ -64,6 +66,12 @@ class RansacParams(C.Structure):
 
 class Calib(C.Structure):
     _fields_ = [("P1", C.c_double * 12), ("P2", C.c_double * 12), ("K", C.c_double * 9)]
+
+
+class Distortion(C.Structure):
+    """vo_distortion: one camera's intrinsics (row-major K, 0-based principal point) and its
+    Brown-Conrady coefficients (cameraIntrinsics RadialDistortion / TangentialDistortion)."""
+    _fields_ = [("K", C.c_double * 9), ("radial", C.c_double * 3), ("tangential", C.c_double * 2)]
 
 
 class Keypoint(C.Structure):
@@ -99,6 +107,7 @@ EXPORTS = [
     "vo_set_landmark_frame", "vo_get_landmark_rows", "vo_landmarks_to_world", "vo_match_f32",
     "vo_sift_ex", "vo_step_batch_ex", "vo_chain_poses", "vo_landmarks_to_world_frames", "vo_landmarks_world_dev",
     "vo_fetch_candidate_counts", "vo_default_match_opts", "vo_match_ex", "vo_match_f32_ex",
+    "vo_undistort", "vo_undistort_batch_dev", "vo_set_distortion", "vo_fetch_rectified",
 ]
 
 # the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the experimental kernels kept
@@ -151,6 +160,10 @@ def load_library(path: str | os.PathLike | None = None):
                               C.c_int, P(C.c_int)]
     L.vo_match_f32_ex.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int, C.c_int, C.c_int, P(MatchOpts),
                                   P(C.c_uint32), P(C.c_float), C.c_int, P(C.c_int)]
+    L.vo_undistort.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(Distortion), P(C.c_uint8), C.c_int]
+    L.vo_undistort_batch_dev.argtypes = [vp, vp, C.c_int, P(Distortion), vp]
+    L.vo_set_distortion.argtypes = [vp, P(Distortion), P(Distortion)]
+    L.vo_fetch_rectified.argtypes = [vp, C.c_int, P(C.c_uint8), C.c_int]
     L.vo_track.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int,
                            P(C.c_uint32), C.c_int, P(C.c_int)]
     L.vo_triangulate.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double)]
@@ -240,6 +253,32 @@ def calib_from(P1, P2, K=None) -> Calib:
     return c
 
 
+def distortion_from(K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0)) -> Distortion:
+    """vo_distortion from a 3x3 K (0-based principal point, K[0][1] the skew) and cameraIntrinsics'
+    RadialDistortion (2 or 3 entries: k1 k2 [k3]) / TangentialDistortion (p1 p2).  In
+    kitti.undistort's order (k1, k2, p1, p2[, k3]) that is radial = (k1, k2, k3),
+    tangential = (p1, p2): see distortion_from_kitti."""
+    radial = [float(v) for v in np.asarray(radial, np.float64).reshape(-1)]
+    tangential = [float(v) for v in np.asarray(tangential, np.float64).reshape(-1)]
+    if len(radial) not in (2, 3) or len(tangential) != 2:
+        raise VOError(VO_ERR_ARG, "distortion_from: radial has 2 or 3 entries, tangential 2")
+    K = np.asarray(K, np.float64)
+    if K.shape != (3, 3):
+        raise VOError(VO_ERR_ARG, "distortion_from: K is 3x3")
+    d = Distortion()
+    d.K[:] = [float(v) for v in K.reshape(-1)]
+    d.radial[:] = radial + [0.0] * (3 - len(radial))
+    d.tangential[:] = tangential
+    return d
+
+
+def distortion_from_kitti(K, dist) -> Distortion:
+    """vo_distortion from kitti.undistort's coefficient tuple (k1, k2, p1, p2[, k3]; shorter
+    tuples are padded with zeros, as kitti.undistort_map pads them)."""
+    k = [float(v) for v in dist] + [0.0] * (5 - len(dist))
+    return distortion_from(K, (k[0], k[1], k[4]), (k[2], k[3]))
+
+
 class Context:
     """One libvo context (one HIP device, fixed image size, up to max_batch frames per call)."""
 
@@ -296,6 +335,47 @@ class Context:
         self._check(self.lib.vo_sift_ex(self.h, _p(img, C.c_uint8), img.shape[0], img.shape[1], ld, col_major,
                                         kps.ctypes.data_as(C.POINTER(Keypoint)), _p(desc, C.c_uint8), cap, C.byref(n)))
         return kps[: n.value].copy(), desc[: n.value].copy()
+
+    # ---- undistortImage ----
+    def undistort(self, img: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0), col_major: bool = False) -> np.ndarray:
+        """J = undistortImage(I, intrinsics) (vo_undistort): a 2-D uint8 image of the context's
+        size; col_major hands it over, and takes the result back, in MATLAB's storage.  A row-major
+        view with a row stride >= cols (e.g. a slice of a wider array) goes through as it lies."""
+        img = np.asarray(img, np.uint8)
+        if img.ndim != 2:
+            raise VOError(VO_ERR_ARG, "undistort: a 2-D uint8 image")
+        rows, cols = img.shape
+        d = distortion_from(K, radial, tangential)
+        if col_major:
+            src = np.asfortranarray(img)
+            out = np.empty((rows, cols), np.uint8, order="F")
+            ld = ld_out = rows
+        else:
+            src = img if img.strides[1] == 1 and img.strides[0] >= cols else np.ascontiguousarray(img)
+            out = np.empty((rows, cols), np.uint8)
+            ld, ld_out = src.strides[0], cols
+        self._check(self.lib.vo_undistort(self.h, _p(src, C.c_uint8), rows, cols, ld, 1 if col_major else 0, C.byref(d),
+                                          _p(out, C.c_uint8), ld_out))
+        return out
+
+    def undistort_batch_dev(self, d_in: int, d_out: int, B: int, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0)) -> None:
+        """vo_undistort_batch_dev: B tightly packed device frames at d_in -> d_out (device
+        pointers), stream-ordered on the context's stream (synchronise before reading d_out)."""
+        d = distortion_from(K, radial, tangential)
+        self._check(self.lib.vo_undistort_batch_dev(self.h, C.c_void_p(d_in or None), B, C.byref(d), C.c_void_p(d_out or None)))
+
+    def set_distortion(self, left: Distortion | None = None, right: Distortion | None = None) -> None:
+        """VO.m:75-76 inside the loop body (vo_set_distortion): step*, sift_match_batch_dev then
+        undistort every frame on the device first.  None, or all-zero coefficients, passes a
+        camera through; (None, None) restores the context's behaviour without distortion."""
+        self._check(self.lib.vo_set_distortion(self.h, C.byref(left) if left is not None else None,
+                                               C.byref(right) if right is not None else None))
+
+    def fetch_rectified(self, image: int) -> np.ndarray:
+        """The undistorted image 2*frame + side of the last batched call (vo_fetch_rectified)."""
+        out = np.empty((self.rows, self.cols), np.uint8)
+        self._check(self.lib.vo_fetch_rectified(self.h, image, _p(out, C.c_uint8), out.size))
+        return out
 
     # ---- matchFeatures ----
     def _match_opts(self, unique, match_threshold, max_ratio) -> MatchOpts:
@@ -639,6 +719,14 @@ def detectSIFTFeatures(I: np.ndarray):
     (points, descriptors) where points is a structured array with MATLAB
     1-based Location (x, y), Scale, Orientation (angle), Metric (response)."""
     return _default_ctx(*I.shape).sift(I)
+
+
+def undistortImage(I: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0)) -> np.ndarray:
+    """undistortImage(I, intrinsics) (VO.m:75-76): K is the 3x3 intrinsic matrix with the principal
+    point in 0-based pixel indices, radial / tangential the intrinsics' RadialDistortion (2 or 3
+    entries) and TangentialDistortion.  OutputView 'same', bilinear, FillValues 0."""
+    I = np.asarray(I)
+    return _default_ctx(*I.shape).undistort(I, K, radial, tangential)
 
 
 def extractFeatures(I: np.ndarray, points=None, Method: str = "SIFT"):
