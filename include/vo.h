@@ -15,6 +15,8 @@
  *   vo_set_distortion      the scale space of the loop-body entries
  *   vo_sift                detectSIFTFeatures + extractFeatures(...,"SIFT")
  *                          VO.m:79-84
+ *   vo_set_strongest       points = selectStrongest(points, N) between the two
+ *                          (VO.m:140,206,217-218), in every entry that detects
  *   vo_match               matchFeatures(F1, F2)  VO.m:87,283,293,311,323
  *   vo_match_ex /          [indexPairs, matchMetric] = matchFeatures(F1, F2,
  *   vo_match_f32_ex        'Unique', u, 'MatchThreshold', t, 'MaxRatio', r)
@@ -195,6 +197,27 @@ int vo_set_distortion(vo_ctx* ctx, const vo_distortion* left, const vo_distortio
  * call, rows*cols bytes row-major (capacity in bytes).  Synchronises like the other vo_fetch_*
  * calls.  VO_ERR_STATE when no distortion is set. */
 int vo_fetch_rectified(vo_ctx* ctx, int image, uint8_t* out, int capacity);
+
+/* points = selectStrongest(points, n) between detectSIFTFeatures and extractFeatures (the knob
+ * VO.m:140, 206 name: "limit the number of points kept"; VO.m:217-218).  Per image: the detections
+ * in detection order, stably sorted by response (Metric) descending -- the key is (response
+ * descending, detection index ascending) -- and the first min(n, count) kept.  The result is in
+ * sorted order also when n >= count.  The orientation peaks of one candidate share a response and
+ * are consecutive, so a cut inside such a group keeps its first peaks.
+ * n = 0 (the default) is off: nothing is launched and every result is that of a context that never
+ * set it.  1 <= n <= max_keypoints turns it on for every entry that detects: vo_sift / vo_sift_ex
+ * (it is a SIFTPoints operation, so unlike the distortion it applies there), vo_sift_match_batch_dev
+ * and the vo_step* entries.  Only the n selected keypoints are described and matched; n_left /
+ * n_right of vo_step_out and vo_pair_stats, vo_sift's *n_out and vo_fetch_keypoints' n are the
+ * selected counts, while VO_FLAG_KEYPOINTS / VO_FLAG_CANDIDATES (and vo_sift's VO_ERR_CAPACITY)
+ * still follow the detected counts.  Takes effect with the next call and keeps the loop state.  The
+ * first n > 0 allocates the comparison keys (12 bytes per candidate slot).
+ * VO_ERR_ARG for any other n, VO_ERR_STATE while step batches are pending; the setting is then
+ * unchanged. */
+int vo_set_strongest(vo_ctx* ctx, int n);
+/* The keypoint count ahead of the selection of image 2*frame + side of the last call (with the
+ * selection off: the count vo_fetch_keypoints reports).  Synchronises like the other vo_fetch_*. */
+int vo_fetch_detected_count(vo_ctx* ctx, int image, int* n_detected);
 
 /* matchFeatures(F1, F2) on SIFT descriptors (uint8 rows of 128).
  * pairs[capacity][2] 1-based; *n_pairs = matches found. */

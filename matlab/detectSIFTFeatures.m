@@ -13,7 +13,7 @@ function points = detectSIFTFeatures(I, varargin)
         I = im2uint8(I);
     end
     [loc, scale, ori, metric, desc, octave, layer] = vo_mex('sift', I);
-    vo_sift_cache('put', I, loc, desc);
+    vo_sift_cache('put', I, [loc, scale, ori], desc);
     points = SIFTPoints(loc, 'Scale', scale, 'Orientation', ori, 'Metric', metric, ...
                         'Octave', octave, 'Layer', layer);
 end

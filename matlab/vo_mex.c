@@ -15,6 +15,10 @@
  *   vo_mex('distortion', cam_l, cam_r)
  *        VO.m:75-76 inside the 'step' command: both cameras' cam rows ([] = none), kept for the
  *        session and applied to every context 'step' creates (vo_set_distortion)
+ *   vo_mex('strongest', N)
+ *        points = selectStrongest(points, N) between detectSIFTFeatures and extractFeatures
+ *        (VO.m:140,206,217-218), in 'sift' and 'step': N kept for the session and applied to
+ *        every context they create (vo_set_strongest); 0 = off
  *   [loc, scale, ori, metric, desc, octave, layer] = vo_mex('sift', I)
  *        detectSIFTFeatures + extractFeatures(..,"Method","SIFT")        VO.m:79-84
  *   [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...)
@@ -60,6 +64,12 @@ static int g_rows = 0, g_cols = 0;
 extern __typeof__(vo_undistort) vo_undistort __attribute__((weak));
 extern __typeof__(vo_set_distortion) vo_set_distortion __attribute__((weak));
 
+/* vo_set_strongest likewise: without it 'strongest' raises vo:selectStrongest:unavailable */
+extern __typeof__(vo_set_strongest) vo_set_strongest __attribute__((weak));
+
+/* the 'strongest' command's N, applied to every context of the session (0 = off) */
+static int g_strongest = 0;
+
 /* the 'distortion' command's cameras, applied to every context of the session */
 static vo_distortion g_dist[2];
 static int g_has_dist[2] = {0, 0};
@@ -99,6 +109,8 @@ static void need_ctx(int rows, int cols)
             const int rc = vo_set_distortion(g_ctx, g_has_dist[0] ? &g_dist[0] : NULL, g_has_dist[1] ? &g_dist[1] : NULL);
             if (rc != VO_OK) mexErrMsgIdAndTxt("vo:badArgument", "%s", vo_last_error(g_ctx));
         }
+        if (g_strongest > 0 && vo_set_strongest && vo_set_strongest(g_ctx, g_strongest) != VO_OK)
+            mexErrMsgIdAndTxt("vo:badArgument", "%s", vo_last_error(g_ctx));
     }
 }
 
@@ -374,6 +386,22 @@ static void cmd_distortion(int nlhs, mxArray* plhs[], int nrhs, const mxArray* p
     }
 }
 
+/* vo_mex('strongest', N): N = 0 turns the selection off */
+static void cmd_strongest(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    (void)nlhs;
+    (void)plhs;
+    need_args(nrhs, 2, "strongest");
+    need_real(prhs[1], mxDOUBLE_CLASS, 1, 1, "N");
+    const double v = mxGetDoubles(prhs[1])[0];
+    if (!(v >= 0.0 && v <= (double)VO_MEX_CAPACITY) || v != (double)(int)v)
+        mexErrMsgIdAndTxt("vo:badArgument", "N must be an integer in 0 .. %d", VO_MEX_CAPACITY);
+    if (!vo_set_strongest)
+        mexErrMsgIdAndTxt("vo:selectStrongest:unavailable", "this libvo has no vo_set_strongest: select on the host, or link a newer libvo");
+    if (g_ctx) check(vo_set_strongest(g_ctx, (int)v));
+    g_strongest = (int)v;
+}
+
 /* [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...) */
 static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
 {
@@ -541,6 +569,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     if (!strcmp(cmd, "sift")) cmd_sift(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "undistort")) cmd_undistort(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "distortion")) cmd_distortion(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "strongest")) cmd_strongest(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "match")) cmd_match(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "triangulate")) cmd_triangulate(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);

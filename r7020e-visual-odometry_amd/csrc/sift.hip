@@ -13,6 +13,8 @@
 //                         uniform), orientation histogram (lanes stride the
 //                         window, 2^-20 fixed-point LDS atomics), peaks by ballot
 //   k_scan_cands/k_expand keypoint list in candidate order, then peak order
+//   k_sel_keys/k_sel_rank only with vo_set_strongest(n > 0), between the two: the candidates'
+//                         slots in selectStrongest's order (response descending, stable)
 //   k_desc                one wave per keypoint: 4x4x8 trilinear histogram
 //                         (fixed-point LDS atomics), norms as a wave tree
 // Every float expression follows oracle/sift_ref.c operation for operation.
@@ -98,6 +100,9 @@ SiftBuffers sift_view(const SiftBuffers& b, const Pyramid& py, int img0, int n)
     v.cout = b.cout + (size_t)img0 * b.cand_cap;
     v.koff = b.koff + (size_t)img0 * b.cand_cap;
     v.n_kp = b.n_kp + img0;
+    v.n_det = b.n_det + img0;
+    if (b.skey) v.skey = b.skey + (size_t)img0 * b.cand_cap;
+    if (b.snpk) v.snpk = b.snpk + (size_t)img0 * b.cand_cap;
     v.kp = b.kp + (size_t)img0 * b.kp_cap;
     v.kpi = b.kpi + (size_t)img0 * b.kp_cap;
     v.desc = b.desc + (size_t)img0 * b.kp_cap * VO_DESC_LEN;
@@ -123,6 +128,7 @@ hipError_t sift_alloc(SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_ca
     VO_ALLOC(b.cout, sizeof(CandOut) * (size_t)cand_cap * n);
     VO_ALLOC(b.koff, sizeof(uint32_t) * (size_t)cand_cap * n);
     VO_ALLOC(b.n_kp, sizeof(int) * n);
+    VO_ALLOC(b.n_det, sizeof(int) * n);
     VO_ALLOC(b.kp, sizeof(vo_keypoint) * (size_t)kp_cap * n);
     VO_ALLOC(b.kpi, sizeof(KpInt) * (size_t)kp_cap * n);
     VO_ALLOC(b.desc, (size_t)VO_DESC_LEN * kp_cap * n);
@@ -131,8 +137,23 @@ hipError_t sift_alloc(SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_ca
     return hipSuccess;
 }
 
+// selectStrongest's comparison keys (k_sel_keys / k_sel_rank), allocated by the first
+// vo_set_strongest(n > 0): all or nothing
+hipError_t sift_alloc_select(SiftBuffers& b)
+{
+    if (b.skey && b.snpk) return hipSuccess;
+    unsigned long long* key = nullptr;
+    uint32_t* npk = nullptr;
+    hipError_t e = hipMalloc((void**)&key, sizeof(unsigned long long) * (size_t)b.cand_cap * b.n_img);
+    if (e == hipSuccess) e = hipMalloc((void**)&npk, sizeof(uint32_t) * (size_t)b.cand_cap * b.n_img);
+    if (e != hipSuccess) { hipFree(key); hipFree(npk); return e; }
+    b.skey = key; b.snpk = npk;
+    return hipSuccess;
+}
+
 void sift_free(SiftBuffers& b)
 {
+    hipFree(b.n_det); hipFree(b.skey); hipFree(b.snpk);
     hipFree(b.arena); hipFree(b.tmp); hipFree(b.mask); hipFree(b.woff); hipFree(b.cand); hipFree(b.n_cand); hipFree(b.acc); hipFree(b.n_acc);
     hipFree(b.cout); hipFree(b.koff); hipFree(b.n_kp); hipFree(b.kp); hipFree(b.kpi); hipFree(b.desc); hipFree(b.meta);
     b = SiftBuffers();
@@ -1937,11 +1958,85 @@ __global__ __launch_bounds__(1024) void k_scan_cands(const CandOut* __restrict__
     if (tid == 0) n_kp[img] = (int)total;
 }
 
+// ---------------------------------------------------------------------------
+// SIFTPoints.selectStrongest(points, N) (vo_set_strongest), between k_scan_cands and k_expand.
+// The order is (response descending, detection index ascending): response = |DoG| is finite and
+// non-negative, so its bits order as a u32, and the 64-bit key  response bits << 32 | ~koff  is
+// larger for the keypoint that comes first.  A candidate's peaks share its response and are
+// consecutive detections, so ranking is done per accepted candidate: its new first slot is the sum
+// of the peak counts of the candidates with a larger key, and k_expand cuts its peaks at N.  The
+// sum is over a set, so the order in which k_refine listed the candidates does not matter.
+//   k_sel_keys  key and peak count of every listed candidate, in list order (12 B each instead of
+//               a CandOut line); n_det = the detected count
+//   k_sel_rank  256 candidates per workgroup against every candidate of the image, the keys staged
+//               through LDS in tiles of 256 (every lane reads the same LDS word: a broadcast);
+//               the new offsets replace koff in place (k_sel_keys holds the old ones), n_kp =
+//               min(n_det, N)
+// grid (VO_SEL_BLOCKS, n_img), 256 threads
+// ---------------------------------------------------------------------------
+#define VO_SEL_BLOCKS 16
+#define VO_SEL_TILE 256
+__global__ __launch_bounds__(VO_SEL_TILE) void k_sel_keys(const CandOut* __restrict__ cout, const int* __restrict__ n_walk,
+                                                          const int* __restrict__ acc, const uint32_t* __restrict__ koff,
+                                                          const int* __restrict__ n_kp, int* __restrict__ n_det,
+                                                          unsigned long long* __restrict__ skey, uint32_t* __restrict__ snpk,
+                                                          int cand_cap)
+{
+    const int img = blockIdx.y;
+    const size_t base = (size_t)img * cand_cap;
+    const int n = min(n_walk[img], cand_cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) n_det[img] = n_kp[img];
+    for (int a = blockIdx.x * VO_SEL_TILE + threadIdx.x; a < n; a += gridDim.x * VO_SEL_TILE) {
+        const int k = VO_ACC_LIST ? acc[base + a] : a;
+        const CandOut& co = cout[base + k];
+        const int npk = co.npk;
+        skey[base + a] = (unsigned long long)__float_as_uint(co.response) << 32 | (unsigned long long)(~koff[base + k]);
+        snpk[base + a] = npk > 0 ? (uint32_t)npk : 0u;
+    }
+}
+
+__global__ __launch_bounds__(VO_SEL_TILE) void k_sel_rank(const int* __restrict__ n_walk, const int* __restrict__ acc,
+                                                          const unsigned long long* __restrict__ skey,
+                                                          const uint32_t* __restrict__ snpk, uint32_t* __restrict__ koff,
+                                                          const int* __restrict__ n_det, int* __restrict__ n_kp, int cand_cap,
+                                                          int limit)
+{
+    __shared__ unsigned long long sk[VO_SEL_TILE];
+    __shared__ uint32_t sn[VO_SEL_TILE];
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const size_t base = (size_t)img * cand_cap;
+    const int n = min(n_walk[img], cand_cap);
+    if (blockIdx.x == 0 && tid == 0) n_kp[img] = min(n_det[img], limit);
+    for (int r0 = blockIdx.x * VO_SEL_TILE; r0 < n; r0 += gridDim.x * VO_SEL_TILE) {    // block-uniform
+        const int a = r0 + tid;
+        const unsigned long long mine = a < n ? skey[base + a] : 0ull;
+        uint32_t off = 0;
+        for (int c0 = 0; c0 < n; c0 += VO_SEL_TILE) {
+            const int j = c0 + tid;
+            __syncthreads();                               // the previous tile's readers are done
+            sk[tid] = j < n ? skey[base + j] : 0ull;       // padding: the smallest key, no peaks
+            sn[tid] = j < n ? snpk[base + j] : 0u;
+            __syncthreads();
+            // both words are read whatever the comparison gives (a mask, not a branch): as
+            // `sk[q] > mine ? sn[q] : 0` the count was read under the comparison's exec mask, one
+            // dependent LDS round trip per candidate; this form reads 16 candidates' words in wide
+            // LDS loads and waits once
+#pragma unroll 16
+            for (int q = 0; q < VO_SEL_TILE; ++q) {
+                const unsigned long long kq = sk[q];
+                const uint32_t nq = sn[q];
+                off += nq & (0u - (uint32_t)(kq > mine));
+            }
+        }
+        if (a < n) koff[base + (VO_ACC_LIST ? acc[base + a] : a)] = off;
+    }
+}
+
 // one thread per accepted candidate (k_refine's list; each writes its own keypoint slots, so the
 // list order does not matter)
 __global__ void k_expand(const CandOut* __restrict__ cout, const int* __restrict__ n_acc, const int* __restrict__ acc,
                          const uint32_t* __restrict__ koff, vo_keypoint* __restrict__ kp, KpInt* __restrict__ kpi,
-                         int cand_cap, int kp_cap, int n_img, int upsample)
+                         int cand_cap, int kp_cap, int n_img, int upsample, int limit)
 {
     __shared__ int fpre[VO_FLAT_MAX_IMG + 1];
     const long total = flat_setup(n_acc, cand_cap, n_img, fpre);
@@ -1958,7 +2053,7 @@ __global__ void k_expand(const CandOut* __restrict__ cout, const int* __restrict
         const float loc_off = upsample ? 0.75f : 1.0f;
         for (int p = 0; p < npk; ++p) {
             const uint32_t idx = base + p;
-            if (idx >= (uint32_t)kp_cap) break;
+            if (idx >= (uint32_t)limit) break;         // kp_cap, or selectStrongest's N (a cut inside the peaks)
             vo_keypoint q;
             q.x = co.xo * oscale + loc_off;
             q.y = co.yo * oscale + loc_off;
@@ -2638,7 +2733,7 @@ static int desc_radius_cap(const Pyramid& py, const vo_sift_params& p)
 }
 
 void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
-                           const Pyramid* d_py)
+                           const Pyramid* d_py, int strongest)
 {
     float* A = b.arena;
     const dim3 gs(py.n_seg > 0 ? py.n_seg : 1, n_img);
@@ -2653,8 +2748,15 @@ void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const v
     VO_LAUNCH_NAMED("k_orient", (k_orient<36>), dim3(kFeatureGrid), dim3(64), fpre_bytes, s, d_py, A, n_walk, b.acc,
                     b.cout, b.koff, b.cand_cap, n_img);
     VO_LAUNCH(k_scan_cands, dim3(n_img), dim3(1024), 0, s, b.cout, b.n_cand, b.koff, b.n_kp, b.cand_cap);
+    if (strongest > 0) {                                     // selectStrongest: koff becomes the slot in sorted order
+        const dim3 gsel(VO_SEL_BLOCKS, n_img);
+        VO_LAUNCH(k_sel_keys, gsel, dim3(VO_SEL_TILE), 0, s, b.cout, n_walk, b.acc, b.koff, b.n_kp, b.n_det, b.skey, b.snpk,
+                  b.cand_cap);
+        VO_LAUNCH(k_sel_rank, gsel, dim3(VO_SEL_TILE), 0, s, n_walk, b.acc, b.skey, b.snpk, b.koff, b.n_det, b.n_kp, b.cand_cap,
+                  strongest);
+    }
     VO_LAUNCH(k_expand, dim3(256), dim3(256), 0, s, b.cout, n_walk, b.acc, b.koff, b.kp, b.kpi, b.cand_cap, b.kp_cap,
-              n_img, p.upsample);
+              n_img, p.upsample, strongest > 0 ? strongest : b.kp_cap);
     // 4 histogram copies: 2 -> +4 %, 8 -> +33 % k_desc time (MI355X)
     // (capping k_desc's residency per CU with 8 / 16 / 28 KB of extra LDS per workgroup, to leave
     // the level blurs beside it more waves: 8886 / 8016 / 6877 against 10186 stereo frames/s --
@@ -2664,11 +2766,11 @@ void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const v
 }
 
 void sift_enqueue(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img, const vo_sift_params& p,
-                  hipStream_t s, const Pyramid* d_py)
+                  hipStream_t s, const Pyramid* d_py, int strongest)
 {
     sift_enqueue_pyramid(py, b, src, n_img, p, s, d_py);
     sift_enqueue_pyramid_tail(py, b, n_img, p, s, d_py, 0);
-    sift_enqueue_features(py, b, n_img, p, s, d_py);
+    sift_enqueue_features(py, b, n_img, p, s, d_py, strongest);
 }
 
 }  // namespace vo

@@ -108,6 +108,11 @@ struct vo_ctx {
     vo_bc_cam ud_cam[2] = {};
     uint8_t* d_rect = nullptr;
     int rect_B = 0;                  // frames of the last batched call that went through d_rect
+    // vo_set_strongest: SIFTPoints.selectStrongest(points, strongest) between detection and
+    // description in every entry that detects (0 = off); sel_used[set]: the set's last SIFT call
+    // ran with it, so its n_det holds the detected counts (otherwise n_kp does)
+    int strongest = 0;
+    bool sel_used[2] = {false, false};
     // vo_match staging
     uint8_t* d_fd[2] = {nullptr, nullptr};
     DescMeta* d_fm[2] = {nullptr, nullptr};
@@ -130,13 +135,14 @@ struct vo_ctx {
     // set, result copies).  A slot outlives its buffer set's reuse by batch n+2.
     struct StepHost {
         FrameGeom* fg = nullptr; int* nkp = nullptr; int* ncand = nullptr; int* np = nullptr; int* rows = nullptr;
+        int* ndet = nullptr;                               // detected counts (selectStrongest on; else nkp is both)
         float* pX = nullptr; uint8_t* pkeep = nullptr;     // the batch's packed landmark rows (pinned)
         float* d_pX = nullptr; uint8_t* d_pkeep = nullptr; // ... and on the device (k_lm_pack)
         hipEvent_t ev = nullptr;                           // end of the batch on `stream`
     };
     StepHost sh[VO_STEP_DEPTH];
     hipStream_t copy_stream = nullptr;
-    struct Pending { int set, slot, B; bool first_tracked; };
+    struct Pending { int set, slot, B; bool first_tracked; bool sel; };
     std::deque<Pending> pending;
     int next_step_set = 0, next_slot = 0;
     std::vector<void*> lm_retired;                   // landmark stores replaced by a larger one (freed at reset)
@@ -238,6 +244,7 @@ static void destroy_buffers(vo_ctx* c)
     geom_free(c->aux.gb);
     for (int k = 0; k < VO_STEP_DEPTH; ++k) {
         hipHostFree(c->sh[k].fg); hipHostFree(c->sh[k].nkp); hipHostFree(c->sh[k].ncand); hipHostFree(c->sh[k].np); hipHostFree(c->sh[k].rows);
+        hipHostFree(c->sh[k].ndet);
         hipHostFree(c->sh[k].pX); hipHostFree(c->sh[k].pkeep);
         hipFree(c->sh[k].d_pX); hipFree(c->sh[k].d_pkeep);
         const hipEvent_t ev = c->sh[k].ev;               // owned by destroy_streams
@@ -391,6 +398,7 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         if ((e = hipHostMalloc((void**)&H.fg, sizeof(FrameGeom) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
         if ((e = hipHostMalloc((void**)&H.nkp, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
         if ((e = hipHostMalloc((void**)&H.ncand, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
+        if ((e = hipHostMalloc((void**)&H.ndet, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
         if ((e = hipHostMalloc((void**)&H.np, sizeof(int) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
         if ((e = hipHostMalloc((void**)&H.rows, sizeof(int) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
         if ((e = hipHostMalloc((void**)&H.pX, sizeof(float) * 3 * max_batch * kp_cap, 0)) != hipSuccess) return bail("pinned", e);
@@ -538,10 +546,12 @@ int vo_sift_ex(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int co
     int rc_stage = stage_images(c, img, ld, col_major, 1, c->d_img);
     if (rc_stage) return rc_stage;
     ImageSrc src{c->d_img, c->d_img, (size_t)rows * cols, cols, 0};
-    sift_enqueue(c->py, c->sb, src, 1, c->sp, c->stream, c->d_py);
+    sift_enqueue(c->py, c->sb, src, 1, c->sp, c->stream, c->d_py, c->strongest);
     c->last_set = 0;                                   // vo_fetch_* now read this result (set 0)
-    int n = 0, n_cand = 0;
+    c->sel_used[0] = c->strongest > 0;
+    int n = 0, n_cand = 0, n_det = -1;
     HIPC(c, hipMemcpyAsync(&n, c->sb.n_kp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (c->strongest > 0) HIPC(c, hipMemcpyAsync(&n_det, c->sb.n_det, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(&n_cand, c->sb.n_cand, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     int rc = finish(c);
     if (rc) return rc;
@@ -554,7 +564,9 @@ int vo_sift_ex(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int co
     if (n_cand > c->sb.cand_cap)
         return fail(c, VO_ERR_CAPACITY, "vo_sift: %d extremum candidates exceed the candidate list (%d = 4 x max_keypoints)",
                     n_cand, c->sb.cand_cap);
-    if (n > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed max_keypoints %d", n, c->sb.kp_cap);
+    if (n_det < 0) n_det = n;                          // selection off: the detected count
+    if (n_det > c->sb.kp_cap)
+        return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed max_keypoints %d", n_det, c->sb.kp_cap);
     if (n > capacity) return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed capacity %d", n, capacity);
     return VO_OK;
 }
@@ -671,6 +683,36 @@ int vo_fetch_rectified(vo_ctx* c, int image, uint8_t* out, int capacity)
     HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
     const uint8_t* src = c->d_rect + ((size_t)(image & 1) * c->max_batch + (image >> 1)) * fs;
     HIPC(c, hipMemcpy(out, src, fs, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
+// ---- SIFTPoints.selectStrongest (VO.m:140, 206, 217-218: "limit the number of points kept") ----
+int vo_set_strongest(vo_ctx* c, int n)
+{
+    if (!c) return VO_ERR_ARG;
+    if (n < 0 || n > c->sp.max_keypoints)
+        return fail(c, VO_ERR_ARG, "vo_set_strongest: n = %d outside 0 (off) .. max_keypoints = %d", n, c->sp.max_keypoints);
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_set_strongest: step batches pending (vo_step_collect first)");
+    if (n > 0) {
+        hipSetDevice(c->device);
+        HIPC(c, sift_alloc_select(c->sb));
+        HIPC(c, sift_alloc_select(c->aux.sb));
+    }
+    c->strongest = n;
+    return VO_OK;
+}
+
+int vo_fetch_detected_count(vo_ctx* c, int image, int* n_detected)
+{
+    if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_detected_count: bad image");
+    hipSetDevice(c->device);
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
+    const bool aux = c->last_set == 1 && image < 2 * c->max_batch;
+    const SiftBuffers& B = aux ? c->aux.sb : c->sb;
+    int cnt = 0;
+    HIPC(c, hipMemcpy(&cnt, (c->sel_used[aux ? 1 : 0] ? B.n_det : B.n_kp) + image, sizeof(int), hipMemcpyDeviceToHost));
+    if (n_detected) *n_detected = cnt;
     return VO_OK;
 }
 
@@ -968,6 +1010,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
     const int o_small = sift_small_octave(c->py);
     const bool undist = c->ud_on[0] || c->ud_on[1];           // vo_set_distortion
     if (undist) c->rect_B = B;
+    c->sel_used[set] = c->strongest > 0;
     const bool ext_on_st = VO_EXT_SPLIT || VO_SMALL_STREAM != 0;   // the test of octaves 1.. on st
     // scale space on sp; octave 0's extremum test on st as soon as octave 0 is built (beside the
     // scale space of octaves 1..), the other octaves' on st after the scale space (VO_EXT_SPLIT)
@@ -1020,7 +1063,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
             if (VO_SMALL_STREAM == 2) HIPC(c, hipStreamWaitEvent(st, c->ev_small[p], 0));
             sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, o_small, c->py.n_oct);
         }
-        sift_enqueue_features(c->py, v, 2 * nf, c->sp, st, c->d_py);
+        sift_enqueue_features(c->py, v, 2 * nf, c->sp, st, c->d_py, c->strongest);
         if (p == parts - 1) HIPC(c, hipEventRecord(c->ev_arena[set], st));
         match_launch(match_view(*S.mb, f0), S.jobs + f0, nf, c->mp, st);
     }
@@ -1048,7 +1091,12 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
     }
     SetRef S = set_ref(c, set);
     std::vector<int> nk(2 * B), nc(2 * B), np(B);
+    std::vector<int> nd;                     // detected counts: the flags' input (selection off: nk)
     HIPC(c, hipMemcpyAsync(nk.data(), S.sb->n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    if (c->strongest > 0) {
+        nd.resize(2 * B);
+        HIPC(c, hipMemcpyAsync(nd.data(), S.sb->n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPC(c, hipMemcpyAsync(nc.data(), S.sb->n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(np.data(), S.pair_n, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     rc = finish(c);
@@ -1056,7 +1104,7 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
     if (stats) {
         for (int f = 0; f < B; ++f) {
             stats[f].n_left = nk[2 * f]; stats[f].n_right = nk[2 * f + 1]; stats[f].n_stereo = np[f];
-            stats[f].flags = capacity_flags(c->sb, nk.data() + 2 * f, nc.data() + 2 * f, 2);
+            stats[f].flags = capacity_flags(c->sb, (nd.empty() ? nk : nd).data() + 2 * f, nc.data() + 2 * f, 2);
         }
     }
     return VO_OK;
@@ -1199,6 +1247,8 @@ static int enqueue_carry(vo_ctx* c, int from, int f, int to)
         HIPC(c, hipMemcpyAsync(Z.sb->meta + (size_t)dst * K, A.sb->meta + (size_t)src * K, sizeof(DescMeta) * K,
                                hipMemcpyDeviceToDevice, c->stream));
         HIPC(c, hipMemcpyAsync(Z.sb->n_kp + dst, A.sb->n_kp + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        if (c->strongest > 0)
+            HIPC(c, hipMemcpyAsync(Z.sb->n_det + dst, A.sb->n_det + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPC(c, hipMemcpyAsync(Z.pair_i + (size_t)M * K, A.pair_i + (size_t)f * K, sizeof(int) * K, hipMemcpyDeviceToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(Z.pair_j + (size_t)M * K, A.pair_j + (size_t)f * K, sizeof(int) * K, hipMemcpyDeviceToDevice, c->stream));
@@ -1235,6 +1285,8 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     vo_ctx::StepHost& H = c->sh[slot];
     HIPC(c, hipMemcpyAsync(H.fg, S.gb->fg, sizeof(FrameGeom) * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(H.nkp, S.sb->n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    if (c->strongest > 0)
+        HIPC(c, hipMemcpyAsync(H.ndet, S.sb->n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(H.ncand, S.sb->n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(H.np, S.pair_n, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(H.rows, S.gb->lm_rows, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
@@ -1243,7 +1295,7 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     HIPC(c, hipEventRecord(H.ev, c->stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
-    c->pending.push_back({set, slot, B, c->have_features});
+    c->pending.push_back({set, slot, B, c->have_features, c->strongest > 0});
     c->next_step_set ^= 1;
     c->next_slot = (slot + 1) % VO_STEP_DEPTH;
     c->have_features = true;
@@ -1319,7 +1371,7 @@ static int collect_batch(vo_ctx* c, vo_step_out* outs, int capacity, int* n_out)
         vo_step_out& o = outs[f];
         memset(&o, 0, sizeof(o));
         o.n_left = H.nkp[2 * f]; o.n_right = H.nkp[2 * f + 1]; o.n_stereo = H.np[f];
-        o.flags = capacity_flags(c->sb, H.nkp + 2 * f, H.ncand + 2 * f, 2);
+        o.flags = capacity_flags(c->sb, (P.sel ? H.ndet : H.nkp) + 2 * f, H.ncand + 2 * f, 2);
         memcpy(o.rel_pose, I4, sizeof(I4));
         const bool tracked = f > 0 || P.first_tracked;
         if (c->lm_camera) {
@@ -1621,6 +1673,7 @@ int vo_track(vo_ctx* c, const uint8_t* old_l, const uint8_t* old_r, int n_old, c
     BEGIN_CALL(c);
     c->have_features = false;
     c->last_set = 0;                                   // set 0's descriptor slots are overwritten
+    c->sel_used[0] = false;
     int rc;
     if ((rc = upload_desc(c, 2 * M, old_l, n_old))) return rc;
     if ((rc = upload_desc(c, 2 * M + 1, old_r, n_old))) return rc;

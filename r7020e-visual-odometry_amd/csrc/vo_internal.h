@@ -149,7 +149,10 @@ struct SiftBuffers {
     int* n_acc = nullptr;              // [n_img]
     CandOut* cout = nullptr;           // [n_img][cand_cap]
     uint32_t* koff = nullptr;          // [n_img][cand_cap]
-    int* n_kp = nullptr;               // [n_img]  (uncapped count)
+    int* n_kp = nullptr;               // [n_img]  (uncapped count; with selectStrongest the selected count)
+    int* n_det = nullptr;              // [n_img]  detected count ahead of selectStrongest (written only while it is on)
+    unsigned long long* skey = nullptr;  // [n_img][cand_cap] selectStrongest keys in acc order (sift_alloc_select)
+    uint32_t* snpk = nullptr;          // [n_img][cand_cap] ... and peak counts
     vo_keypoint* kp = nullptr;         // [n_img][kp_cap]
     KpInt* kpi = nullptr;              // [n_img][kp_cap]
     uint8_t* desc = nullptr;           // [n_img][kp_cap][128]
@@ -174,11 +177,13 @@ bool sift_params_supported(const vo_sift_params& p);
 // View of images [img0, img0 + n) of b: every per-image array shifted (image-major layout).
 SiftBuffers sift_view(const SiftBuffers& b, const Pyramid& py, int img0, int n);
 hipError_t sift_alloc(SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_cap);
+hipError_t sift_alloc_select(SiftBuffers& b);     // selectStrongest's key arrays (first vo_set_strongest(n > 0))
 void sift_free(SiftBuffers& b);
 // Enqueue the whole detect+describe pipeline for n_img images (<= allocated).
-// d_py is a device copy of py.
+// d_py is a device copy of py.  strongest > 0: SIFTPoints.selectStrongest(points, strongest) between
+// detection and description (k_sel_keys / k_sel_rank; needs sift_alloc_select); 0 launches neither.
 void sift_enqueue(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img,
-                  const vo_sift_params& p, hipStream_t s, const Pyramid* d_py);
+                  const vo_sift_params& p, hipStream_t s, const Pyramid* d_py, int strongest = 0);
 // The phases of sift_enqueue: the scale space of the large octaves (base, level blurs, octave
 // bases; ev_o0, if given, is recorded once octave 0 is complete); its tail (the LDS-sized octaves
 // and the extremum test of octaves [ext_o_begin, n_oct)); the extremum test of an octave range;
@@ -195,7 +200,7 @@ void sift_enqueue_extrema(const Pyramid& py, SiftBuffers& b, int n_img, const vo
 int sift_small_octave(const Pyramid& py);
 void sift_enqueue_small(const Pyramid& py, SiftBuffers& b, int n_img, hipStream_t s, const Pyramid* d_py);
 void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
-                           const Pyramid* d_py);
+                           const Pyramid* d_py, int strongest = 0);
 
 // ---------------------------------------------------------------------------
 // undistortImage (undistort.hip): k_undistort remaps B frames of one or two cameras in one

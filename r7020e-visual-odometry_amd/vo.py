@@ -108,6 +108,7 @@ EXPORTS = [
     "vo_sift_ex", "vo_step_batch_ex", "vo_chain_poses", "vo_landmarks_to_world_frames", "vo_landmarks_world_dev",
     "vo_fetch_candidate_counts", "vo_default_match_opts", "vo_match_ex", "vo_match_f32_ex",
     "vo_undistort", "vo_undistort_batch_dev", "vo_set_distortion", "vo_fetch_rectified",
+    "vo_set_strongest", "vo_fetch_detected_count",
 ]
 
 # the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the experimental kernels kept
@@ -164,6 +165,8 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_undistort_batch_dev.argtypes = [vp, vp, C.c_int, P(Distortion), vp]
     L.vo_set_distortion.argtypes = [vp, P(Distortion), P(Distortion)]
     L.vo_fetch_rectified.argtypes = [vp, C.c_int, P(C.c_uint8), C.c_int]
+    L.vo_set_strongest.argtypes = [vp, C.c_int]
+    L.vo_fetch_detected_count.argtypes = [vp, C.c_int, P(C.c_int)]
     L.vo_track.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int,
                            P(C.c_uint32), C.c_int, P(C.c_int)]
     L.vo_triangulate.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double)]
@@ -376,6 +379,20 @@ class Context:
         out = np.empty((self.rows, self.cols), np.uint8)
         self._check(self.lib.vo_fetch_rectified(self.h, image, _p(out, C.c_uint8), out.size))
         return out
+
+    # ---- SIFTPoints.selectStrongest ----
+    def set_strongest(self, n: int) -> None:
+        """points = selectStrongest(points, n) between detection and description in every entry
+        that detects (vo_set_strongest): per image the n keypoints of largest response, sorted by
+        response descending with ties in detection order.  0 turns it off (the default)."""
+        self._check(self.lib.vo_set_strongest(self.h, int(n)))
+
+    def fetch_detected_count(self, image: int) -> int:
+        """The keypoint count of image 2*frame + side of the last call ahead of the selection
+        (vo_fetch_detected_count)."""
+        n = C.c_int(0)
+        self._check(self.lib.vo_fetch_detected_count(self.h, image, C.byref(n)))
+        return n.value
 
     # ---- matchFeatures ----
     def _match_opts(self, unique, match_threshold, max_ratio) -> MatchOpts:
@@ -714,11 +731,23 @@ def _default_ctx(rows: int, cols: int) -> Context:
     return _ctx_cache[key]
 
 
-def detectSIFTFeatures(I: np.ndarray):
+def _sift_strongest(I: np.ndarray, strongest):
+    """sift() of the default context with selectStrongest(points, strongest) for this call only."""
+    ctx = _default_ctx(*I.shape)
+    ctx.set_strongest(0 if strongest is None else strongest)
+    try:
+        return ctx.sift(I)
+    finally:
+        ctx.set_strongest(0)
+
+
+def detectSIFTFeatures(I: np.ndarray, strongest: int | None = None):
     """detectSIFTFeatures(I) (VO.m:79-80) fused with its descriptor pass: returns
     (points, descriptors) where points is a structured array with MATLAB
-    1-based Location (x, y), Scale, Orientation (angle), Metric (response)."""
-    return _default_ctx(*I.shape).sift(I)
+    1-based Location (x, y), Scale, Orientation (angle), Metric (response).
+    strongest=N is selectStrongest(detectSIFTFeatures(I), N): the N points of largest Metric,
+    sorted, and only their descriptors computed."""
+    return _sift_strongest(I, strongest)
 
 
 def undistortImage(I: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0)) -> np.ndarray:
@@ -729,13 +758,13 @@ def undistortImage(I: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.
     return _default_ctx(*I.shape).undistort(I, K, radial, tangential)
 
 
-def extractFeatures(I: np.ndarray, points=None, Method: str = "SIFT"):
+def extractFeatures(I: np.ndarray, points=None, Method: str = "SIFT", strongest: int | None = None):
     """extractFeatures(I, points, "Method", "SIFT") (VO.m:83-84) -> (features, validPoints).
     SIFT descriptors are computed in the same device pass as detection; all
-    points are valid."""
+    points are valid.  strongest=N describes selectStrongest(points, N) only."""
     if Method != "SIFT":
         raise VOError(VO_ERR_ARG, "only Method 'SIFT' is on the hot path")
-    kps, desc = _default_ctx(*I.shape).sift(I)
+    kps, desc = _sift_strongest(I, strongest)
     return desc, kps
 
 
