@@ -88,7 +88,24 @@ extern "C" {
 
 /* detectSIFTFeatures / extractFeatures defaults (MATLAB R2022b+).
  * contrast_threshold is in OpenCV units: MATLAB's ContrastThreshold 0.0133
- * equals 0.04 / NumLayersInOctave. */
+ * equals 0.04 / NumLayersInOctave.
+ *
+ * Accepted ranges.  vo_create checks the block before any HIP call and returns NULL, with the
+ * offending field named in vo_last_error(NULL), for anything else:
+ *   n_octave_layers     1 .. 5.
+ *   sigma               finite, > 0, and small enough that every blur of the scale space has a
+ *                       kernel radius of at most 40 (VO_SIFT_MAX_RADIUS in vo_spec.h).  Level i
+ *                       (1 .. n_octave_layers + 2) blurs with
+ *                         s_i = sigma 2^((i - 1) / L) sqrt(2^(2 / L) - 1),  L = n_octave_layers,
+ *                       at radius (round(8 s_i + 1) | 1) / 2; the top level binds:
+ *                       sigma <= 1.45 at L = 1, 3.55 at L = 2, 5.2 at L = 3, 6.5 at L = 4,
+ *                       7.7 at L = 5.  (The default sigma 1.6 is therefore refused at L = 1.)
+ *   contrast_threshold  finite, >= 0.  The extremum pre-test uses floor(0.5 ct / L * 255), which is 0
+ *                       below ct = 2 L / 255.
+ *   edge_threshold      finite, > 0.
+ *   upsample            0 or non-zero (non-zero: first octave is the x2 upsampled image).
+ *   max_keypoints       >= 16.
+ * Every accepted block gives the CPU specification's keypoints and descriptors bit for bit. */
 typedef struct {
     int32_t n_octave_layers;      /* NumLayersInOctave, 3 */
     float   sigma;                /* Sigma, 1.6 */

@@ -362,13 +362,23 @@ VO_HD double vo_base_sigma(double sigma, int upsample)
     return sqrt(v);
 }
 
+/* Radius vo_gauss_kernel gives for s (ksize / 2), without building the kernel; -1 when s is not
+ * finite and positive or the radius exceeds VO_SIFT_MAX_RADIUS (the bound keeps the int cast defined). */
+VO_HD int vo_gauss_radius(double s)
+{
+    if (!(s > 0.0) || !(s * 8.0 + 1.0 < 4.0 * VO_SIFT_MAX_RADIUS)) return -1;
+    int r = (vo_round_d(s * 8.0 + 1.0) | 1) / 2;
+    return r <= VO_SIFT_MAX_RADIUS ? r : -1;
+}
+
 /* Gaussian kernel (getGaussianKernel for float images, ksize = round(8s+1)|1).
- * Writes k[0..radius] (centre first); returns radius or -1 if > cap-1. */
+ * Writes k[0..radius] (centre first); returns radius, or -1 (nothing written) if it is > cap-1
+ * or > VO_SIFT_MAX_RADIUS (the size of t[] below). */
 VO_HD int vo_gauss_kernel(double s, float* k, int cap)
 {
-    int ksize = vo_round_d(s * 8.0 + 1.0) | 1;
-    int r = ksize / 2;
-    if (r + 1 > cap) return -1;
+    int r = vo_gauss_radius(s);
+    if (r < 0 || r + 1 > cap) return -1;
+    int ksize = 2 * r + 1;
     double t[2 * VO_SIFT_MAX_RADIUS + 1];
     double sum = 0.0, scale2x = -0.5 / (s * s);
     for (int i = 0; i < ksize; ++i) {
@@ -379,6 +389,20 @@ VO_HD int vo_gauss_kernel(double s, float* k, int cap)
     sum = 1.0 / sum;
     for (int i = 0; i <= r; ++i) k[i] = (float)(t[r + i] * sum);
     return r;
+}
+
+/* Whether every blur of the scale space has a kernel: the base blur and the level blurs 1..L+2
+ * (vo_base_sigma, vo_level_sigmas) all within VO_SIFT_MAX_RADIUS.  The top level binds:
+ * sigma <~ 1.45 at L = 1, 3.55 at L = 2, 5.2 at L = 3, 6.5 at L = 4, 7.7 at L = 5. */
+VO_HD int vo_sift_radii_ok(int L, double sigma, int upsample)
+{
+    if (L < 1 || L + 3 > VO_SIFT_MAX_LAYERS || !(sigma > 0.0)) return 0;
+    double sig[VO_SIFT_MAX_LAYERS];
+    vo_level_sigmas(L, sigma, sig);
+    if (vo_gauss_radius(vo_base_sigma(sigma, upsample)) < 0) return 0;
+    for (int i = 1; i < L + 3; ++i)
+        if (vo_gauss_radius(sig[i]) < 0) return 0;
+    return 1;
 }
 
 /* reflect-101 border index (OpenCV BORDER_REFLECT_101, iterated) */

@@ -26,6 +26,12 @@
 extern "C" {
 #endif
 
+/* 1 for the parameter blocks the spec covers (the ones vo_create accepts): 1..5 layers, finite
+ * sigma > 0 with every blur radius <= VO_SIFT_MAX_RADIUS, finite contrast_threshold >= 0 and
+ * edge_threshold > 0.  oracle_sift, oracle_pyramid, oracle_run_sequence and
+ * oracle_sift_match_pair return -1 for any other block and compute nothing. */
+int oracle_sift_params_ok(const vo_sift_params* p);
+
 /* SIFT detect + describe (VO.m:79-84). Returns number of keypoints (may be >
  * capacity; only capacity written), or <0 on error. */
 int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,

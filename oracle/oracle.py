@@ -138,6 +138,16 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _check_params(n: int, p: SiftParams, what: str) -> int:
+    """A negative count is the oracle refusing the parameter block (oracle_sift_params_ok)."""
+    if n < 0:
+        raise ValueError(f"oracle.{what}: unsupported SIFT parameters (n_octave_layers={p.n_octave_layers}, "
+                         f"sigma={p.sigma}, contrast_threshold={p.contrast_threshold}, "
+                         f"edge_threshold={p.edge_threshold}, upsample={p.upsample}): a blur radius beyond "
+                         "VO_SIFT_MAX_RADIUS or a field out of range")
+    return n
+
+
 def sift(img: np.ndarray, params: SiftParams | None = None, cv: bool = False):
     """-> (keypoints structured array, descriptors [n,128] u8)"""
     img = np.ascontiguousarray(img, np.uint8)
@@ -147,13 +157,15 @@ def sift(img: np.ndarray, params: SiftParams | None = None, cv: bool = False):
     desc = np.zeros((cap, 128), np.uint8)
     n = lib(cv).oracle_sift(_p(img, C.c_uint8), img.shape[0], img.shape[1], img.shape[1], C.byref(p),
                           kps.ctypes.data_as(C.POINTER(Keypoint)), _p(desc, C.c_uint8), cap)
-    n = min(n, cap)
+    n = min(_check_params(n, p, "sift"), cap)
     return kps[:n].copy(), desc[:n].copy()
 
 
 def gauss_kernel(sigma: float) -> np.ndarray:
     k = np.zeros(64, np.float32)
     r = lib().oracle_gauss_kernel(sigma, _p(k, C.c_float), 64)
+    if r < 0:
+        raise ValueError(f"oracle.gauss_kernel: sigma={sigma} has no kernel (radius beyond VO_SIFT_MAX_RADIUS = 40)")
     return k[: r + 1].copy()
 
 
@@ -176,6 +188,7 @@ def pyramid(img: np.ndarray, params: SiftParams | None = None) -> np.ndarray:
     img = np.ascontiguousarray(img, np.uint8)
     p = params or sift_params()
     n = lib().oracle_pyramid(_p(img, C.c_uint8), img.shape[0], img.shape[1], img.shape[1], C.byref(p), None)
+    _check_params(n, p, "pyramid")
     out = np.empty(n, np.float32)
     lib().oracle_pyramid(_p(img, C.c_uint8), img.shape[0], img.shape[1], img.shape[1], C.byref(p), _p(out, C.c_float))
     return out
@@ -278,12 +291,14 @@ def run_sequence(L, R, P1, P2, sp=None, mp=None, rp=None, lm_cap: int = 1 << 20,
     cal = calib_from(P1, P2)
     X = np.zeros((lm_cap, 3), np.float32) if camera_rows else None
     keep = np.zeros(lm_cap, np.uint8) if camera_rows else None
+    sp = sp or sift_params()
     n = lib(cv).oracle_run_sequence(_p(L, C.c_uint8), _p(R, C.c_uint8), F, rows, cols, C.byref(cal),
-                                  C.byref(sp or sift_params()), C.byref(mp or match_params()),
+                                  C.byref(sp), C.byref(mp or match_params()),
                                   C.byref(rp or ransac_params()), outs.ctypes.data_as(C.POINTER(StepOut)),
                                   _p(lm, C.c_double), lm_cap, key0,
                                   _p(X, C.c_float) if camera_rows else None,
                                   _p(keep, C.c_uint8) if camera_rows else None)
+    _check_params(n, sp, "run_sequence")
     if camera_rows:
         return outs, (X[:n].copy(), keep[:n].astype(bool))
     return outs, lm[:n].copy()
@@ -304,10 +319,11 @@ def sift_match_pair(left, right, sp=None, mp=None):
     left = np.ascontiguousarray(left, np.uint8)
     right = np.ascontiguousarray(right, np.uint8)
     nl, nr = C.c_int(0), C.c_int(0)
+    sp = sp or sift_params()
     S = lib().oracle_sift_match_pair(_p(left, C.c_uint8), _p(right, C.c_uint8), left.shape[0], left.shape[1],
-                                     C.byref(sp or sift_params()), C.byref(mp or match_params()),
+                                     C.byref(sp), C.byref(mp or match_params()),
                                      C.byref(nl), C.byref(nr))
-    return S, nl.value, nr.value
+    return _check_params(S, sp, "sift_match_pair"), nl.value, nr.value
 
 
 SPEC_FN = {"expf": 0, "atan2_deg": 1, "sin_deg": 2, "cos_deg": 3, "exp_d": 4, "log_d": 5, "rcp_nr": 6, "sift_wt": 7}

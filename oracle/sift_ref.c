@@ -116,6 +116,19 @@ typedef struct {
     octave_t oct[VO_SIFT_MAX_OCTAVES];
 } pyramid_t;
 
+/* The parameter blocks the spec covers (those vo_create accepts): 1..5 layers, a finite sigma > 0
+ * whose blur radii all stay within VO_SIFT_MAX_RADIUS (vo_gauss_kernel has no kernel beyond it),
+ * finite thresholds with contrast >= 0 and edge > 0. */
+int oracle_sift_params_ok(const vo_sift_params* p)
+{
+    if (p->n_octave_layers < 1 || p->n_octave_layers > 5) return 0;
+    if (!isfinite(p->sigma) || !(p->sigma > 0.0f)) return 0;
+    if (!isfinite(p->contrast_threshold) || p->contrast_threshold < 0.0f) return 0;
+    if (!isfinite(p->edge_threshold) || !(p->edge_threshold > 0.0f)) return 0;
+    return vo_sift_radii_ok(p->n_octave_layers, p->sigma, p->upsample);
+}
+
+/* caller has checked oracle_sift_params_ok(p): every radius below is >= 0 */
 static void build_pyramid(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
                           pyramid_t* py)
 {
@@ -167,6 +180,7 @@ static void free_pyramid(pyramid_t* py)
 
 long oracle_pyramid(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p, float* out)
 {
+    if (!oracle_sift_params_ok(p)) return -1;
     int n_oct = vo_num_octaves(rows, cols, p->upsample), L = p->n_octave_layers;
     long total = 0;
     int r = p->upsample ? rows * 2 : rows, c = p->upsample ? cols * 2 : cols;
@@ -509,6 +523,7 @@ static int cv_remove_duplicated_sorted(vo_keypoint* kps, uint8_t* desc, int n)
 int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
                 vo_keypoint* kps, uint8_t* desc, int capacity)
 {
+    if (!oracle_sift_params_ok(p)) return -1;
     pyramid_t py;
     build_pyramid(img, rows, cols, ld, p, &py);
     const int L = py.L;

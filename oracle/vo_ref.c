@@ -666,6 +666,7 @@ long oracle_run_sequence(const uint8_t* lefts, const uint8_t* rights, int F, int
                          const vo_ransac_params* rp, vo_step_out* outs, double* lm_out, long lm_cap,
                          uint32_t key0, float* lm_cam_X, uint8_t* lm_cam_keep)
 {
+    if (!oracle_sift_params_ok(sp)) return -1;
     int cap = sp->max_keypoints;
     vo_keypoint *kl = malloc(sizeof(vo_keypoint) * cap), *kr = malloc(sizeof(vo_keypoint) * cap);
     uint8_t *dl = malloc((size_t)cap * 128), *dr = malloc((size_t)cap * 128);
@@ -750,6 +751,7 @@ int oracle_sift_match_pair(const uint8_t* left, const uint8_t* right, int rows, 
                            const vo_sift_params* sp, const vo_match_params* mp,
                            int* n_left, int* n_right)
 {
+    if (!oracle_sift_params_ok(sp)) return -1;
     int cap = sp->max_keypoints;
     vo_keypoint *kl = malloc(sizeof(vo_keypoint) * cap), *kr = malloc(sizeof(vo_keypoint) * cap);
     uint8_t *dl = malloc((size_t)cap * 128), *dr = malloc((size_t)cap * 128);

@@ -2712,14 +2712,25 @@ void sift_enqueue_pyramid_tail(const Pyramid& py, SiftBuffers& b, int n_img, con
 // weight < 361 * 2^10, |dI| <= 255), and a column receives 1/VO_ORIENT_COLS of the window's samples:
 // the window fits while (2r + 1)^2 <= VO_ORIENT_COLS * floor(2^32 / (361 * 2^10)).  r bounds the
 // orientation radius round(4.5 scl) for any refined scale (scl < sigma 2^((L + 0.5) / L), k_refine):
-// sigma up to ~17 at L = 1, ~21 at L = 3.
-bool sift_params_supported(const vo_sift_params& p)
+// that alone would allow sigma up to ~17 at L = 1, ~21 at L = 3.
+// The blur kernels bind much earlier: every level's radius (round(8 s_i + 1) | 1) / 2 and the base
+// blur's must be at most VO_SIFT_MAX_RADIUS (vo_sift_radii_ok, the same computation as
+// build_pyramid_geometry) -- sigma <~ 1.45 at L = 1, 3.55 at L = 2, 5.2 at L = 3, 6.5 at L = 4,
+// 7.7 at L = 5.  Beyond it vo_gauss_kernel has no kernel and the blurs would run on radius -1.
+// -> nullptr when the block is supported, else the name of the field that is not.
+const char* sift_params_refusal(const vo_sift_params& p)
 {
-    if (!(p.sigma > 0.0f) || !std::isfinite(p.sigma) || p.n_octave_layers < 1) return false;
+    if (p.n_octave_layers < 1 || p.n_octave_layers > 5) return "n_octave_layers";
+    if (p.max_keypoints < 16) return "max_keypoints";
+    if (!(p.sigma > 0.0f) || !std::isfinite(p.sigma)) return "sigma";
+    if (!std::isfinite(p.contrast_threshold) || p.contrast_threshold < 0.0f) return "contrast_threshold";
+    if (!std::isfinite(p.edge_threshold) || !(p.edge_threshold > 0.0f)) return "edge_threshold";
     const double scl = p.sigma * std::exp2((p.n_octave_layers + 0.5) / p.n_octave_layers);
     const double r = std::ceil(VO_SIFT_ORI_RADIUS * scl) + 1;
     const double per_column = std::floor(4294967296.0 / (361.0 * VO_DESC_FX_SCALE));
-    return (2 * r + 1) * (2 * r + 1) <= VO_ORIENT_COLS * per_column;
+    if (!((2 * r + 1) * (2 * r + 1) <= VO_ORIENT_COLS * per_column)) return "sigma";
+    if (!vo_sift_radii_ok(p.n_octave_layers, p.sigma, p.upsample)) return "sigma";
+    return nullptr;
 }
 
 // Largest descriptor window radius any keypoint can have: k_refine accepts layer <= L with

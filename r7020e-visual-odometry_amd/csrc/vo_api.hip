@@ -274,6 +274,16 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         fail(nullptr, VO_ERR_ARG, "vo_create: bad size rows=%d cols=%d max_batch=%d", rows, cols, max_batch);
         return nullptr;
     }
+    {   // the parameter block, like the size, is checked before any HIP call
+        vo_sift_params sp;
+        if (sift) sp = *sift; else vo_default_sift_params(&sp);
+        if (const char* field = sift_params_refusal(sp)) {
+            fail(nullptr, VO_ERR_ARG, "vo_create: unsupported sift params: %s (n_octave_layers=%d sigma=%g contrast_threshold=%g "
+                 "edge_threshold=%g upsample=%d max_keypoints=%d)", field, sp.n_octave_layers, (double)sp.sigma,
+                 (double)sp.contrast_threshold, (double)sp.edge_threshold, sp.upsample, sp.max_keypoints);
+            return nullptr;
+        }
+    }
     if (hipSetDevice(device) != hipSuccess) { fail(nullptr, VO_ERR_HIP, "hipSetDevice(%d) failed", device); return nullptr; }
     vo_ctx* c = new vo_ctx();
     c->device = device; c->rows = rows; c->cols = cols; c->max_batch = max_batch;
@@ -282,12 +292,6 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
     if (ransac) c->rp = *ransac; else vo_default_ransac_params(&c->rp);
     if (calib) { c->calib = *calib; c->has_calib = true; }
     memcpy(c->pose, I4, sizeof(I4));
-    if (c->sp.n_octave_layers < 1 || c->sp.n_octave_layers > 5 || c->sp.max_keypoints < 16 ||
-        !sift_params_supported(c->sp)) {
-        fail(nullptr, VO_ERR_ARG, "vo_create: bad sift params");
-        delete c;
-        return nullptr;
-    }
     auto bail = [&](const char* what, hipError_t e) -> vo_ctx* {
         fail(nullptr, VO_ERR_HIP, "vo_create: %s: %s", what, hipGetErrorString(e));
         destroy_buffers(c);

@@ -91,3 +91,83 @@ def test_create_rejects_bad_sizes_before_touching_the_gpu(vo, rows, cols, batch)
     assert not h
     msg = lib.vo_last_error(None).decode()
     assert "bad size" in msg and f"max_batch={batch}" in msg, msg
+
+
+# (n_octave_layers, sigma, upsample): the top level's blur radius (round(8 s + 1) | 1) / 2 is 45, 46, 47
+# (and 41 at (3, 5.3), the first beyond the cap) -- beyond VO_SIFT_MAX_RADIUS = 40, where
+# vo_gauss_kernel has no kernel
+RADIUS_REFUSED = [(1, 1.6, 1), (2, 4.0, 1), (3, 6.0, 1), (1, 1.6, 0), (2, 4.0, 0), (3, 6.0, 0), (3, 5.3, 1)]
+
+
+def _sift_block(vo, **kw):
+    p = vo.default_sift_params()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _create_refused(vo, p):
+    """vo_create on a good size with SIFT block p -> the vo_last_error(NULL) message of the refusal."""
+    import ctypes
+    lib = vo.load_library()
+    h = lib.vo_create(0, 64, 64, 1, None, ctypes.byref(p), None, None)
+    if h:
+        lib.vo_destroy(ctypes.c_void_p(h))
+    assert not h, "vo_create accepted an unsupported parameter block"
+    msg = lib.vo_last_error(None).decode()
+    assert "bad size" not in msg and "unsupported sift params" in msg, msg
+    return msg
+
+
+@pytest.mark.parametrize("L,sigma,upsample", RADIUS_REFUSED)
+def test_create_refuses_blur_radii_beyond_the_cap_before_touching_the_gpu(vo, oracle, L, sigma, upsample):
+    """A level radius above VO_SIFT_MAX_RADIUS (vo_gauss_kernel returns -1 and writes no kernel) is
+    refused by vo_create before any HIP call, naming sigma, and by the oracle: neither blurs with a
+    radius of -1 and an uninitialised kernel.  The bound lies far inside the orientation bound."""
+    import numpy as np
+    msg = _create_refused(vo, _sift_block(vo, n_octave_layers=L, sigma=sigma, upsample=upsample))
+    assert ": sigma " in msg and f"n_octave_layers={L}" in msg, msg
+    rp = oracle.SiftParams(L, sigma, 0.04, 10.0, upsample, 16384)
+    img = np.random.default_rng(11).integers(0, 256, (64, 64)).astype(np.uint8)
+    with pytest.raises(ValueError):
+        oracle.sift(img, rp)
+    with pytest.raises(ValueError):
+        oracle.pyramid(img, rp)
+    with pytest.raises(ValueError):
+        oracle.run_sequence(np.stack([img, img]), np.stack([img, img]), np.eye(3, 4), np.eye(3, 4), sp=rp)
+
+
+@pytest.mark.parametrize("field,value", [
+    ("contrast_threshold", float("nan")), ("contrast_threshold", float("inf")), ("contrast_threshold", -0.01),
+    ("edge_threshold", float("nan")), ("edge_threshold", float("inf")), ("edge_threshold", -10.0), ("edge_threshold", 0.0),
+    ("sigma", float("nan")), ("sigma", float("inf")), ("sigma", 0.0), ("sigma", -1.6), ("sigma", 40.0),
+    ("n_octave_layers", 0), ("n_octave_layers", 6), ("max_keypoints", 15)])
+def test_create_refuses_out_of_range_fields_before_touching_the_gpu(vo, oracle, field, value):
+    """Non-finite or negative thresholds, edge_threshold 0 and the refusals vo_create had before:
+    NULL before any HIP call, with the offending field named."""
+    import numpy as np
+    msg = _create_refused(vo, _sift_block(vo, **{field: value}))
+    assert f": {field} " in msg, msg
+    if field != "max_keypoints":                       # (the oracle's capacity is the caller's array)
+        rp = oracle.sift_params()
+        setattr(rp, field, value)
+        with pytest.raises(ValueError):
+            oracle.sift(np.zeros((32, 32), np.uint8), rp)
+
+
+def test_supported_blocks_pass_the_parameter_check(vo):
+    """The accepted side, as far as a machine without a GPU shows it: blocks next to each bound get
+    past the parameter check (any failure is the device's, not "unsupported sift params").  That
+    they detect what the oracle detects is tests/test_gpu_sift_params.py."""
+    import ctypes
+    import torch
+    lib = vo.load_library()
+    for kw in (dict(n_octave_layers=1, sigma=1.4), dict(n_octave_layers=2, sigma=3.4), dict(n_octave_layers=3, sigma=5.0),
+               dict(n_octave_layers=3, sigma=5.2), dict(n_octave_layers=5, upsample=0), dict(contrast_threshold=0.0), dict(edge_threshold=0.5)):
+        p = _sift_block(vo, **kw)
+        if torch.cuda.is_available():
+            vo.Context(64, 64, 1, sift=p).close()
+        else:
+            h = lib.vo_create(0, 64, 64, 1, None, ctypes.byref(p), None, None)
+            assert not h
+            assert "unsupported sift params" not in lib.vo_last_error(None).decode(), kw

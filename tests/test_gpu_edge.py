@@ -189,15 +189,18 @@ def test_padded_and_flipped_views(vo, oracle, syn):
 
 def test_create_refuses_sigma_beyond_the_orientation_bound(vo):
     """ADVICE r4: k_orient's u32 column sums hold windows up to a bound (sift_params_supported);
-    vo_create refuses a Sigma whose orientation windows could exceed it instead of wrapping a bin."""
-    for sigma in (float("nan"), 0.0, -1.6, 40.0):
+    vo_create refuses a Sigma whose orientation windows could exceed it instead of wrapping a bin.
+    The blur-radius cap binds earlier (5.3 at 3 layers: top-level radius 41 of at most 40), between
+    the accepted 4.0 / 5.2 and the orientation bound."""
+    for sigma in (float("nan"), 0.0, -1.6, 40.0, 5.3):
         p = vo.default_sift_params()
         p.sigma = sigma
         with pytest.raises(vo.VOError):
             vo.Context(64, 64, 1, sift=p)
-    p = vo.default_sift_params()
-    p.sigma = 4.0                                      # well inside the bound: accepted
-    vo.Context(64, 64, 1, sift=p).close()
+    for sigma in (4.0, 5.2):                           # inside both bounds (5.2: radius 40 exactly): accepted
+        p = vo.default_sift_params()
+        p.sigma = sigma
+        vo.Context(64, 64, 1, sift=p).close()
 
 
 def test_candidate_overflow_is_reported(vo, syn):

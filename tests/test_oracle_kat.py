@@ -89,6 +89,125 @@ def test_sift_finds_blob(oracle, cx, cy, s):
     assert d.shape == (len(k), 128) and d[j].max() > 0
 
 
+# ------------------------------------------------- scale space and detection away from the defaults
+# (n_octave_layers, sigma, upsample): 1, 2, 4 and 5 layers, sigma next to the blur-radius cap (3, 5.0: top
+# level radius 39 of 40; 1, 1.2: 34), both upsample settings
+NONDEFAULT = [(1, 1.2, 1), (2, 1.6, 0), (5, 1.6, 1), (3, 5.0, 0), (4, 2.0, 1)]
+
+
+def _split_pyramid(flat, rows, cols, L, upsample):
+    """oracle.pyramid's flat array -> [(G[0..L+2], D[0..L+1])] per octave, for any L / upsample."""
+    R, C = (2 * rows, 2 * cols) if upsample else (rows, cols)
+    n_oct = max(1, int(round(math.log2(min(R, C)) - 2)) + (1 if upsample else 0))
+    out, off = [], 0
+    for o in range(n_oct):
+        if o:
+            R, C = R // 2, C // 2
+        G = [flat[off + i * R * C: off + (i + 1) * R * C].reshape(R, C) for i in range(L + 3)]
+        off += (L + 3) * R * C
+        D = [flat[off + i * R * C: off + (i + 1) * R * C].reshape(R, C) for i in range(L + 2)]
+        off += (L + 2) * R * C
+        out.append((G, D))
+    assert off == flat.size, (off, flat.size)
+    return out
+
+
+def _reflect101(i, n):
+    """BORDER_REFLECT_101 index, iterated (a radius may exceed the plane: np.pad's 'reflect' folds once)."""
+    i = np.asarray(i).copy()
+    if n == 1:
+        return np.zeros_like(i)
+    while ((i < 0) | (i >= n)).any():
+        i = np.where(i < 0, -i, i)
+        i = np.where(i >= n, 2 * n - 2 - i, i)
+    return i
+
+
+def _blur_f64(img, k):
+    """float64 separable convolution with the float kernel k[0..r] (centre first), reflect-101."""
+    r = len(k) - 1
+    kk = np.concatenate([k[::-1], k[1:]]).astype(np.float64)
+    a = img.astype(np.float64)
+    R, C = a.shape
+    h = np.stack([np.convolve(row, kk, mode="valid") for row in a[:, _reflect101(np.arange(-r, C + r), C)]])
+    return np.stack([np.convolve(col, kk, mode="valid") for col in h[_reflect101(np.arange(-r, R + r), R)].T]).T
+
+
+@pytest.mark.parametrize("L,sigma,upsample", NONDEFAULT)
+def test_pyramid_structure_and_levels_at_other_parameters(oracle, L, sigma, upsample):
+    """test_pyramid_structure generalised to L and upsample, plus every level G_i against a float64
+    convolution of the oracle's own G_{i-1} with oracle.gauss_kernel(s_i) (tolerance: the 2e-4 of
+    test_blur_matches_float64_convolution; a float accumulation of <= 81 taps of values <= 255)."""
+    rng = np.random.default_rng(3)
+    rows, cols = 40, 64
+    img = rng.integers(0, 256, (rows, cols)).astype(np.uint8)
+    p = oracle.SiftParams(L, sigma, 0.04, 10.0, upsample, 16384)
+    octs = _split_pyramid(oracle.pyramid(img, p), rows, cols, L, upsample)   # (asserts the total length)
+    base = min(rows, cols) * (2 if upsample else 1)
+    assert len(octs) == oracle.lib().oracle_num_octaves(rows, cols, upsample) \
+        == int(round(math.log2(base) - 2)) + (1 if upsample else 0)
+    assert octs[0][0][0].shape == ((2 * rows, 2 * cols) if upsample else (rows, cols))
+    sig = [sigma * 2.0 ** ((i - 1) / L) * math.sqrt(2.0 ** (2.0 / L) - 1.0) for i in range(1, L + 3)]
+    worst = 0.0
+    for o, (G, D) in enumerate(octs):
+        if o:
+            pr = octs[o - 1][0][L]
+            assert G[0].shape == (pr.shape[0] // 2, pr.shape[1] // 2)
+            assert np.array_equal(G[0], pr[: 2 * G[0].shape[0]: 2, : 2 * G[0].shape[1]: 2])
+        for i in range(L + 2):
+            assert np.array_equal(D[i], G[i + 1] - G[i])
+        for i in range(1, L + 3):
+            k = oracle.gauss_kernel(sig[i - 1])
+            assert 1 <= len(k) - 1 <= 40
+            err = np.abs(G[i] - _blur_f64(G[i - 1], k)).max()
+            worst = max(worst, err)
+            assert err < 2e-4, (o, i, err)
+    print(f"L={L} sigma={sigma} upsample={upsample}: worst level error {worst:.2e}")
+
+
+def test_gauss_kernel_stops_at_the_radius_cap(oracle):
+    """vo_gauss_kernel builds kernels up to radius 40 (VO_SIFT_MAX_RADIUS, the size of its own
+    scratch array) whatever capacity the caller offers; beyond it, and for sigma that is not finite
+    and positive, it returns -1 and oracle.gauss_kernel raises."""
+    k = oracle.gauss_kernel(10.0)                       # ksize round(81) | 1 = 81
+    assert len(k) == 41 and abs(2 * k[1:].sum() + k[0] - 1) < 1e-6 and np.all(np.diff(k) < 0)
+    assert oracle.lib().oracle_gauss_radius(10.0) == 40 and oracle.lib().oracle_gauss_radius(10.2) == -1
+    for sigma in (10.2, 15.0, 1e9, float("inf"), float("nan"), 0.0, -1.0):
+        with pytest.raises(ValueError):
+            oracle.gauss_kernel(sigma)
+
+
+@pytest.fixture(scope="module")
+def blob_defaults(oracle):
+    """The default-parameter detection of the two blobs of test_sift_finds_blob (computed once)."""
+    out = {}
+    for cx, cy, s in [(40.0, 30.0, 3.0), (70.5, 41.25, 5.0)]:
+        k, _ = oracle.sift(_blob_image(80, 120, cx, cy, s))
+        j = np.argmin(np.hypot(k["x"] - (cx + 1), k["y"] - (cy + 1)))
+        out[(cx, cy, s)] = float(k["scale"][j])
+    return out
+
+
+@pytest.mark.parametrize("cx,cy,s", [(40.0, 30.0, 3.0), (70.5, 41.25, 5.0)])
+@pytest.mark.parametrize("L,sigma,upsample", [(2, 1.6, 0), (4, 1.6, 1), (5, 1.6, 0), (3, 2.5, 1)])
+def test_sift_finds_blob_at_other_parameters(oracle, blob_defaults, L, sigma, upsample, cx, cy, s):
+    """The blob KAT at other layer counts, sigma and without the upsample: the same blob is found
+    at the same place, at the default detection's scale to within one layer step 2^(1/L), in a
+    layer 1..L, and in a non-negative octave when the image is not upsampled."""
+    img = _blob_image(80, 120, cx, cy, s)
+    k, d = oracle.sift(img, oracle.SiftParams(L, sigma, 0.04, 10.0, upsample, 16384))
+    assert len(k) >= 1
+    dist = np.hypot(k["x"] - (cx + 1), k["y"] - (cy + 1))
+    j = np.argmin(dist)
+    ratio = k["scale"][j] / blob_defaults[(cx, cy, s)]
+    print(f"L={L} sigma={sigma} upsample={upsample} blob {s}: {dist[j]:.3f} px, scale ratio {ratio:.3f}")
+    assert dist[j] < 0.3
+    assert 2.0 ** (-1.0 / L) < ratio < 2.0 ** (1.0 / L)
+    assert 1 <= k["layer"][j] <= L
+    assert k["octave"].min() >= (-1 if upsample else 0)
+    assert d.shape == (len(k), 128) and d[j].max() > 0
+
+
 def test_sift_rotation_90_invariance(oracle, syn):
     L, _ = syn.stereo_pair(syn.SEED_BASE + 3, rows=120, cols=160)
     rot = np.ascontiguousarray(np.rot90(L))        # 90 deg counter-clockwise
