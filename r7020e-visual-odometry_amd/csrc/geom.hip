@@ -1,8 +1,9 @@
 // geom.hip — tracking + geometry stages of the per-frame path (see vo_geom.h).
 //
 //   find_remaining_points (VO.m:280-334)  four match jobs per frame whose row
-//       sets are index lists; k_compose turns each step's (i, j) pairs into the
-//       next step's lists, so no descriptor is ever copied.
+//       sets are index lists; each step's finishing kernel (k_match_finish,
+//       match.hip) composes its (i, j) pairs into the next step's lists, so no
+//       descriptor is ever copied.
 //   triangulate (VO.m:113-116)            k_gather_tri: one lane per tracked
 //       point, linear DLT + one-sided Jacobi SVD in f64 (oracle dlt_point).
 //   estworldpose (VO.m:123-127)           k_msac: one block per frame walks the
@@ -100,50 +101,6 @@ void geom_fill_track_jobs(const GeomBuffers& g, MatchJob* jobs, int M, int first
         J3.d1 = D(cl); J3.m1 = Mt(cl); J3.idx1 = glist(g, f, TL_CL2); J3.n1 = g.list_n + 4 * f + 2;
         J3.d2 = D(pl); J3.m2 = Mt(pl); J3.idx2 = glist(g, f, TL_OL2); J3.n2 = g.list_n + 4 * f + 1;
     }
-}
-
-// ---------------------------------------------------------------------------
-// index composition after each tracking step (VO.m:287-290,297-300,305-308,
-// 314-317,326-333).  grid (blocks, B)
-// ---------------------------------------------------------------------------
-struct ComposeArgs {
-    int* lists; int* list_n; const int* step_i; const int* step_j; const int* step_n;
-    const int* pair_i; const int* pair_j; const int* pair_n;
-    int M, kp_cap, step;
-};
-
-__global__ void k_compose(ComposeArgs a)
-{
-    const int f = blockIdx.y, K = a.kp_cap, M = a.M;
-    const int s = a.step;
-    int n = a.step_n[s * M + f];
-    if (n > K) n = K;
-    if (n < 0) n = 0;
-    const int* si = a.step_i + ((size_t)s * M + f) * K;
-    const int* sj = a.step_j + ((size_t)s * M + f) * K;
-    int* L = a.lists + (size_t)f * TL_COUNT * K;
-    const int pp = f ? f - 1 : M;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
-        const int i = si[k], j = sj[k];
-        if (s == 0) {
-            L[TL_OL1 * K + k] = a.pair_i[(size_t)pp * K + j];
-            L[TL_OR1 * K + k] = a.pair_j[(size_t)pp * K + j];
-            L[TL_CL * K + k] = i;
-        } else if (s == 1) {
-            L[TL_OL2 * K + k] = L[TL_OL1 * K + j];
-            L[TL_OR2 * K + k] = L[TL_OR1 * K + j];
-            L[TL_CR * K + k] = i;
-        } else if (s == 2) {
-            L[TL_CL2 * K + k] = L[TL_CL * K + i];
-            L[TL_CR2 * K + k] = L[TL_CR * K + j];
-        } else {
-            L[TL_OLF * K + k] = L[TL_OL2 * K + j];
-            L[TL_ORF * K + k] = L[TL_OR2 * K + j];
-            L[TL_CLF * K + k] = L[TL_CL2 * K + i];
-            L[TL_CRF * K + k] = L[TL_CR2 * K + i];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.list_n[4 * f + s] = n;
 }
 
 // ---------------------------------------------------------------------------
@@ -690,20 +647,6 @@ __device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status
 #ifndef VO_MSAC_T
 #define VO_MSAC_T 1024            // 16 waves: a chunk's 64 slots scored 4 per wave (one block per frame)
 #endif
-#ifndef VO_MSAC_SPLITGEN
-#define VO_MSAC_SPLITGEN 0        // 1: the first chunk's hypotheses come from k_msac_gen (64-lane blocks)
-#endif
-
-#if VO_MSAC_SPLITGEN
-// first chunk of every frame, one lane per slot: a 64-thread block has the whole register file
-// for the P3P root finder that spills at k_msac's 1024-thread bound
-__global__ __launch_bounds__(64) void k_msac_gen(MsacArgs a)
-{
-    const int f = blockIdx.x, s = threadIdx.x;
-    const int limit = a.max_trials < a.n_hyp ? a.max_trials : a.n_hyp;
-    if (s < VO_MSAC_FIRST && s < limit) msac_hyp_slot(a, f, s, msac_n(a, f));
-}
-#endif
 
 __global__ __launch_bounds__(VO_MSAC_T) void k_msac(MsacArgs a)
 {
@@ -719,7 +662,7 @@ __global__ __launch_bounds__(VO_MSAC_T) void k_msac(MsacArgs a)
     __syncthreads();
     for (int c0 = 0, c1 = min(VO_MSAC_FIRST, limit); !s_done && c0 < limit;
          c0 = c1, c1 = min(c1 + VO_MSAC_CHUNK, limit)) {
-        if (tid < c1 - c0 && (!VO_MSAC_SPLITGEN || c0 > 0)) msac_hyp_slot(a, f, c0 + tid, n);
+        if (tid < c1 - c0) msac_hyp_slot(a, f, c0 + tid, n);
         __syncthreads();                                    // the chunk's slots are written
         for (int s = c0 + wv; s < c1; s += VO_MSAC_T / 64)
             if (a.hyp[(size_t)f * a.n_hyp + s].valid) msac_score_slot(a, f, s, n, lane);
@@ -937,9 +880,6 @@ static void msac_enqueue(const MsacArgs& a, int B, hipStream_t s)
         return;
     }
 #endif
-#if VO_MSAC_SPLITGEN
-    VO_LAUNCH(k_msac_gen, dim3(B), dim3(64), 0, s, a);
-#endif
     VO_LAUNCH(k_msac, dim3(B), dim3(VO_MSAC_T), 0, s, a);
 }
 
@@ -947,20 +887,9 @@ void track_enqueue(GeomBuffers& g, const MatchBuffers& mb, const MatchJob* d_tra
                    const vo_match_params& mp, hipStream_t s)
 {
     const int B = a.B, M = a.max_frames, K = a.kp_cap;
-    if (VO_MATCH_FINISH) {                           // the composition inside match_launch's finishing kernel (csrc/match.hip)
-        for (int step = 0; step < 4; ++step) {
-            MatchCompose cp{g.lists, g.list_n, a.pair_i, a.pair_j, M, K, step, 0};
-            match_launch(mb, d_track_jobs + step * M, B, mp, s, &cp);
-        }
-        return;
-    }
-    ComposeArgs ca;
-    ca.lists = g.lists; ca.list_n = g.list_n; ca.step_i = g.step_i; ca.step_j = g.step_j; ca.step_n = g.step_n;
-    ca.pair_i = a.pair_i; ca.pair_j = a.pair_j; ca.pair_n = a.pair_n; ca.M = M; ca.kp_cap = K;
-    for (int step = 0; step < 4; ++step) {
-        match_launch(mb, d_track_jobs + step * M, B, mp, s);
-        ca.step = step;
-        VO_LAUNCH(k_compose, dim3(16, B), dim3(256), 0, s, ca);
+    for (int step = 0; step < 4; ++step) {           // the composition inside match_launch's finishing kernel (csrc/match.hip)
+        MatchCompose cp{g.lists, g.list_n, a.pair_i, a.pair_j, M, K, step, 0};
+        match_launch(mb, d_track_jobs + step * M, B, mp, s, &cp);
     }
 }
 

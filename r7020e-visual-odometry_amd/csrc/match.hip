@@ -12,7 +12,7 @@
 // row over the F2 columns it holds, the two half-waves that share a row merge with a
 // (value, index) total order, and the F2 chunks merge in k_match_finish (one workgroup
 // per job), which also applies MatchThreshold / MaxRatio and writes the pairs in
-// ascending F1 order (k_match_merge + k_match_compact with VO_MATCH_FINISH=0).
+// ascending F1 order.
 #include "vo_internal.h"
 #include "vo_geom.h"
 
@@ -99,12 +99,6 @@ __device__ __forceinline__ v4i load_frag(const uint8_t* row, int off)
 #define VO_MP_BLOCKS 5            // workgroups per CU the register budget of k_match_partial<1> is sized for (92 VGPRs)
 #endif
 #define MP_NBUF 2
-#ifndef VO_MP_BSEARCH
-// 1: binary search of a task's job in the task table (8 dependent LDS reads); 0: the linear scan
-// (up to 255).  k_match_partial 0.623 against 0.667 / 0.679 ms isolated per 256-frame step
-// (profiles/r06_r_ab_match_task.txt)
-#define VO_MP_BSEARCH 1
-#endif
 // NB: 32-row F1 sub-blocks per wave (MP_ROWS * NB rows per workgroup); NB = 2 runs two
 // independent MFMA chains per tile on the same F2 fragments (half the LDS reads per MFMA)
 // SWAP: the job's row side is the spec's F2 and its column side the spec's F1 (the backward pass
@@ -150,13 +144,12 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
     // XCD's L2 -- measured slower: 0.825 against 0.667 ms isolated, profiles/r06_r_ab_match_task.txt)
     for (int t = blockIdx.x; t < total; t += gridDim.x) {       // workgroup-uniform
         int jb = 0;
-#if VO_MP_BSEARCH
-        // last job whose first task <= t (tstart is nondecreasing; empty jobs repeat a value)
+        // last job whose first task <= t (tstart is nondecreasing; empty jobs repeat a value): a
+        // binary search of the task table, 8 dependent LDS reads where a linear scan took up to 255
+        // (k_match_partial 0.623 against 0.667 / 0.679 ms isolated per 256-frame step,
+        // profiles/r06_r_ab_match_task.txt)
         for (int step = VO_MP_MAX_JOBS / 2; step >= 1; step >>= 1)
             if (jb + step < n_jobs && tstart[jb + step] <= t) jb += step;
-#else
-        while (jb + 1 < n_jobs && tstart[jb + 1] <= t) ++jb;
-#endif
         const int n1 = jn1[jb], nch = jnch[jb];
         const int n2 = job_rows(jobs[jb].n2, row_cap);
         const long rel = t - tstart[jb];
@@ -298,86 +291,14 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
     }
 }
 
-// One thread per (job, F1 row): merge the F2 chunks, back to SSD, MatchThreshold and
-// MaxRatio.  res = accepted F2 index or -1.
-__global__ __launch_bounds__(256) void k_match_merge(const MatchJob* __restrict__ jobs, const MatchTop2* __restrict__ partial,
-                                                     int* __restrict__ res, int row_cap, int n_chunks_cap, float T, float max_ratio)
-{
-    const int jb = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
-    const int n1 = job_rows(jobs[jb].n1, row_cap), n2 = job_rows(jobs[jb].n2, row_cap);
-    if (r >= n1) return;
-    const int nch = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
-    const MatchTop2* P = partial + (size_t)jb * n_chunks_cap * row_cap + r;
-    float b = -INFINITY, s = -INFINITY;
-    int i = -1;
-    for (int c = 0; c < nch; ++c) {
-        const MatchTop2 m = P[(size_t)c * row_cap];
-        top2c_merge(b, i, s, m.best, m.idx, m.second);
-    }
-    const float bs = 2.0f - 2.0f * b, ss = 2.0f - 2.0f * s;      // SSD of best / second best
-    const bool ok = i >= 0 && bs <= T && (bs / ss) <= max_ratio;
-    res[(size_t)jb * row_cap + r] = ok ? i : -1;
-}
-
-__device__ __forceinline__ uint32_t block_exscan_1024_m(uint32_t v, uint32_t* sh, uint32_t* total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        uint32_t s = lane < 16 ? sh[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            uint32_t y = __shfl_up(s, o);
-            if (lane >= o) s += y;
-        }
-        if (lane < 16) sh[16 + lane] = s;
-    }
-    __syncthreads();
-    uint32_t before = wid ? sh[16 + wid - 1] : 0;
-    *total = sh[16 + 15];
-    __syncthreads();
-    return before + x - v;
-}
-
-// One block (1024 threads) per job: compact the accepted rows in ascending F1 order.
-__global__ __launch_bounds__(1024) void k_match_compact(const MatchJob* __restrict__ jobs, const int* __restrict__ res, int row_cap)
-{
-    __shared__ uint32_t sh[32];
-    const int jb = blockIdx.x, tid = threadIdx.x;
-    const MatchJob J = jobs[jb];
-    const int n1 = job_rows(J.n1, row_cap);
-    const int chunk = (n1 + 1023) / 1024;
-    const int a = tid * chunk, e = min(a + chunk, n1);
-    const int* R = res + (size_t)jb * row_cap;
-    uint32_t cnt = 0;
-    for (int r = a; r < e; ++r) cnt += R[r] >= 0;
-    uint32_t total;
-    uint32_t base = block_exscan_1024_m(cnt, sh, &total);
-    for (int r = a; r < e; ++r) {
-        const int i = R[r];
-        if (i >= 0) {
-            if (base < (uint32_t)J.cap) { gst(J.out_i + base, r); gst(J.out_j + base, i); }
-            base++;
-        }
-    }
-    if (tid == 0) gst(J.out_n, (int)(total < (uint32_t)J.cap ? total : (uint32_t)J.cap));
-}
-
-// One 256-thread workgroup per job: k_match_merge + k_match_compact (+ k_compose) in one
-// launch.  Rows go in tiles of 256 in ascending F1 order (coalesced partial reads): thread t
-// merges row 256 k + t over the F2 chunks and applies MatchThreshold / MaxRatio; the tile's
-// accepted rows are placed by a block prefix sum after the running count, so the pairs come
-// out in ascending F1 order exactly as k_match_compact writes them.  With `compose` (a
-// tracking step of find_remaining_points), the workgroup then applies that step's index
-// composition to its frame's lists (k_compose, VO.m:287-333) -- so a tracking step is two
-// launches (partial, finish) instead of four.
+// One 256-thread workgroup per job: the merge of the F2 chunks, the compaction of the accepted
+// rows (and a tracking step's index composition) in one launch.  Rows go in tiles of 256 in
+// ascending F1 order (coalesced partial reads): thread t merges row 256 k + t over the F2 chunks,
+// back to SSD, and applies MatchThreshold / MaxRatio; the tile's accepted rows are placed by a
+// block prefix sum after the running count, so the pairs come out in ascending F1 order.  With
+// `compose` (a tracking step of find_remaining_points), the workgroup then applies that step's
+// index composition to its frame's lists (VO.m:287-333) -- so a tracking step is two launches
+// (partial, finish); as separate merge, compact and compose kernels it was four.
 __global__ __launch_bounds__(256) void k_match_finish(const MatchJob* __restrict__ jobs, const MatchTop2* __restrict__ partial,
                                                       int row_cap, int n_chunks_cap, float T, float max_ratio,
                                                       MatchCompose cp, int with_compose)
@@ -416,7 +337,7 @@ __global__ __launch_bounds__(256) void k_match_finish(const MatchJob* __restrict
     if (tid == 0) gst(J.out_n, n_out);
     if (!with_compose) return;
     __syncthreads();                                              // the pairs are visible to the block
-    // k_compose of tracking step cp.step for frame f = jb
+    // the index composition of tracking step cp.step for frame f = jb
     const int f = cp.f0 + jb, K = cp.kp_cap, M = cp.M, st = cp.step;
     int* L = cp.lists + (size_t)f * TL_COUNT * K;
     const int pp = f ? f - 1 : M;
@@ -522,7 +443,6 @@ hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap)
     b.n_chunks = (row_cap + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
     hipError_t e = hipMalloc((void**)&b.jobs, sizeof(MatchJob) * max_jobs);
     if (e != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&b.res, sizeof(int) * (size_t)max_jobs * row_cap)) != hipSuccess) return e;
     return hipMalloc((void**)&b.partial, sizeof(MatchTop2) * (size_t)max_jobs * b.n_chunks * row_cap);
 }
 
@@ -530,7 +450,6 @@ void match_free(MatchBuffers& b)
 {
     hipFree(b.jobs);
     hipFree(b.partial);
-    hipFree(b.res);
     b = MatchBuffers();
 }
 
@@ -564,7 +483,6 @@ MatchBuffers match_view(const MatchBuffers& b, int k0)
     MatchBuffers v = b;
     v.jobs = b.jobs ? b.jobs + k0 : nullptr;
     v.partial = b.partial + (size_t)k0 * b.n_chunks * b.row_cap;
-    v.res = b.res + (size_t)k0 * b.row_cap;
     v.max_jobs = b.max_jobs - k0;
     return v;
 }
@@ -596,16 +514,10 @@ void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, con
     // -1 %, the 1080p block 0.123 against 0.128 of i8 peak, profiles/r06_y_ab_match_nb2_chunk.txt)
     VO_LAUNCH_NAMED("k_match_partial", k_match_partial<1>, dim3(compose ? VO_TRACK_GRID : VO_STEREO_GRID), dim3(256), 0, s,
                     d_jobs, n_jobs, b.partial, b.row_cap, b.n_chunks);
-    if (VO_MATCH_FINISH) {
-        MatchCompose cp{};
-        if (compose) cp = *compose;
-        VO_LAUNCH(k_match_finish, dim3(n_jobs), dim3(256), 0, s, d_jobs, (const MatchTop2*)b.partial, b.row_cap, b.n_chunks,
-                  p.match_threshold * 0.04f, p.max_ratio, cp, compose ? 1 : 0);
-        return;
-    }
-    VO_LAUNCH(k_match_merge, dim3((b.row_cap + 255) / 256, n_jobs), dim3(256), 0, s, d_jobs, (const MatchTop2*)b.partial,
-              b.res, b.row_cap, b.n_chunks, p.match_threshold * 0.04f, p.max_ratio);
-    VO_LAUNCH(k_match_compact, dim3(n_jobs), dim3(1024), 0, s, d_jobs, (const int*)b.res, b.row_cap);
+    MatchCompose cp{};
+    if (compose) cp = *compose;
+    VO_LAUNCH(k_match_finish, dim3(n_jobs), dim3(256), 0, s, d_jobs, (const MatchTop2*)b.partial, b.row_cap, b.n_chunks,
+              p.match_threshold * 0.04f, p.max_ratio, cp, compose ? 1 : 0);
 }
 
 void match_launch(const MatchBuffers& b, const MatchJob* d_jobs, int n_jobs, const vo_match_params& p, hipStream_t s)

@@ -1,7 +1,7 @@
 // octave.hip — one octave's Gaussian levels 1..5, its extremum test and the next octave's base
 // in a single pass (k_octave): detectSIFTFeatures' scale space + DoG extrema, VO.m:79-80.
 //
-// The per-level path (sift.hip: k_blur_stream per level, k_ext_stream, k_down) moves every
+// The per-level path (sift.hip: k_blur_stream per level, k_ext_inner, k_down) moves every
 // octave pixel through HBM ~16 times: each level blur reads G_{i-1} and writes G_i (8 B per
 // pixel and level), the extremum test re-reads all six levels (24 B), k_down re-reads G_3.
 // Here one workgroup streams a vertical strip of the octave top to bottom and keeps the
@@ -15,7 +15,7 @@
 //     base (G_3 decimated by 2).
 //   * 1 extremum wave: per row, D_0..D_4 rows from the DoG histories, horizontal 3-max/min
 //     (4 columns per lane, outer neighbours by DPP), a 3-row register window, the 26-neighbour
-//     test of layers 1..3, words OR-ed into the mask in k_ext_stream's (even, odd) layout.
+//     test of layers 1..3, words OR-ed into the mask in k_ext_inner's (even, odd) layout (k_seg_emit reads it).
 // Waves run decoupled, synchronised by per-history counters in LDS (rows emitted, rows
 // released): a level emits row y only into a free slot, a consumer reads row q only once it
 // has been emitted.  HBM traffic per octave pixel: G_0 read ~1.5x (window overlap) + G_1..G_5
@@ -360,7 +360,8 @@ __device__ __forceinline__ void of_level(const float* __restrict__ g0, float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// An extremum wave: k_ext_stream's test of one layer on the DoG histories, 4 columns per lane.
+// An extremum wave: the full 26-neighbour test of one layer (what k_ext_inner and k_refine's
+// outer-level check compute together) on the DoG histories, 4 columns per lane.
 // Layer LY reads D_{LY-1}, D_LY, D_{LY+1}; it loads row rho once G_{LY+2} row rho is emitted and
 // releases it at once (its horizontal 3-max/min and centre stay in a 3-row register window).
 // ---------------------------------------------------------------------------------------------

@@ -1,18 +1,24 @@
 // sift.hip — detectSIFTFeatures + extractFeatures (VO.m:79-84) on gfx950.
 //
 // Pipeline per batch of n_img images:
-//   k_blur_fused          one launch per scale level: row + column Gaussian
-//                         passes through one LDS tile, writes G_i and the DoG
-//                         D_{i-1} = G_i - G_{i-1} (octave 0: x2 upsample fused)
-//   k_down                next octave base = G[o-1][L](2y, 2x)
-//   k_ext_tile            26-neighbour extremum test on LDS tiles of all DoG
-//                         levels, ballot -> 64-bit mask per 64 columns
+//   k_blur_stream         one launch per scale level: a wave streams a band of rows, row
+//                         pass across lanes, column pass in a register ring, writes G_i
+//                         (octave 0's base: x2 upsample of the u8 image fused); DoG planes
+//                         are never stored, D_i = G_{i+1} - G_i is formed where it is read
+//   k_base_src/k_blur_fused  the generic path (untabled radii, planes shorter than a band):
+//                         row + column passes through one LDS tile
+//   k_down                next octave base = G[o-1][L](2y, 2x), where the level-L blur did
+//                         not store it
+//   k_small_pyr           the LDS-sized octaves, every level, in one launch
+//   k_ext_inner           26-neighbour extremum test against the streamed levels G_1..G_{L+1},
+//                         ballot -> 64-bit mask words per 128-column strip
 //   k_seg_count/scan/emit deterministic compaction in (octave, layer, row,
 //                         col) scan order (prefix sums, no atomic append)
-//   k_refine_orient       one wave per candidate: Newton refinement (wave-
-//                         uniform), orientation histogram (lanes stride the
-//                         window, 2^-20 fixed-point LDS atomics), peaks by ballot
-//   k_scan_cands/k_expand keypoint list in candidate order, then peak order
+//   k_refine              one lane per candidate: the outer-level part of the extremum test,
+//                         Newton refinement, contrast / edge tests; lists the accepted ones
+//   k_orient              one wave per accepted candidate: orientation histogram (lanes stride
+//                         the window, fixed-point LDS atomics), peaks by ballot
+//   k_scan_cands/k_expand keypoint offsets in candidate order, then the keypoints in peak order
 //   k_sel_keys/k_sel_rank only with vo_set_strongest(n > 0), between the two: the candidates'
 //                         slots in selectStrongest's order (response descending, stable)
 //   k_desc                one wave per keypoint: 4x4x8 trilinear histogram
@@ -71,7 +77,7 @@ void build_pyramid_geometry(Pyramid& py, int rows, int cols, int n_img, const vo
         if (ir < 0) ir = 0;
         if (ic < 0) ic = 0;
         // words of 64 absolute columns covering the interior [BORDER, cols - BORDER)
-        // (an even count: the extremum test writes a strip's two words as a pair, see k_ext_stream)
+        // (an even count: the extremum test writes a strip's two words as a pair, see k_ext_inner)
         py.wrow[o] = ic > 0 ? ((py.oct[o].cols - VO_SIFT_BORDER - 1) / 64 + 2) / 2 * 2 : 0;
         for (int l = 0; l < L; ++l) { py.wbase[b++] = w; w += ir * py.wrow[o]; }
         py.ebase[o] = t;
@@ -1038,11 +1044,11 @@ __device__ __forceinline__ void decode_word(const Pyramid* __restrict__ py, int 
 }
 
 // ---------------------------------------------------------------------------
-// 26-neighbour extremum test, streaming.  One wave per (image, octave, strip
-// of 128 columns, band of VO_EXT_BAND interior rows); lane l owns the adjacent
+// 26-neighbour extremum test, streaming (k_ext_inner).  One wave per (image, octave,
+// strip of 128 columns, band of VO_EXT_BAND interior rows); lane l owns the adjacent
 // columns xs+2l and xs+2l+1.  The wave walks the band's rows (+1 above and below):
-// per row it loads the L+3 Gaussian levels (one coalesced 8-B load + one halo
-// column: xs-1 in lane 0, xs+128 in lane 63), forms D_l = G_{l+1} - G_l (never
+// per row it loads the Gaussian levels G_1 .. G_{L+1} (one coalesced 8-B load + one
+// halo column: xs-1 in lane 0, xs+128 in lane 63), forms D_l = G_{l+1} - G_l (never
 // stored), reduces each level to its horizontal 3-max/3-min -- the outer neighbours
 // xs+2l-1 and xs+2l+2 arrive by one DPP wave shift each, lanes 0 / 63 keeping their
 // halo column -- and keeps the last 3 rows of those in a register window (rows
@@ -1064,13 +1070,22 @@ __device__ __forceinline__ float vo_wave_shl1_or(float old, float x)   // lane i
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), 0x130, 0xf, 0xf, false));
 }
 
+// The inner part of the extremum test: of the L + 3 Gaussian levels the wave streams
+// only G_1 .. G_{L+1} -- D_1 .. D_L, the centres of every layer and every neighbour level
+// except D_0 (layer 1's lower neighbour, G_1 - G_0) and D_{L+1} (layer L's upper one).  A bit is
+// set when its centre passes |val| > thr and the extremum test against those streamed levels;
+// k_refine completes the test for layers 1 and L (val >= / <= the 9 values of D_0 / D_{L+1})
+// before anything else and rejects the centres that fail it.  val >= max of the 27 <=> val >=
+// the max of each part, so the keypoints are the full test's; 2 of the L + 3 planes leave the
+// streamed bytes (4 (L + 1) B per octave px).  Measured: the extremum test 3.28 -> 2.34 ms, k_refine
+// 0.39 -> 0.77 ms isolated (the partial candidates), +3.5-3.9 % stereo frames/s (DESIGN.md 9e).
 template <int L>
-__global__ __launch_bounds__(64) void k_ext_stream(const Pyramid* __restrict__ py, const float* __restrict__ arena,
+__global__ __launch_bounds__(64) void k_ext_inner(const Pyramid* __restrict__ py, const float* __restrict__ arena,
                                                    unsigned long long* __restrict__ mask, float thr, int n_img, int u_first,
                                                    int u_last)
 {
     vo_ss_prio();
-    constexpr int NG = L + 3, ND = L + 2, W = 3;      // Gaussian levels, DoG levels, row window
+    constexpr int NG = L + 1, ND = L, W = 3;          // streamed levels G_1..G_{L+1}, DoG D_1..D_L
     const int lane = threadIdx.x;
     const int u_all = xcd_remap(blockIdx.x, gridDim.x);
     // units [u_first, u_last) of every image (a range of octaves; those below a fused prefix
@@ -1095,14 +1110,12 @@ __global__ __launch_bounds__(64) void k_ext_stream(const Pyramid* __restrict__ p
     const float* base = arena + img * py->istride;
     size_t goff[NG];
 #pragma unroll
-    for (int lv = 0; lv < NG; ++lv) goff[lv] = g.g_off[lv];
+    for (int lv = 0; lv < NG; ++lv) goff[lv] = g.g_off[lv + 1];
     const int wr = py->wrow[o];
     unsigned long long* mrow = mask + (size_t)img * py->n_words;
-#if VO_EXT_BSTORE
     // mask words by buffer stores issued by every lane every row: lanes other than 0/1 (and rows
     // past the band) get an out-of-range offset and the hardware drops them -- no store branch
     const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(mrow, 0, py->n_words * 8, 0x00020000);
-#endif
     int wb[L];                                       // mask word base per layer, hoisted: the mask
 #pragma unroll                                       // stores could alias *py for the compiler
     for (int l = 0; l < L; ++l) wb[l] = py->wbase[o * L + l];
@@ -1115,7 +1128,7 @@ __global__ __launch_bounds__(64) void k_ext_stream(const Pyramid* __restrict__ p
     f2_t hmx[W][ND], hmn[W][ND];                     // horizontal 3-max / 3-min per row slot
     f2_t dc[W][L];                                   // D of layers 1..L per row slot (centres)
 
-#define VO_ET_LOAD(T, SL)                                                                          \
+#define VO_ES_LOAD(T, SL)                                                                          \
     do {                                                                                           \
         const int y_ = min(r0 - 1 + (T), rows - 1);                                                \
         const float* rp_ = base + (size_t)y_ * pitch;                                              \
@@ -1137,7 +1150,7 @@ __global__ __launch_bounds__(64) void k_ext_stream(const Pyramid* __restrict__ p
         }
         // refill the slot with row t+3 -- only rows the band uses (r0-1 .. r0+nrow): the last
         // steps' prefetches were 3 wasted rows per 30-row band (~9 % of the kernel's fetches)
-        if (t + W <= nrow + 1) VO_ET_LOAD(t + W, SL);
+        if (t + W <= nrow + 1) VO_ES_LOAD(t + W, SL);
 #pragma unroll
         for (int lv = 0; lv < ND; ++lv) {
             // outer neighbours: xa-1 = lane l-1's xb (lane 0: its halo xs-1), xb+1 = lane
@@ -1147,142 +1160,9 @@ __global__ __launch_bounds__(64) void k_ext_stream(const Pyramid* __restrict__ p
             hmn[SL][lv] = f2_t{fminf(fminf(la, d[lv].x), d[lv].y), fminf(fminf(d[lv].x, d[lv].y), rb)};
         }
 #pragma unroll
-        for (int l = 0; l < L; ++l) dc[SL][l] = d[l + 1];
-        if constexpr (decltype(test_c)::value) {
-            constexpr int A = (SL + 1) % W, M = (SL + 2) % W;   // rows t-2, t-1 (tested)
-            const int r = r0 + t - 2;
-            f2_t mx3[ND], mn3[ND];
-#pragma unroll
-            for (int lv = 0; lv < ND; ++lv) {
-                mx3[lv] = f2_t{fmaxf(fmaxf(hmx[A][lv].x, hmx[M][lv].x), hmx[SL][lv].x),
-                               fmaxf(fmaxf(hmx[A][lv].y, hmx[M][lv].y), hmx[SL][lv].y)};
-                mn3[lv] = f2_t{fminf(fminf(hmn[A][lv].x, hmn[M][lv].x), hmn[SL][lv].x),
-                               fminf(fminf(hmn[A][lv].y, hmn[M][lv].y), hmn[SL][lv].y)};
-            }
-#pragma unroll
-            for (int layer = 1; layer <= L; ++layer) {
-                bool e[2];
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const float val = c ? dc[M][layer - 1].y : dc[M][layer - 1].x;
-                    const float bmx = fmaxf(fmaxf(c ? mx3[layer - 1].y : mx3[layer - 1].x, c ? mx3[layer].y : mx3[layer].x),
-                                            c ? mx3[layer + 1].y : mx3[layer + 1].x);
-                    const float bmn = fminf(fminf(c ? mn3[layer - 1].y : mn3[layer - 1].x, c ? mn3[layer].y : mn3[layer].x),
-                                            c ? mn3[layer + 1].y : mn3[layer + 1].x);
-                    // |val| > thr && (val > 0 ? val >= bmx : val <= bmn), as lane-mask compares
-                    e[c] = ((val > thr) & (val >= bmx)) | ((val < -thr) & (val <= bmn));
-                }
-                const uint64_t w0 = __ballot(e[0] & in0), w1 = __ballot(e[1] & in1);
-                const int k = 2 * strip + lane;               // wr is even: both words exist
-#if VO_EXT_BSTORE
-                const uint32_t mo = (lane < 2 && t - 2 < nrow) ? (uint32_t)(wb[layer - 1] + (r - VO_SIFT_BORDER) * wr + k) * 8u
-                                                               : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(vo_i2, (uint64_t)(lane ? w1 : w0)), rs_m, mo, 0, 0);
-#else
-                if (lane < 2 && t - 2 < nrow)
-                    mrow[wb[layer - 1] + (size_t)(r - VO_SIFT_BORDER) * wr + k] = lane ? w1 : w0;
-#endif
-            }
-        }
-    };
-
-    vo_static_for<W>([&](auto c) { VO_ET_LOAD(decltype(c)::value, decltype(c)::value); });
-    step(0, std::integral_constant<int, 0>{}, std::false_type{});
-    step(1, std::integral_constant<int, 1>{}, std::false_type{});
-#pragma unroll 1
-    for (int t0 = 2; t0 < nrow + 2; t0 += W) {
-        step(t0, std::integral_constant<int, 2>{}, std::true_type{});
-        step(t0 + 1, std::integral_constant<int, 0>{}, std::true_type{});
-        step(t0 + 2, std::integral_constant<int, 1>{}, std::true_type{});
-    }
-#undef VO_ET_LOAD
-}
-
-// The inner part of the extremum test (VO_EXT_INNER, the default): the same streaming wave with
-// only G_1 .. G_{L+1} loaded -- D_1 .. D_L, the centres of every layer and every neighbour level
-// except D_0 (layer 1's lower neighbour, G_1 - G_0) and D_{L+1} (layer L's upper one).  A bit is
-// set when its centre passes |val| > thr and the extremum test against those streamed levels;
-// k_refine completes the test for layers 1 and L (val >= / <= the 9 values of D_0 / D_{L+1})
-// before anything else and rejects the centres that fail it.  val >= max of the 27 <=> val >=
-// the max of each part, so the keypoints are the full test's; 2 of the L + 3 planes leave the
-// streamed bytes (4 (L + 1) B per octave px).  Measured: the extremum test 3.28 -> 2.34 ms, k_refine
-// 0.39 -> 0.77 ms isolated (the partial candidates), +3.5-3.9 % stereo frames/s (DESIGN.md 9e).
-template <int L>
-__global__ __launch_bounds__(64) void k_ext_inner(const Pyramid* __restrict__ py, const float* __restrict__ arena,
-                                                   unsigned long long* __restrict__ mask, float thr, int n_img, int u_first,
-                                                   int u_last)
-{
-    vo_ss_prio();
-    constexpr int NG = L + 1, ND = L, W = 3;          // streamed levels G_1..G_{L+1}, DoG D_1..D_L
-    const int lane = threadIdx.x;
-    const int u_all = xcd_remap(blockIdx.x, gridDim.x);
-    const int nu = u_last - u_first;
-    const int img = u_all / nu;
-    int u = u_first + u_all - img * nu;
-    int o = 0;
-    while (o + 1 < py->n_oct && py->ebase[o + 1] <= u) ++o;
-    o = __builtin_amdgcn_readfirstlane(o);
-    u -= py->ebase[o];
-    const OctGeom& g = py->oct[o];
-    const int rows = g.rows, cols = g.cols, pitch = g.pitch;
-    const int ns = py->estrips[o];
-    const int strip = u % ns, band = u / ns;
-    const int ir = rows - 2 * VO_SIFT_BORDER;
-    const int r0 = VO_SIFT_BORDER + band * VO_EXT_BAND;
-    const int nrow = min(VO_EXT_BAND, ir - band * VO_EXT_BAND);
-    const int xs = strip * 128, xa = xs + 2 * lane, xb = xa + 1;
-    const int hx = lane == 63 ? xs + 128 : max(xs - 1, 0);
-    const float* base = arena + img * py->istride;
-    size_t goff[NG];
-#pragma unroll
-    for (int lv = 0; lv < NG; ++lv) goff[lv] = g.g_off[lv + 1];
-    const int wr = py->wrow[o];
-    unsigned long long* mrow = mask + (size_t)img * py->n_words;
-#if VO_EXT_BSTORE
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(mrow, 0, py->n_words * 8, 0x00020000);
-#endif
-    int wb[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) wb[l] = py->wbase[o * L + l];
-    const bool in0 = xa >= VO_SIFT_BORDER && xa < cols - VO_SIFT_BORDER;
-    const bool in1 = xb >= VO_SIFT_BORDER && xb < cols - VO_SIFT_BORDER;
-
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    f2_t pm[W][NG];
-    float ph[W][NG];
-    f2_t hmx[W][ND], hmn[W][ND];
-    f2_t dc[W][L];
-
-#define VO_ES_LOAD(T, SL)                                                                          \
-    do {                                                                                           \
-        const int y_ = min(r0 - 1 + (T), rows - 1);                                                \
-        const float* rp_ = base + (size_t)y_ * pitch;                                              \
-        _Pragma("unroll") for (int lv = 0; lv < NG; ++lv) {                                        \
-            if (xa < cols) pm[SL][lv] = *reinterpret_cast<const f2_t*>(rp_ + goff[lv] + xa);      \
-            ph[SL][lv] = rp_[goff[lv] + hx];                                                       \
-        }                                                                                          \
-    } while (0)
-
-    auto step = [&](int t, auto sl_c, auto test_c) {
-        constexpr int SL = decltype(sl_c)::value;
-        f2_t d[ND];
-        float hd[ND];
-#pragma unroll
-        for (int lv = 0; lv < ND; ++lv) {
-            d[lv] = pm[SL][lv + 1] - pm[SL][lv];
-            hd[lv] = ph[SL][lv + 1] - ph[SL][lv];
-        }
-        if (t + W <= nrow + 1) VO_ES_LOAD(t + W, SL);
-#pragma unroll
-        for (int lv = 0; lv < ND; ++lv) {
-            const float la = vo_wave_shr1_or(hd[lv], d[lv].y), rb = vo_wave_shl1_or(hd[lv], d[lv].x);
-            hmx[SL][lv] = f2_t{fmaxf(fmaxf(la, d[lv].x), d[lv].y), fmaxf(fmaxf(d[lv].x, d[lv].y), rb)};
-            hmn[SL][lv] = f2_t{fminf(fminf(la, d[lv].x), d[lv].y), fminf(fminf(d[lv].x, d[lv].y), rb)};
-        }
-#pragma unroll
         for (int l = 0; l < L; ++l) dc[SL][l] = d[l];
         if constexpr (decltype(test_c)::value) {
-            constexpr int A = (SL + 1) % W, M = (SL + 2) % W;
+            constexpr int A = (SL + 1) % W, M = (SL + 2) % W;   // rows t-2, t-1 (tested)
             const int r = r0 + t - 2;
             const bool live = t - 2 < nrow;
             f2_t mx3[ND], mn3[ND];
@@ -1312,19 +1192,15 @@ __global__ __launch_bounds__(64) void k_ext_inner(const Pyramid* __restrict__ py
                         bmx = fmaxf(bmx, c ? mx3[layer].y : mx3[layer].x);
                         bmn = fminf(bmn, c ? mn3[layer].y : mn3[layer].x);
                     }
+                    // |val| > thr && (val > 0 ? val >= bmx : val <= bmn), as lane-mask compares
                     pos[c] = (val[c] > thr) & (val[c] >= bmx);
                     neg[c] = (val[c] < -thr) & (val[c] <= bmn);
                 }
                 const uint64_t w0 = __ballot((pos[0] | neg[0]) & in0), w1 = __ballot((pos[1] | neg[1]) & in1);
-                const int k = 2 * strip + lane;
-#if VO_EXT_BSTORE
+                const int k = 2 * strip + lane;               // wr is even: both words exist
                 const uint32_t mo = (lane < 2 && live) ? (uint32_t)(wb[layer - 1] + (r - VO_SIFT_BORDER) * wr + k) * 8u
                                                        : 0x80000000u;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(vo_i2, (uint64_t)(lane ? w1 : w0)), rs_m, mo, 0, 0);
-#else
-                if (lane < 2 && live)
-                    mrow[wb[layer - 1] + (size_t)(r - VO_SIFT_BORDER) * wr + k] = lane ? w1 : w0;
-#endif
             }
         }
     };
@@ -1448,7 +1324,7 @@ __global__ __launch_bounds__(256) void k_seg_emit(const Pyramid* __restrict__ py
         mw[q] = (w0 + q < nw) ? m[w0 + q] : 0ull;
         cnt += (uint32_t)__popcll(mw[q]);
     }
-    // k_ext_stream writes a strip's words as (even columns, odd columns); w0 and every mask
+    // k_ext_inner writes a strip's words as (even columns, odd columns); w0 and every mask
     // row start are even, so each (q, q+1) pair is one strip: interleave into column order
 #pragma unroll
     for (int q = 0; q < 4; q += 2) {
@@ -1646,7 +1522,6 @@ __global__ __launch_bounds__(256) void k_refine(const Pyramid* __restrict__ py, 
         // these (the loop only exits with ok at convergence, without moving), so they are kept
         // instead of re-read
         float kD[3] = {0, 0, 0}, kv = 0, kxx = 0, kyy = 0, kxy = 0;
-#if VO_EXT_INNER
         // the extremum test's remaining part (k_ext_inner streams G_1 .. G_{L+1} only): a centre of
         // layer 1 / L must also be >= (val > 0) or <= (val < 0) the 9 values of D_0 / D_{L+1}
         // around it.  It passed the rest of the 26-neighbour test with |val| > thr, so this is
@@ -1675,7 +1550,6 @@ __global__ __launch_bounds__(256) void k_refine(const Pyramid* __restrict__ py, 
             }
         }
         if (ok)
-#endif
         for (; it < VO_SIFT_MAX_INTERP; ++it) {
             const float* gb = arena + img * py->istride;
             const float* im = gb + g.g_off[layer];          // DoG level l = G_{l+1} - G_l (VO_DOG)
@@ -1720,8 +1594,8 @@ __global__ __launch_bounds__(256) void k_refine(const Pyramid* __restrict__ py, 
             scl = sigma * vo_expf(((float)layer + xi) / (float)L * 0.693147181f);
             resp = fabsf(contr);
         }
-        // Every candidate's record is stored, although with the accepted list (VO_ACC_LIST,
-        // VO_NPK_COMPACT) nothing reads a rejected one's: storing only the accepted ones (~13 %)
+        // Every candidate's record is stored, although with the accepted list (acc) and the peak
+        // counts in koff nothing reads a rejected one's: storing only the accepted ones (~13 %)
         // cut k_refine's own time 1.14 -> 0.98 ms and its PMC bytes 5.34 -> 4.84 GB per 256-frame
         // step, but the step got 3 % slower (10181 -> 9878 stereo frames/s on one box, the level
         // blurs beside it 20.4 -> 21.6 ms in situ, profiles/r06_s_ab_round6_bisect.txt; re-measured
@@ -1729,13 +1603,11 @@ __global__ __launch_bounds__(256) void k_refine(const Pyramid* __restrict__ py, 
         out->xo = xo; out->yo = yo; out->scl = scl; out->response = resp;
         out->o = o; out->layer = layer; out->r = r; out->c = c;
         out->npk = ok ? -1 : 0;
-#if VO_NPK_COMPACT
+        // the peak counts also as a 4-B array (koff, scanned in place by k_scan_cands)
         knpk[(size_t)img * cand_cap + kidx] = ok ? 0xFFFFFFFFu : 0u;   // k_orient writes the accepted ones' count
-#endif
         // the accepted candidates as a list (k_orient walks only those: on KITTI-00 street frames
         // ~6 in 7 candidates are rejected here, profiles/r05_d_content_pmc_*); the list order is
         // free -- every result is stored at its candidate's index
-#if VO_ACC_LIST
         // one atomic per (wave, image): the lanes of a wave hold consecutive candidates, one image
         // (two at an image boundary); per-lane atomics on 128 counters serialised k_refine 7x
         unsigned long long todo = __ballot(ok);
@@ -1749,7 +1621,6 @@ __global__ __launch_bounds__(256) void k_refine(const Pyramid* __restrict__ py, 
             if (ok && img == limg) acc[(size_t)limg * cand_cap + base + __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] = kidx;
             todo &= ~m;
         }
-#endif
 #undef DOGV
     }
 }
@@ -1806,11 +1677,7 @@ __device__ __forceinline__ int orient_candidate(const Pyramid* __restrict__ py, 
 #pragma unroll
     for (int b2 = 4 * lane; b2 < HS * NC; b2 += 256) *reinterpret_cast<u4_t*>(&hp[b2]) = u4_t{0u, 0u, 0u, 0u};
     __syncthreads();
-#if defined(VO_ORIENT_DIAG)
-    const int side = 2 * radius + 1, nsamp = 0;  // diagnostic build (timing only): no sample loop
-#else
     const int side = 2 * radius + 1, nsamp = side * side;
-#endif
     const float inv_side = 1.0f / (float)side;          // (s + 0.5) * inv_side is exact enough to floor (s < 2^22)
     // gradient loads through a buffer resource based at gim - P - 1: one 32-bit lane offset
     // (the window row as a 24-bit multiply of the clamped row step), row y as one 12-B load
@@ -1894,9 +1761,7 @@ __device__ __forceinline__ int orient_candidate(const Pyramid* __restrict__ py, 
     __syncthreads();
     if (lane == 0) {
         out->npk = __popcll(bal);
-#if VO_NPK_COMPACT
         *knpk_slot = (uint32_t)__popcll(bal);
-#endif
     }
     return __popcll(bal);
 }
@@ -1917,13 +1782,8 @@ __global__ __launch_bounds__(64, VO_ORIENT_WAVES) void k_orient(const Pyramid* _
     for (long t = blockIdx.x; t < total; t += gridDim.x) {
         int img, a;
         flat_find_wave(fpre, n_img, t, img, a);
-#if VO_ACC_LIST
         const int kidx = __builtin_amdgcn_readfirstlane(acc[(size_t)img * cand_cap + a]);
-#else
-        const int kidx = a;                              // every candidate (n_acc = n_cand)
-#endif
         CandOut* out = cout + (size_t)img * cand_cap + kidx;
-        if (!VO_ACC_LIST && __builtin_amdgcn_readfirstlane(out->npk) != -1) continue;
         orient_candidate<HS>(py, arena, out, knpk + (size_t)img * cand_cap + kidx, img, hp, tf, hs);
     }
 }
@@ -1936,25 +1796,16 @@ __global__ __launch_bounds__(1024) void k_scan_cands(const CandOut* __restrict__
     const int img = blockIdx.x, tid = threadIdx.x;
     int n = n_cand[img];
     if (n > cand_cap) n = cand_cap;
-    const CandOut* co = cout + (size_t)img * cand_cap;
     uint32_t* ko = koff + (size_t)img * cand_cap;
     const int chunk = (n + 1023) / 1024;
     const int a = tid * chunk, e = min(a + chunk, n);
     uint32_t s = 0;
-#if VO_NPK_COMPACT
     // the peak counts as k_refine / k_orient left them in koff (4 B per candidate instead of a
     // CandOut line each), scanned in place
-    (void)co;
     for (int k = a; k < e; ++k) s += ko[k];
     uint32_t total;
     uint32_t base = block_exscan_1024(s, sh, &total);
     for (int k = a; k < e; ++k) { const uint32_t v = ko[k]; ko[k] = base; base += v; }
-#else
-    for (int k = a; k < e; ++k) s += (uint32_t)co[k].npk;
-    uint32_t total;
-    uint32_t base = block_exscan_1024(s, sh, &total);
-    for (int k = a; k < e; ++k) { ko[k] = base; base += (uint32_t)co[k].npk; }
-#endif
     if (tid == 0) n_kp[img] = (int)total;
 }
 
@@ -1987,7 +1838,7 @@ __global__ __launch_bounds__(VO_SEL_TILE) void k_sel_keys(const CandOut* __restr
     const int n = min(n_walk[img], cand_cap);
     if (blockIdx.x == 0 && threadIdx.x == 0) n_det[img] = n_kp[img];
     for (int a = blockIdx.x * VO_SEL_TILE + threadIdx.x; a < n; a += gridDim.x * VO_SEL_TILE) {
-        const int k = VO_ACC_LIST ? acc[base + a] : a;
+        const int k = acc[base + a];
         const CandOut& co = cout[base + k];
         const int npk = co.npk;
         skey[base + a] = (unsigned long long)__float_as_uint(co.response) << 32 | (unsigned long long)(~koff[base + k]);
@@ -2028,7 +1879,7 @@ __global__ __launch_bounds__(VO_SEL_TILE) void k_sel_rank(const int* __restrict_
                 off += nq & (0u - (uint32_t)(kq > mine));
             }
         }
-        if (a < n) koff[base + (VO_ACC_LIST ? acc[base + a] : a)] = off;
+        if (a < n) koff[base + acc[base + a]] = off;
     }
 }
 
@@ -2043,7 +1894,7 @@ __global__ void k_expand(const CandOut* __restrict__ cout, const int* __restrict
     for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         int img, a;
         flat_find(fpre, n_img, t, img, a);
-        const int k = VO_ACC_LIST ? acc[(size_t)img * cand_cap + a] : a;
+        const int k = acc[(size_t)img * cand_cap + a];
         const CandOut& co = cout[(size_t)img * cand_cap + k];
         const int npk = co.npk;
         if (!npk) continue;
@@ -2124,9 +1975,6 @@ __device__ __forceinline__ void desc_tables(const Pyramid* __restrict__ py, KpIn
     const float exp_scale = -1.0f / ((float)(DW * DW) * 0.5f);
     const float hist_width = VO_SIFT_DESCR_SCL * q.scl;
     int radius = vo_round(hist_width * 1.4142135623730951f * (float)(DW + 1) * 0.5f);
-#if defined(VO_DESC_DIAG) && VO_DESC_DIAG >= 2
-    radius = 0;                                  // diagnostic build (timing only): no window tables
-#endif
     if (radius > g.dmax) radius = g.dmax;
     if (radius > VO_SIFT_DESCR_RMAX) radius = VO_SIFT_DESCR_RMAX;
     radius = min(radius, dcap);                 // (never binds: dcap bounds every refined scale)
@@ -2232,11 +2080,7 @@ __device__ __forceinline__ void desc_keypoint(const Pyramid* __restrict__ py, co
     const float ori = __uint_as_float(hdr[DT_ORI]);
     const int px = (int)hdr[DT_PX], pyy = (int)hdr[DT_PY], radius = (int)hdr[DT_RADIUS];
     const float cos_t = __uint_as_float(hdr[DT_COS]), sin_t = __uint_as_float(hdr[DT_SIN]);
-#if defined(VO_DESC_DIAG) && VO_DESC_DIAG >= 1
-    const int nsamp = 0;                         // diagnostic build (timing only): no sample loop
-#else
     const int nsamp = (int)hdr[DT_NSAMP];
-#endif
     uint32_t* hc = hfx + (lane & (DCOPIES - 1)) * DCS;
     // one sample: weights, bins, fixed-point LDS atomics
     auto accum = [&](float c_rot, float r_rot, float w, float dx, float dy) {
@@ -2675,7 +2519,7 @@ constexpr int kFeatureGrid = VO_FEATURE_GRID;
 
 // The extremum test of octaves [o_begin, o_end).  vo_api.hip enqueues it in two parts on the
 // feature stream: octave 0 as soon as the scale-space stream records ev_o0 (beside the level blurs
-// of octaves 1..), and octaves 1.. after the scale space's tail (VO_EXT_SPLIT).
+// of octaves 1..), and octaves 1.. after the scale space's tail.
 void sift_enqueue_extrema(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
                           const Pyramid* d_py, int o_begin, int o_end)
 {
@@ -2685,11 +2529,7 @@ void sift_enqueue_extrema(const Pyramid& py, SiftBuffers& b, int n_img, const vo
     const int u_first = py.ebase[std::max(o_begin, fused_octaves(py))], u_last = py.ebase[o_end];
     if (u_last > u_first) {
         const dim3 ge((u_last - u_first) * n_img);
-#if VO_EXT_INNER
 #define VO_EXT_K(LL) VO_LAUNCH(k_ext_inner<LL>, ge, dim3(64), 0, s, d_py, A, b.mask, thr, n_img, u_first, u_last)
-#else
-#define VO_EXT_K(LL) VO_LAUNCH(k_ext_stream<LL>, ge, dim3(64), 0, s, d_py, A, b.mask, thr, n_img, u_first, u_last)
-#endif
         switch (L) {
         case 1: VO_EXT_K(1); break;
         case 2: VO_EXT_K(2); break;
@@ -2754,19 +2594,18 @@ void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const v
     VO_LAUNCH(k_refine, dim3(VO_REFINE_BLOCKS), dim3(256), 0, s, d_py, A, b.cand, b.n_cand, b.cout, b.acc, b.n_acc, b.koff, b.cand_cap, n_img,
               p.contrast_threshold, p.edge_threshold, p.sigma);
     const size_t fpre_bytes = sizeof(int) * (size_t)(n_img + 1);
-    const int* n_walk = VO_ACC_LIST ? b.n_acc : b.n_cand;    // the accepted list, or every candidate
     const size_t dt_bytes = sizeof(uint32_t) * (size_t)dt_stride(py.dcap);
-    VO_LAUNCH_NAMED("k_orient", (k_orient<36>), dim3(kFeatureGrid), dim3(64), fpre_bytes, s, d_py, A, n_walk, b.acc,
+    VO_LAUNCH_NAMED("k_orient", (k_orient<36>), dim3(kFeatureGrid), dim3(64), fpre_bytes, s, d_py, A, b.n_acc, b.acc,
                     b.cout, b.koff, b.cand_cap, n_img);
     VO_LAUNCH(k_scan_cands, dim3(n_img), dim3(1024), 0, s, b.cout, b.n_cand, b.koff, b.n_kp, b.cand_cap);
     if (strongest > 0) {                                     // selectStrongest: koff becomes the slot in sorted order
         const dim3 gsel(VO_SEL_BLOCKS, n_img);
-        VO_LAUNCH(k_sel_keys, gsel, dim3(VO_SEL_TILE), 0, s, b.cout, n_walk, b.acc, b.koff, b.n_kp, b.n_det, b.skey, b.snpk,
+        VO_LAUNCH(k_sel_keys, gsel, dim3(VO_SEL_TILE), 0, s, b.cout, b.n_acc, b.acc, b.koff, b.n_kp, b.n_det, b.skey, b.snpk,
                   b.cand_cap);
-        VO_LAUNCH(k_sel_rank, gsel, dim3(VO_SEL_TILE), 0, s, n_walk, b.acc, b.skey, b.snpk, b.koff, b.n_det, b.n_kp, b.cand_cap,
+        VO_LAUNCH(k_sel_rank, gsel, dim3(VO_SEL_TILE), 0, s, b.n_acc, b.acc, b.skey, b.snpk, b.koff, b.n_det, b.n_kp, b.cand_cap,
                   strongest);
     }
-    VO_LAUNCH(k_expand, dim3(256), dim3(256), 0, s, b.cout, n_walk, b.acc, b.koff, b.kp, b.kpi, b.cand_cap, b.kp_cap,
+    VO_LAUNCH(k_expand, dim3(256), dim3(256), 0, s, b.cout, b.n_acc, b.acc, b.koff, b.kp, b.kpi, b.cand_cap, b.kp_cap,
               n_img, p.upsample, strongest > 0 ? strongest : b.kp_cap);
     // 4 histogram copies: 2 -> +4 %, 8 -> +33 % k_desc time (MI355X)
     // (capping k_desc's residency per CU with 8 / 16 / 28 KB of extra LDS per workgroup, to leave

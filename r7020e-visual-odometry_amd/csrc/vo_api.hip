@@ -71,7 +71,7 @@ struct vo_ctx {
     static constexpr int MAX_SUB = 4;
     int n_sub = 1;
     hipStream_t sub[MAX_SUB] = {};                 // sub[0]: scale-space stream, sub[1]: feature stream
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_SUB] = {}, ev_o0[MAX_SUB] = {}, ev_small[MAX_SUB] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[MAX_SUB] = {}, ev_o0[MAX_SUB] = {};
     // Asynchronous batch pipeline (vo_sift_match_batch_dev): calls alternate between two
     // buffer sets; set 0 is the context's own buffers (sb, mb, stereo jobs, pairs), set 1
     // is `aux`.  A call's scale space waits only for the previous use of its own set, so
@@ -215,8 +215,7 @@ static void destroy_streams(vo_ctx* c)
         if (c->sub[k]) hipStreamDestroy(c->sub[k]);
         if (c->ev_join[k]) hipEventDestroy(c->ev_join[k]);
         if (c->ev_o0[k]) hipEventDestroy(c->ev_o0[k]);
-        if (c->ev_small[k]) hipEventDestroy(c->ev_small[k]);
-        c->sub[k] = nullptr; c->ev_join[k] = nullptr; c->ev_o0[k] = nullptr; c->ev_small[k] = nullptr;
+        c->sub[k] = nullptr; c->ev_join[k] = nullptr; c->ev_o0[k] = nullptr;
     }
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     c->ev_fork = nullptr;
@@ -313,7 +312,6 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         if (e != hipSuccess) return bail("stream", e);
         if ((e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
         if ((e = hipEventCreateWithFlags(&c->ev_o0[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_small[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
     }
     if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("event", e);
     for (int k = 0; k < 2; ++k) {
@@ -972,53 +970,44 @@ static SetRef set_ref(vo_ctx* c, int set)
 // feature stages + stereo matching on sub[1] once that part's scale space is done, so the
 // features of part k overlap the scale space of part k+1 (and of the next call, which uses
 // the other set).  Inputs are ordered after earlier work on `stream`; the set's previous
-// contents are released by its ev_done.  With `join`, `stream` waits for the result.
-// Where the extremum test of octaves 1.. runs: 1 (default) on the feature stream after the
-// scale space, 0 at the scale space's tail.  With the faster k_desc / k_orient of round 3 the
-// scale-space stream became the critical path again, and moving that 0.4 ms of test off it
-// gave 7.51-7.55 vs 7.66-7.77 ms per 64-frame step (A/B on one box).
-#ifndef VO_EXT_SPLIT
-#define VO_EXT_SPLIT 1
-#endif
-// Where the LDS-sized octaves (k_small_pyr: one 1024-thread workgroup per image, ~120 KB of LDS,
-// 0.13 ms isolated but ~1 ms in situ while it waits for a CU with that much free LDS) run:
-// 0 at the scale space's tail; 1 at the head of the feature stream's second part (measured
-// slower: the feature stream is the critical one at 128 frames per step); 2 on a
-// stream of their own (sub[2]) after the level blurs, so neither stream waits for its
-// placement -- only the extremum test of the small octaves does.
-#ifndef VO_ARENA_EVENT
-#define VO_ARENA_EVENT 1          // the scale space of a set waits for its arena's last reader, not the whole feature stream
-#endif
-#ifndef VO_SMALL_STREAM
-#define VO_SMALL_STREAM 0
-#endif
+// contents are released by its events (below).  With `join`, `stream` waits for the result.
+// The arrangement of one part:
+//   sub[0]  waits for the set's arena (ev_arena: the previous call's last reader, k_desc -- not
+//           that call's whole feature stream, whose stereo match reads descriptors only); the
+//           scale space of the large octaves, ev_o0 once octave 0 is built, then the LDS-sized
+//           octaves (k_small_pyr) at its tail; ev_join.
+//   sub[1]  after ev_o0 the extremum test of octave 0, beside the scale space of octaves 1..;
+//           after ev_join the extremum test of octaves 1.., the feature stages and the stereo
+//           match.
+// The extremum test of octaves 1.. at the scale space's tail instead (round 3's placement, then
+// 0.4 ms on the critical stream) measured 7.66-7.77 against 7.51-7.55 ms per 64-frame step and no
+// better since.  k_small_pyr (one 1024-thread workgroup per image, ~120 KB of
+// LDS: 0.13 ms isolated, ~1 ms in situ while it waits for a CU with that much free LDS) at the
+// head of the feature stream's part, or on a stream of its own, measured slower than waiting at
+// the tail.  Waiting for the set's ev_done (after the stereo match) instead of
+// ev_arena cost the full path 1.4 %.
 static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uint8_t* d_r, int B, bool join,
                                bool fork = true)
 {
     const size_t fs = (size_t)c->rows * c->cols;
     const int parts = std::min(c->n_sub, B);
     SetRef S = set_ref(c, set);
-    hipStream_t sp = c->sub[0], st = c->sub[1], ss = c->sub[2];
+    hipStream_t sp = c->sub[0], st = c->sub[1];
     if (fork) {                                                 // inputs / earlier work on `stream`
         HIPC(c, hipEventRecord(c->ev_fork, c->stream));
         HIPC(c, hipStreamWaitEvent(sp, c->ev_fork, 0));
     }
-#if VO_ARENA_EVENT
     // the set's arena free: its previous call's last reader (k_desc) is done -- the stereo match
     // of that call (descriptors only) may still run; everything else of the set is written by st,
     // in order behind it
     HIPC(c, hipStreamWaitEvent(sp, c->ev_arena[set], 0));
-#else
-    HIPC(c, hipStreamWaitEvent(sp, c->ev_done[set], 0));      // set free (its previous features done)
-#endif
     const int o_small = sift_small_octave(c->py);
     const bool undist = c->ud_on[0] || c->ud_on[1];           // vo_set_distortion
     if (undist) c->rect_B = B;
     c->sel_used[set] = c->strongest > 0;
-    const bool ext_on_st = VO_EXT_SPLIT || VO_SMALL_STREAM != 0;   // the test of octaves 1.. on st
     // scale space on sp; octave 0's extremum test on st as soon as octave 0 is built (beside the
-    // scale space of octaves 1..), the other octaves' on st after the scale space (VO_EXT_SPLIT)
-    // -- the split that balances the two streams
+    // scale space of octaves 1..), the other octaves' on st after the scale space -- the split
+    // that balances the two streams
     for (int p = 0; p < parts; ++p) {
         const int f0 = B * p / parts, nf = B * (p + 1) / parts - f0;
         const uint8_t* pl = d_l + f0 * fs;
@@ -1042,14 +1031,8 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
         ImageSrc src{pl, pr, fs, c->cols, 0};
         SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
         sift_enqueue_pyramid(c->py, v, src, 2 * nf, c->sp, sp, c->d_py, c->ev_o0[p]);
-        if (VO_SMALL_STREAM == 0) sift_enqueue_small(c->py, v, 2 * nf, sp, c->d_py);
-        if (!ext_on_st) sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, sp, c->d_py, 1, c->py.n_oct);
+        sift_enqueue_small(c->py, v, 2 * nf, sp, c->d_py);
         HIPC(c, hipEventRecord(c->ev_join[p], sp));
-        if (VO_SMALL_STREAM == 2) {
-            HIPC(c, hipStreamWaitEvent(ss, c->ev_join[p], 0));
-            sift_enqueue_small(c->py, v, 2 * nf, ss, c->d_py);
-            HIPC(c, hipEventRecord(c->ev_small[p], ss));
-        }
     }
     for (int p = 0; p < parts; ++p) {
         const int f0 = B * p / parts, nf = B * (p + 1) / parts - f0;
@@ -1057,16 +1040,11 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
         // (a synchronous profiled call -- bench.py's isolated pass -- starts it after the whole
         // scale space, so its per-kernel durations stay undisturbed)
         const bool iso = c->prof.on && join;
-        if (iso && VO_SMALL_STREAM == 2) HIPC(c, hipStreamWaitEvent(st, c->ev_small[p], 0));
         HIPC(c, hipStreamWaitEvent(st, iso ? c->ev_join[p] : c->ev_o0[p], 0));
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 0, 1);
         HIPC(c, hipStreamWaitEvent(st, c->ev_join[p], 0));
-        if (VO_SMALL_STREAM == 1) sift_enqueue_small(c->py, v, 2 * nf, st, c->d_py);
-        if (ext_on_st) {
-            sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 1, o_small);
-            if (VO_SMALL_STREAM == 2) HIPC(c, hipStreamWaitEvent(st, c->ev_small[p], 0));
-            sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, o_small, c->py.n_oct);
-        }
+        sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 1, o_small);
+        sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, o_small, c->py.n_oct);
         sift_enqueue_features(c->py, v, 2 * nf, c->sp, st, c->d_py, c->strongest);
         if (p == parts - 1) HIPC(c, hipEventRecord(c->ev_arena[set], st));
         match_launch(match_view(*S.mb, f0), S.jobs + f0, nf, c->mp, st);

@@ -81,14 +81,6 @@ struct Pyramid {
     int dcap;                                 // largest descriptor window radius the parameters allow
 };
 
-// Feature-stage build switch (A/B builds; the product uses the default):
-//  VO_ACC_LIST   1: k_refine lists the accepted candidates and k_orient / k_expand walk the list
-#ifndef VO_ACC_LIST
-#define VO_ACC_LIST 1
-#endif
-
-
-
 // k_desc's per-keypoint window tables in LDS (desc_tables), u32 words: a header of DT_HDR words
 // (DT_ORI .. DT_LAYER below), the row table (2 dcap + 10 entries) and the separable window
 // weights (dcap + 1 floats); stride rounded to 16 B.
@@ -100,15 +92,6 @@ static inline __host__ __device__ int dt_stride(int dcap) { return (DT_HDR + 3 *
 
 #ifndef VO_EXT_BAND
 #define VO_EXT_BAND 30            // interior rows per extremum-test wave (a multiple of 3)
-#endif
-#ifndef VO_EXT_INNER
-#define VO_EXT_INNER 1            // extremum test: 1 = k_ext_inner + k_refine's outer-level check, 0 = k_ext_stream (all L+3 levels)
-#endif
-#ifndef VO_NPK_COMPACT
-#define VO_NPK_COMPACT 1          // peak counts also as a 4-B array (koff, scanned in place) for k_scan_cands
-#endif
-#ifndef VO_EXT_BSTORE
-#define VO_EXT_BSTORE 1           // extremum test: mask words by unconditional buffer stores (0: branchy stores)
 #endif
 #define VO_SEG_WORDS 1024
 
@@ -266,18 +249,12 @@ struct MatchTop2 { float best; int idx; float second; int pad; };
 struct MatchBuffers {
     MatchJob* jobs = nullptr;        // device copy of the jobs [max_jobs]
     MatchTop2* partial = nullptr;    // [max_jobs][n_chunks][row_cap]
-    int* res = nullptr;              // [max_jobs][row_cap] accepted F2 index per F1 row, -1 if none
     int max_jobs = 0, row_cap = 0, n_chunks = 0;
 };
 
 #ifndef VO_MATCH_CHUNK
 #define VO_MATCH_CHUNK 4096          // F2 columns per task (512/1024/2048 swept before; 4096: the tracking steps' ~2.1 k
                                      // columns in one chunk, match -10 % isolated, full path +1.3 %, r06_y)
-#endif
-
-#ifndef VO_MATCH_FINISH
-#define VO_MATCH_FINISH 1            // 1: k_match_finish (merge + compact, and a tracking step's index composition, in one
-                                     // launch); 0: k_match_merge + k_match_compact (+ k_compose) as separate launches
 #endif
 
 hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap);

@@ -58,8 +58,11 @@ def fused_octaves(rows: int, cols: int, layers: int = 3, enabled: bool = False) 
 def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, fused: bool = False, ext_inner: bool = True) -> dict:
     """Algorithmic bytes per CALL (all launches of that kernel name in one
     batch of n_img images) and launches per call, per kernel name.  ext_inner: the
-    extremum test as k_ext_inner (the default build, VO_EXT_INNER=1: G_1..G_{L+1} streamed,
-    the outer levels checked by k_refine around candidates) instead of k_ext_stream (all L+3)."""
+    extremum test as k_ext_inner (the kernel: G_1..G_{L+1} streamed, the outer levels checked
+    by k_refine around candidates).  ext_inner=False models the dense form that streams all
+    L+3 levels, under the key k_ext_stream<L>, for comparison only:
+    that kernel left csrc/ together with the A/B build switches, in the commit that added
+    this sentence."""
     dims = octave_dims(rows, cols)
     lv = layers + 2          # blurred levels per octave (1..L+2)
     n_fused = fused_octaves(rows, cols, layers, fused)
