@@ -1088,8 +1088,7 @@ __global__ __launch_bounds__(64) void k_ext_inner(const Pyramid* __restrict__ py
     constexpr int NG = L + 1, ND = L, W = 3;          // streamed levels G_1..G_{L+1}, DoG D_1..D_L
     const int lane = threadIdx.x;
     const int u_all = xcd_remap(blockIdx.x, gridDim.x);
-    // units [u_first, u_last) of every image (a range of octaves; those below a fused prefix
-    // are tested by k_octave)
+    // units [u_first, u_last) of every image (a range of octaves)
     const int nu = u_last - u_first;
     const int img = u_all / nu;
     int u = u_first + u_all - img * nu;
@@ -2370,24 +2369,6 @@ static float ext_threshold(const Pyramid& py, const vo_sift_params& p)
     return (float)floor(0.5 * p.contrast_threshold / py.L * 255.0);
 }
 
-// octaves [0, n) whose levels 1..L+2, extremum test and next base k_octave computes in one pass
-// (octave.hip): a prefix of the octaves, below the LDS-sized ones.  Experimental: bit-exact but
-// measured 2.4x slower than the per-level kernels on MI355X, so it is compiled only
-// into the test build libvo_exp.so (VO_EXPERIMENTAL, selected there by vo_exp_set); the product
-// library always takes the per-level kernels.
-static int fused_octaves(const Pyramid& py)
-{
-#if VO_EXPERIMENTAL
-    if (!g_exp_fused_octave) return 0;
-    int n = 0;
-    while (n < py.n_oct && octave_fused_ok(py, n)) ++n;
-    return n;
-#else
-    (void)py;
-    return 0;
-#endif
-}
-
 // First octave from which every remaining octave fits the one-launch LDS path (k_small_pyr),
 // its reflect-table length and dynamic LDS size.
 // LDS holds 3 planes of the largest octave (cap floats), the largest next-octave base (bcap
@@ -2441,17 +2422,6 @@ void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src
     float* A = b.arena;
     const SmallPlan sp = small_plan(py);
     const int o_small = sp.o_small;
-    const int n_fused = std::min(fused_octaves(py), o_small);
-    if (n_fused > 0) {
-        // k_octave ORs its extremum words into the mask (strips share the words at their
-        // boundaries): clear the fused octaves' words of every image first
-        const size_t w0 = (size_t)py.wbase[0], w1 = (size_t)py.wbase[n_fused * L];
-        hipMemset2DAsync(b.mask + w0, sizeof(unsigned long long) * py.n_words, 0, sizeof(unsigned long long) * (w1 - w0),
-                         n_img, s);
-    }
-#if VO_EXPERIMENTAL
-    const float thr = ext_threshold(py, p);
-#endif
     bool base_done = false;                            // octave o's base already stored
     for (int o = 0; o < py.n_oct; ++o) {
         const OctGeom& g = py.oct[o];
@@ -2477,18 +2447,12 @@ void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src
                 launch_blur<0>(gf, s, b.tmp, g.plane, py.istride, g.pitch, R, C, A + g.g_off[0], nullptr, K0, src, 0, 0,
                                "k_blur_base");
             }
-        } else if (o - 1 >= n_fused && !base_done) {  // (a fused octave / level-L blur wrote it)
+        } else if (!base_done) {                       // (otherwise a streamed level-L blur wrote it)
             const OctGeom& pg = py.oct[o - 1];
             VO_LAUNCH(k_down, dim3((C + 255) / 256, R, n_img), dim3(256), 0, s, A + pg.g_off[L], py.istride, pg.pitch,
                       A + g.g_off[0], py.istride, g.pitch, C);
         }
         base_done = false;
-#if VO_EXPERIMENTAL
-        if (o < n_fused) {
-            octave_fused_launch(py, d_py, b, o, n_img, thr, s);
-            continue;
-        }
-#endif
         for (int i = 1; i < L + 3; ++i) {
             Kern K = make_kern(py, i);
             // level L stores the next octave's base from its store path (no k_down pass: that
@@ -2526,7 +2490,7 @@ void sift_enqueue_extrema(const Pyramid& py, SiftBuffers& b, int n_img, const vo
     const int L = py.L;
     float* A = b.arena;
     const float thr = ext_threshold(py, p);
-    const int u_first = py.ebase[std::max(o_begin, fused_octaves(py))], u_last = py.ebase[o_end];
+    const int u_first = py.ebase[o_begin], u_last = py.ebase[o_end];
     if (u_last > u_first) {
         const dim3 ge((u_last - u_first) * n_img);
 #define VO_EXT_K(LL) VO_LAUNCH(k_ext_inner<LL>, ge, dim3(64), 0, s, d_py, A, b.mask, thr, n_img, u_first, u_last)

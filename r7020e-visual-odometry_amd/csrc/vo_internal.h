@@ -202,28 +202,10 @@ struct UndistortSide {
 void undistort_launch(const UndistortSide* sides, int n_sides, int rows, int cols, int B, size_t in_stride,
                       size_t out_stride, hipStream_t s);
 
-// One octave's levels 1..5 + extremum test + next octave base in one pass (octave.hip).
-struct OctArgs {
-    float* arena;
-    size_t istride;                     // floats per image
-    int R, C, pitch, pad0;
-    size_t goff[6];                     // this octave's G_0..G_5 plane offsets
-    float* nbase;                       // next octave's G_0 plane (image 0), or nullptr
-    int Rn, Cn, pitchn, pad1;
-    unsigned long long* mask;
-    int n_words, wr;                    // words per image, words per mask row of this octave
-    int wb[3];                          // word base of layers 1..3 of this octave
-    float thr;                          // extremum threshold (DoG units)
-    float k[6][16];                     // taps of levels 1..5 (k[i][0..r_i])
-    int n_strips, pad2;
-};
 #if VO_EXPERIMENTAL
-// test build only (libvo_exp.so): the fused octave (octave.hip) and the eager MSAC kernels, each
-// selected by vo_exp_set; the product libvo.so has neither the kernels nor a switch
-bool octave_fused_ok(const Pyramid& py, int o);
-void octave_fused_launch(const Pyramid& py, const Pyramid* d_py, const SiftBuffers& b, int o, int n_img, float thr,
-                         hipStream_t s);
-extern int g_exp_fused_octave, g_exp_msac_eager;
+// test build only (libvo_exp.so): the eager MSAC kernels (geom.hip), selected by
+// vo_exp_set; the product libvo.so has neither the kernels nor a switch
+extern int g_exp_msac_eager;
 #endif
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize, 160 KB) once per (kernel, device)
 void raise_lds_limit(const void* fn);

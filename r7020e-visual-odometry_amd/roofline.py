@@ -38,24 +38,7 @@ def pyramid_bytes_per_image(rows: int, cols: int, layers: int = 3) -> int:
     return rows * cols + 4 * (2 * G + 2 * D)
 
 
-FUSED_MIN_COLS, FUSED_MIN_ROWS = 256, 64   # csrc/octave.hip octave_fused_ok (default SIFT radii, 3 layers)
-
-
-def fused_octaves(rows: int, cols: int, layers: int = 3, enabled: bool = False) -> int:
-    """Octaves [0, n) the test build libvo_exp.so builds with k_octave when vo_exp_set selects it
-    (levels 1..L+2, extremum test and the next base in one pass): the leading octaves at least
-    256 columns wide and 64 rows tall.  The product libvo.so has no k_octave: 0 by default."""
-    if layers != 3 or not enabled:
-        return 0
-    dims = octave_dims(rows, cols)
-    o_small = next((o for o in range(1, len(dims)) if all(r * c <= SMALL_PX for r, c in dims[o:])), len(dims))
-    n = 0
-    while n < min(len(dims), o_small) and dims[n][1] >= FUSED_MIN_COLS and dims[n][0] >= FUSED_MIN_ROWS:
-        n += 1
-    return n
-
-
-def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, fused: bool = False, ext_inner: bool = True) -> dict:
+def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, ext_inner: bool = True) -> dict:
     """Algorithmic bytes per CALL (all launches of that kernel name in one
     batch of n_img images) and launches per call, per kernel name.  ext_inner: the
     extremum test as k_ext_inner (the kernel: G_1..G_{L+1} streamed, the outer levels checked
@@ -65,7 +48,6 @@ def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, fused: bool 
     this sentence."""
     dims = octave_dims(rows, cols)
     lv = layers + 2          # blurred levels per octave (1..L+2)
-    n_fused = fused_octaves(rows, cols, layers, fused)
     out = {}
 
     def add(name, nbytes, launches):
@@ -83,11 +65,6 @@ def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, fused: bool 
             continue
         # octave o's base (o >= 1, below o_small) is stored by the level-L blur of octave o - 1
         # (priced with k_blur_fused below); k_blur_small decimates its own first base
-        if o < n_fused:
-            # k_octave: G_0 in once, G_1..G_{L+2} out once, the next octave's base out (1/4 px)
-            nxt = 4 * dims[o + 1][0] * dims[o + 1][1] * n_img if o + 1 < len(dims) else 0
-            add(f"k_octave_o{o}", 4 * px * (1 + lv) + nxt, 1)
-            continue
         nb = 4 * dims[o + 1][0] * dims[o + 1][1] * n_img if o + 1 < o_small else 0
         add("k_blur_fused", 8 * px * lv + nb, lv)                         # G_{i-1} in, G_i out (+ next base)
     # extremum test reads the L+1 (k_ext_inner) or L+3 (k_ext_stream) Gaussian levels of every
@@ -95,9 +72,9 @@ def kernel_bytes(rows: int, cols: int, n_img: int, layers: int = 3, fused: bool 
     # two launches when octave 0 is tested separately (on the feature stream, beside the scale
     # space of octaves 1..; the rest at the scale space's tail)
     nlev = layers + 1 if ext_inner else layers + 3
-    ext = sum(4 * nlev * r * c for o, (r, c) in enumerate(dims) if o >= n_fused) * n_img
+    ext = sum(4 * nlev * r * c for r, c in dims) * n_img
     if ext:
-        add(f"k_ext_{'inner' if ext_inner else 'stream'}<{layers}>", ext, 2 if n_fused == 0 and len(dims) > 1 else 1)
+        add(f"k_ext_{'inner' if ext_inner else 'stream'}<{layers}>", ext, 2 if len(dims) > 1 else 1)
     return out
 
 

@@ -111,9 +111,9 @@ EXPORTS = [
     "vo_set_strongest", "vo_fetch_detected_count",
 ]
 
-# the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the experimental kernels kept
-# as cross-checks (fused octave, eager MSAC), selected by its extra export vo_exp_set.  Only the
-# parity tests load it (load_experimental_library); the product path never does.
+# the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the eager MSAC kernels kept
+# as a cross-check of k_msac, selected by its extra export vo_exp_set.  Only their parity test
+# loads it (load_experimental_library); the product path never does.
 EXP_LIBPATH = PKG / "lib" / "libvo_exp.so"
 
 _libs: dict = {}
@@ -215,7 +215,7 @@ def experimental_library_path() -> Path:
 
 
 def load_experimental_library():
-    """The test build libvo_exp.so (experimental_library_path()) with `vo_exp_set(fused_octave,
+    """The test build libvo_exp.so (experimental_library_path()) with `vo_exp_set(ignored,
     msac_eager)` bound; pass it to Context(lib=...).  Raises VOError if it is not built."""
     L = load_library(experimental_library_path())
     if not hasattr(L, "vo_exp_set"):

@@ -50,9 +50,9 @@ def test_product_never_imports_or_links_the_oracle():
 
 
 def test_product_library_has_no_experiments_or_env_switches():
-    """The experimental kernels (fused octave, eager MSAC) live only in the test build
-    libvo_exp.so (csrc `make exp`, -DVO_EXPERIMENTAL=1); the product library carries neither the
-    kernels nor any environment-variable switch."""
+    """The eager MSAC kernels live only in the test build libvo_exp.so (csrc `make exp`,
+    -DVO_EXPERIMENTAL=1) and the fused octave kernel is removed; the product library carries
+    neither kernels nor any environment-variable switch."""
     lib = PKG / "lib" / "libvo.so"
     syms = subprocess.run(["nm", "-C", str(lib)], capture_output=True, text=True, check=True).stdout
     for k in ("k_octave", "k_msac_hyp", "k_msac_score", "k_msac_select", "vo_exp_set"):
@@ -65,7 +65,7 @@ def test_product_library_has_no_experiments_or_env_switches():
     exp = PKG / "lib" / "libvo_exp.so"
     assert exp.exists(), "build() builds the test build too"
     xs = subprocess.run(["nm", "-C", str(exp)], capture_output=True, text=True, check=True).stdout
-    for k in ("k_octave", "k_msac_hyp", "vo_exp_set"):
+    for k in ("k_msac_hyp", "vo_exp_set"):
         assert k in xs, k
 
 

@@ -15,7 +15,6 @@ generic base; k_down runs exactly where level L of a large octave was generic; e
 k_blur_small (k_small_pyr) and the feature kernels.  The refusals beyond the cap are in
 tests/test_abi.py (no GPU needed)."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -239,40 +238,7 @@ def test_select_strongest_at_five_layers(vo, oracle):
     ctx.close()
 
 
-# ------------------------------------------------------------------ (e) the experimental library
-def test_experimental_library_equals_product_at_other_parameters(vo):
-    """libvo_exp.so with the fused-octave path selected (vo_exp_set(1, 0)) must fall back to the
-    per-level kernels for radii other than the defaults' (octave_fused_ok) and equal libvo.so."""
-    if os.environ.get("VO_LIBPATH") and not vo.experimental_library_path().exists():
-        pytest.skip("variant build without its own libvo_exp.so")
-    rows, cols = 150, 200
-    exp = vo.load_experimental_library()
-    outs = []
-    for lib in (None, exp):
-        if lib is not None:
-            lib.vo_exp_set(1, 0)
-        try:
-            ctx = vo.Context(rows, cols, 2, sift=_params(vo, 2, 1.6, 1), lib=lib)
-            _batch(vo, ctx, rows, cols)
-            planes = [ctx.fetch_gaussian(img, o, i) for img in (0, 3) for o in range(3) for i in range(5)]
-            kps = [ctx.fetch_keypoints(img) for img in range(4)]
-            pairs = [ctx.fetch_stereo_pairs(f) for f in range(2)]
-            outs.append((planes, kps, pairs))
-            ctx.close()
-        finally:
-            if lib is not None:
-                lib.vo_exp_set(0, 0)
-    (p0, k0, s0), (p1, k1, s1) = outs
-    for a, b in zip(p0, p1):
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    for (ka, da), (kb, db) in zip(k0, k1):
-        assert ka.tobytes() == kb.tobytes() and np.array_equal(da, db)
-    for a, b in zip(s0, s1):
-        assert np.array_equal(a, b)
-    assert sum(len(ka) for ka, _ in k0) > 100 and sum(len(a) for a in s0) > 20
-
-
-# ------------------------------------------------------------------ (f) the accepted side of the bounds
+# ------------------------------------------------------------------ (e) the accepted side of the bounds
 @pytest.mark.parametrize("L,sigma", [(1, 1.4), (2, 3.4), (3, 5.0), (3, 5.2)])
 def test_sigma_next_to_the_radius_cap_is_accepted_and_exact(vo, oracle, L, sigma):
     """Top-level radius 39, and at (3, 5.2) 40 = VO_SIFT_MAX_RADIUS itself (the refused side, 45 /

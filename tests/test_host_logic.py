@@ -34,24 +34,15 @@ def test_roofline_model_matches_survey():
     # default path: per-level blurs (k_blur_fused, one launch per level of octaves 0..3; level 3
     # also stores the next octave's base, so no k_down pass), octaves 4..8 (<= 9216 px per
     # plane) in the single LDS-resident k_blur_small
-    kb = roofline.kernel_bytes(375, 1242, 2, fused=False)
-    assert roofline.fused_octaves(375, 1242, enabled=False) == 0
+    kb = roofline.kernel_bytes(375, 1242, 2)
     assert kb["k_blur_fused"][1] == 4 * 5 and "k_down" not in kb and kb["k_blur_small"][1] == 1
     assert kb["k_blur_fused"][0] == 2 * sum(8 * 5 * r * c + (4 * dims[o + 1][0] * dims[o + 1][1] if o < 3 else 0)
                                             for o, (r, c) in enumerate(dims[:4]))
     assert kb["k_ext_inner<3>"][0] == 2 * sum(4 * 4 * r * c for r, c in dims)      # G_1..G_4 streamed
-    kd = roofline.kernel_bytes(375, 1242, 2, fused=False, ext_inner=False)
+    kd = roofline.kernel_bytes(375, 1242, 2, ext_inner=False)
     assert kd["k_ext_stream<3>"][0] == 2 * sum(4 * 6 * r * c for r, c in dims)     # all L+3 levels
-    # experimental k_octave path (test build libvo_exp.so, vo_exp_set): octaves 0..3 (>= 256 columns, >= 64 rows)
-    # are one launch each (levels, extremum test, next base)
-    kf = roofline.kernel_bytes(375, 1242, 2, fused=True)
-    assert roofline.fused_octaves(375, 1242, enabled=True) == 4
-    assert all(kf[f"k_octave_o{o}"][1] == 1 for o in range(4)) and "k_blur_fused" not in kf and "k_down" not in kf
-    assert kf["k_blur_base"][1] == 1 and kf["k_blur_small"][1] == 1
-    R, C = dims[0]
-    assert kf["k_octave_o0"][0] == 2 * (4 * R * C * 6 + 4 * dims[1][0] * dims[1][1])   # G0 in, G1..5 out, next base
-    # other layer counts keep the per-level kernels
-    kb5 = roofline.kernel_bytes(375, 1242, 2, layers=4, fused=True)
+    # other layer counts: one launch per level all the same
+    kb5 = roofline.kernel_bytes(375, 1242, 2, layers=4)
     assert kb5["k_blur_fused"][1] == 4 * 6 and "k_down" not in kb5
 
 
