@@ -908,7 +908,8 @@ void geom_enqueue(GeomBuffers& g, const MatchBuffers& mb, const MatchJob* d_trac
     VO_LAUNCH(k_lm_tri, dim3(16, B), dim3(64), 0, s, g.spos, g.lm_new, g.lm_M, K, cal, g.lm_X, g.lm_keep, g.lm_rows);
 }
 
-// block f: its offset is the sum of the earlier frames' row counts (B <= 128), then a plain copy
+// block f: its offset is the sum of the earlier frames' row counts (a loop over them: any B up to
+// VO_MAX_BATCH), then a plain copy
 __global__ __launch_bounds__(256) void k_lm_pack(const float* __restrict__ lm_X, const uint8_t* __restrict__ lm_keep,
                                                  const int* __restrict__ lm_rows, int kp_cap, float* __restrict__ pX,
                                                  uint8_t* __restrict__ pkeep)

@@ -2364,6 +2364,15 @@ static bool launch_blur(dim3 grid, hipStream_t s, const float* src, size_t plane
     }
 }
 
+// launch_blur_r lowers the band height of a level blur below VO_BLUR_MAX_TH when the plane is too
+// small for VO_BLUR_WAVES waves at full bands: such an octave is latency-bound rather than HBM-bound
+static bool blur_latency_bound(int R, int C, int n_img)
+{
+    const int cpl = C <= VO_CPL2_MAXC ? 2 : 4;
+    const long n_strips = (C + 64 * cpl - 1) / (64 * cpl);
+    return (long)R * n_strips * n_img / VO_BLUR_WAVES < VO_BLUR_MAX_TH;
+}
+
 static float ext_threshold(const Pyramid& py, const vo_sift_params& p)
 {
     return (float)floor(0.5 * p.contrast_threshold / py.L * 255.0);
@@ -2400,9 +2409,10 @@ static SmallPlan small_plan(const Pyramid& py)
 }
 
 // The LDS-sized octaves (one k_small_pyr launch).  sift_enqueue_pyramid_tail enqueues it on the
-// scale-space stream after the last level blur (its workgroups need ~120 KB of one CU's LDS; by
-// then octave 0's extremum test has moved to the feature stream, so the previous batch's
-// descriptor waves no longer hold every CU's LDS when it arrives -- DESIGN.md §9c).
+// scale-space stream after the last level blur, the batched path at the end of the down chain
+// (its workgroups need ~120 KB of one CU's LDS; by then octave 0's extremum test has moved to the
+// feature stream, so the previous batch's descriptor waves no longer hold every CU's LDS when it
+// arrives -- DESIGN.md §9c).
 int sift_small_octave(const Pyramid& py) { return small_plan(py).o_small; }
 
 void sift_enqueue_small(const Pyramid& py, SiftBuffers& b, int n_img, hipStream_t s, const Pyramid* d_py)
@@ -2415,18 +2425,35 @@ void sift_enqueue_small(const Pyramid& py, SiftBuffers& b, int n_img, hipStream_
                     sp.rtab, sp.cap, sp.bcap);
 }
 
+// With ch.down the scale space forks into two chains after the level-L blur of octave o_fork:
+// octave 1 (octave 0 when it is the only large one), moved down past every octave whose level blurs
+// still run at full bands -- those are HBM-bound, and beside the octave above they only share its
+// rate (1920x1080 at 128 pairs with octaves 2, 3 on the down chain: 0.4-0.8 % slower than one chain;
+// at 1242x375 and 256 pairs forking after octave 1 or 2 measured the same).  That blur is the last launch anything below its
+// octave depends on: it stores the next octave's base, or k_down / k_small_pyr read its plane.  The
+// top chain stays on s: octaves 0..o_fork whole, so it ends with o_fork's levels L+1, L+2.  The down
+// chain, on ch.down behind ch.ev_fork, holds the octaves after o_fork; the caller enqueues
+// k_small_pyr there too.  Neither chain reads what the other writes; the extremum test of the octaves
+// from o_fork on needs both.  Fork octave 1: the latency-bound octaves 2.. and k_small_pyr run beside
+// octave 1's two widest blurs instead of alone at the tail, and ev_o0 fires as early as on one chain
+// (forking after octave 0 delayed it by the down chain's share of the GPU; after octave 2 measured
+// the same as after octave 1: DESIGN.md §9j).
 void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img, const vo_sift_params& p,
-                          hipStream_t s, const Pyramid* d_py, hipEvent_t ev_o0)
+                          hipStream_t s, const Pyramid* d_py, hipEvent_t ev_o0, const ScaleChains& ch)
 {
     const int L = py.L;
     float* A = b.arena;
     const SmallPlan sp = small_plan(py);
     const int o_small = sp.o_small;
+    const bool forked = ch.down != nullptr && ch.down != s;
+    int o_fork = std::min(1, o_small - 1);
+    while (o_fork + 1 < o_small && !blur_latency_bound(py.oct[o_fork + 1].rows, py.oct[o_fork + 1].cols, n_img)) ++o_fork;
     bool base_done = false;                            // octave o's base already stored
     for (int o = 0; o < py.n_oct; ++o) {
         const OctGeom& g = py.oct[o];
         const int R = g.rows, C = g.cols;
         if (o == o_small) break;                       // octaves o_small.. : sift_enqueue_small
+        if (forked && o == o_fork + 1) s = ch.down;    // (k_down, where level L was not streamed, included)
         dim3 gf((C + FT_W - 1) / FT_W, (R + FT_H - 1) / FT_H, n_img);
         if (o == 0) {
             Kern K0 = make_kern(py, 0);
@@ -2467,6 +2494,10 @@ void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src
             const bool streamed = launch_blur<0>(gf, s, A + g.g_off[i - 1], py.istride, py.istride, g.pitch, R, C,
                                                  A + g.g_off[i], nullptr, K, src, 0, 0);
             if (emit) base_done = streamed;
+            if (forked && o == o_fork && i == L) {               // the down chain may start
+                hipEventRecord(ch.ev_fork, s);
+                hipStreamWaitEvent(ch.down, ch.ev_fork, 0);
+            }
         }
         if (o == 0 && ev_o0) hipEventRecord(ev_o0, s);           // octave 0 complete: its extremum test may start
     }

@@ -72,6 +72,11 @@ struct vo_ctx {
     int n_sub = 1;
     hipStream_t sub[MAX_SUB] = {};                 // sub[0]: scale-space stream, sub[1]: feature stream
     hipEvent_t ev_fork = nullptr, ev_join[MAX_SUB] = {}, ev_o0[MAX_SUB] = {};
+    // the scale space's second chain (octaves 2.. and k_small_pyr, beside octave 1's top levels):
+    // ev_down[p] is recorded on sub[0] after the fork octave's level-L blur of part p, ev_top[p]
+    // at the end of sub[0]'s chain, ev_join[p] at the end of this one
+    hipStream_t down = nullptr;
+    hipEvent_t ev_down[MAX_SUB] = {}, ev_top[MAX_SUB] = {};
     // Asynchronous batch pipeline (vo_sift_match_batch_dev): calls alternate between two
     // buffer sets; set 0 is the context's own buffers (sb, mb, stereo jobs, pairs), set 1
     // is `aux`.  A call's scale space waits only for the previous use of its own set, so
@@ -215,8 +220,12 @@ static void destroy_streams(vo_ctx* c)
         if (c->sub[k]) hipStreamDestroy(c->sub[k]);
         if (c->ev_join[k]) hipEventDestroy(c->ev_join[k]);
         if (c->ev_o0[k]) hipEventDestroy(c->ev_o0[k]);
-        c->sub[k] = nullptr; c->ev_join[k] = nullptr; c->ev_o0[k] = nullptr;
+        if (c->ev_down[k]) hipEventDestroy(c->ev_down[k]);
+        if (c->ev_top[k]) hipEventDestroy(c->ev_top[k]);
+        c->sub[k] = nullptr; c->ev_join[k] = nullptr; c->ev_o0[k] = nullptr; c->ev_down[k] = nullptr; c->ev_top[k] = nullptr;
     }
+    if (c->down) hipStreamDestroy(c->down);
+    c->down = nullptr;
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     c->ev_fork = nullptr;
     for (int k = 0; k < 2; ++k) {
@@ -312,7 +321,12 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         if (e != hipSuccess) return bail("stream", e);
         if ((e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
         if ((e = hipEventCreateWithFlags(&c->ev_o0[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
+        if ((e = hipEventCreateWithFlags(&c->ev_down[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
+        if ((e = hipEventCreateWithFlags(&c->ev_top[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
     }
+    // (the down stream at the lowest / highest priority, forked after octave 0: 1-3 % slower than at
+    // the default)
+    if ((e = hipStreamCreateWithFlags(&c->down, hipStreamNonBlocking)) != hipSuccess) return bail("stream", e);
     if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("event", e);
     for (int k = 0; k < 2; ++k) {
         if ((e = hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
@@ -468,6 +482,7 @@ static int finish(vo_ctx* c)
 {
     hipError_t e = hipStreamSynchronize(c->stream);
     for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipStreamSynchronize(c->sub[k]);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->down);
     if (e != hipSuccess) return fail(c, VO_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
     e = hipGetLastError();
     if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
@@ -971,29 +986,49 @@ static SetRef set_ref(vo_ctx* c, int set)
 // features of part k overlap the scale space of part k+1 (and of the next call, which uses
 // the other set).  Inputs are ordered after earlier work on `stream`; the set's previous
 // contents are released by its events (below).  With `join`, `stream` waits for the result.
-// The arrangement of one part:
+// The arrangement of one part (with `chains`; without, `down`'s work follows on sub[0]):
 //   sub[0]  waits for the set's arena (ev_arena: the previous call's last reader, k_desc -- not
-//           that call's whole feature stream, whose stereo match reads descriptors only); the
-//           scale space of the large octaves, ev_o0 once octave 0 is built, then the LDS-sized
-//           octaves (k_small_pyr) at its tail; ev_join.
+//           that call's whole feature stream, whose stereo match reads descriptors only);
+//           octave 0, ev_o0; octave 1's levels 1..L, ev_down, its levels L+1..L+2, ev_top (the
+//           top chain; with no large octave 1 the fork follows octave 0's level L).
+//   down    after ev_down (octave 1's level L has stored octave 2's base) the large octaves 2..
+//           with all their levels, then the LDS-sized octaves (k_small_pyr); ev_join.  Ordered
+//           behind sub[0]'s wait for the arena by ev_down.  One stream for both buffer sets: a call's
+//           fork already follows the previous call's top chain on sub[0], and with `stream`, the two
+//           forked streams and the copy stream of the pipelined loop a stream per set would be the
+//           process's sixth.
 //   sub[1]  after ev_o0 the extremum test of octave 0, beside the scale space of octaves 1..;
-//           after ev_join the extremum test of octaves 1.., the feature stages and the stereo
-//           match.
+//           after ev_top and ev_join (both chains) the extremum test of octaves 1.., the feature
+//           stages and the stereo match.  ev_arena and ev_done are recorded here, so they cover
+//           both chains: the set's next call, the batch's slot event of the pipelined loop and
+//           begin_call's quiesce wait for them as before.
+// Forking after octave 0's level L instead (octaves 1.. beside octave 0's two widest blurs), with or
+// without octave 1's top levels back on sub[0], and the down stream at another priority all measured
+// 1-3 % slower than one chain: ev_o0 fires 9 ms later and the feature stream becomes the critical one
+// (DESIGN.md §9j).
 // The extremum test of octaves 1.. at the scale space's tail instead (round 3's placement, then
 // 0.4 ms on the critical stream) measured 7.66-7.77 against 7.51-7.55 ms per 64-frame step and no
 // better since.  k_small_pyr (one 1024-thread workgroup per image, ~120 KB of
 // LDS: 0.13 ms isolated, ~1 ms in situ while it waits for a CU with that much free LDS) at the
-// head of the feature stream's part, or on a stream of its own, measured slower than waiting at
-// the tail.  Waiting for the set's ev_done (after the stereo match) instead of
-// ev_arena cost the full path 1.4 %.
+// head of the feature stream's part, or on a stream of its own behind the last level blur,
+// measured slower than waiting at the tail; on the down chain it follows octaves 2..
+// beside octave 1's top levels (0.5-0.7 instead of 1.4-2.1 ms in situ).  Waiting for the set's
+// ev_done (after the stereo match) instead of ev_arena cost the full path 1.4 %.
 static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uint8_t* d_r, int B, bool join,
-                               bool fork = true)
+                               bool chains, bool fork = true)
 {
     const size_t fs = (size_t)c->rows * c->cols;
     const int parts = std::min(c->n_sub, B);
     SetRef S = set_ref(c, set);
     hipStream_t sp = c->sub[0], st = c->sub[1];
-    if (fork) {                                                 // inputs / earlier work on `stream`
+    // (a synchronous profiled call -- bench.py's isolated pass -- keeps the scale space one chain
+    // and starts the features after all of it, so its per-kernel durations stay undisturbed)
+    const bool iso = c->prof.on && join;
+    // The pipelined loop body (chains = false) keeps one chain as well: its geometry stream and copy
+    // stream are busy beside the two forked ones, and with `down` as a fifth stream on four hardware
+    // queues the full path lost 4 %
+    const hipStream_t sd = (iso || !chains) ? sp : c->down;
+    if (fork) {                                               // inputs / earlier work on `stream`
         HIPC(c, hipEventRecord(c->ev_fork, c->stream));
         HIPC(c, hipStreamWaitEvent(sp, c->ev_fork, 0));
     }
@@ -1030,18 +1065,21 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
         }
         ImageSrc src{pl, pr, fs, c->cols, 0};
         SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
-        sift_enqueue_pyramid(c->py, v, src, 2 * nf, c->sp, sp, c->d_py, c->ev_o0[p]);
-        sift_enqueue_small(c->py, v, 2 * nf, sp, c->d_py);
-        HIPC(c, hipEventRecord(c->ev_join[p], sp));
+        ScaleChains ch;
+        ch.down = sd;
+        ch.ev_fork = c->ev_down[p];
+        sift_enqueue_pyramid(c->py, v, src, 2 * nf, c->sp, sp, c->d_py, c->ev_o0[p], ch);
+        HIPC(c, hipEventRecord(c->ev_top[p], sp));              // the top chain's end
+        sift_enqueue_small(c->py, v, 2 * nf, sd, c->d_py);
+        HIPC(c, hipEventRecord(c->ev_join[p], sd));
     }
     for (int p = 0; p < parts; ++p) {
         const int f0 = B * p / parts, nf = B * (p + 1) / parts - f0;
         SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
-        // (a synchronous profiled call -- bench.py's isolated pass -- starts it after the whole
-        // scale space, so its per-kernel durations stay undisturbed)
-        const bool iso = c->prof.on && join;
         HIPC(c, hipStreamWaitEvent(st, iso ? c->ev_join[p] : c->ev_o0[p], 0));
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 0, 1);
+        // the end of both chains (one chain gave both by ev_join alone)
+        HIPC(c, hipStreamWaitEvent(st, c->ev_top[p], 0));
         HIPC(c, hipStreamWaitEvent(st, c->ev_join[p], 0));
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 1, o_small);
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, o_small, c->py.n_oct);
@@ -1062,7 +1100,7 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
     const int set = c->next_set;
     c->next_set ^= 1;
     const bool sync = stats != nullptr;      // profiling events are collected by vo_kernel_times
-    int rc = enqueue_sift_stereo(c, set, d_lefts, d_rights, B, sync);
+    int rc = enqueue_sift_stereo(c, set, d_lefts, d_rights, B, sync, true);
     if (rc) return rc;
     c->last_B = B;
     if (!sync) {
@@ -1260,7 +1298,7 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     SetRef S = set_ref(c, set);
     for (const vo_ctx::Pending& q : c->pending)         // batch n-2 (same set), still in flight
         if (q.set == set) HIPC(c, hipStreamWaitEvent(c->sub[1], c->sh[q.slot].ev, 0));
-    int rc = enqueue_sift_stereo(c, set, d_l, d_r, B, true, fork);   // `stream` waits for this set's SIFT
+    int rc = enqueue_sift_stereo(c, set, d_l, d_r, B, true, false, fork);   // `stream` waits for this set's SIFT
     if (rc) return rc;
     StepArgs a = step_args(c, B, set);
     geom_enqueue(*S.gb, *S.mb, S.track_jobs, a, c->mp, c->stream);
@@ -1609,6 +1647,7 @@ int vo_reset(vo_ctx* c)
     // drops any pending asynchronous batches: wait for this context's streams only
     HIPC(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < vo_ctx::MAX_SUB; ++k) HIPC(c, hipStreamSynchronize(c->sub[k]));
+    HIPC(c, hipStreamSynchronize(c->down));
     HIPC(c, hipStreamSynchronize(c->copy_stream));
     c->pending.clear();
     c->next_step_set = 0;

@@ -175,8 +175,20 @@ void sift_enqueue(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_
 // and the feature stages (mask compaction, refinement, orientation, descriptors).  The batched
 // path runs the extremum test of octave 0 on the feature stream as soon as ev_o0 fires, beside
 // the scale space of octaves 1.., and the rest at the scale space's tail (vo_api.hip).
+// The scale space as two chains (batched path, sift.hip: sift_enqueue_pyramid): with `down`, the
+// octaves after the fork octave (1, or 0 when only octave 0 is a large one; a later one while the
+// next octave's blurs are still HBM-bound) run on `down` once
+// ev_fork -- recorded on s after the fork octave's level-L blur -- has fired, beside that octave's
+// levels L+1, L+2 on s.  The caller enqueues sift_enqueue_small on `down` and orders the extremum
+// test of octaves 1.. after the end of both s and `down`.  Streams and events belong to the caller;
+// none is created here.
+struct ScaleChains {
+    hipStream_t down = nullptr;         // nullptr (or s): one chain on s
+    hipEvent_t ev_fork = nullptr;
+};
 void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img,
-                          const vo_sift_params& p, hipStream_t s, const Pyramid* d_py, hipEvent_t ev_o0 = nullptr);
+                          const vo_sift_params& p, hipStream_t s, const Pyramid* d_py, hipEvent_t ev_o0 = nullptr,
+                          const ScaleChains& ch = ScaleChains());
 void sift_enqueue_pyramid_tail(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
                                const Pyramid* d_py, int ext_o_begin);
 void sift_enqueue_extrema(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
