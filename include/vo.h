@@ -15,6 +15,9 @@
  *   vo_set_distortion      the scale space of the loop-body entries
  *   vo_sift                detectSIFTFeatures + extractFeatures(...,"SIFT")
  *                          VO.m:79-84
+ *   vo_describe /          extractFeatures(I, points, "Method", "SIFT") at points the caller
+ *   vo_describe_batch      gives (VO.m:83-84 outside the fused path); vo_check_points is
+ *   vo_check_points        their host-side argument check
  *   vo_set_strongest       points = selectStrongest(points, N) between the two
  *                          (VO.m:140,206,217-218), in every entry that detects
  *   vo_match               matchFeatures(F1, F2)  VO.m:87,283,293,311,323
@@ -143,7 +146,7 @@ typedef struct {
     float   angle;       /* orientation in degrees [0,360) (OpenCV convention) */
     float   response;    /* |DoG| at the refined extremum (Metric) */
     int32_t octave;      /* octave index, -1 = upsampled */
-    int32_t layer;       /* layer within octave 1..n_octave_layers */
+    int32_t layer;       /* layer within octave 1..n_octave_layers (vo_describe takes 0..n_octave_layers + 2) */
     float   scale;       /* Scale = size / 2 in image pixels */
 } vo_keypoint;
 
@@ -177,6 +180,65 @@ int vo_sift(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld,
  * transpose on the host; the device transposes).  col_major = 0 is vo_sift. */
 int vo_sift_ex(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld, int col_major,
                vo_keypoint* kps, uint8_t* desc, int capacity, int* n_out);
+
+/* ---- extractFeatures at caller-given points ----------------------------- */
+/* features = extractFeatures(I, points, "Method", "SIFT") for points the caller chose: detections
+ * that were moved, rescaled or re-oriented, points of another detector, a grid, SIFTPoints built by
+ * hand (OpenCV's compute() on provided keypoints, in this library's conventions).
+ *
+ * Spec.  For a context with SIFT block p (L = n_octave_layers) and a point q, only x, y, scale,
+ * angle, octave and layer are read; size and response are ignored.
+ *   o       = q.octave + (p.upsample ? 1 : 0)          plane index, 0 <= o < n_octaves
+ *   oscale  = (float)(1 << o) * (p.upsample ? 0.5f : 1.0f)
+ *   loc_off = p.upsample ? 0.75f : 1.0f
+ *   xo = (q.x - loc_off) / oscale;  yo = (q.y - loc_off) / oscale;  scl = q.scale / oscale
+ *   desc = descriptor(G(o, q.layer), xo, yo, q.angle, scl)
+ * with descriptor() the arithmetic of the detecting entries, unchanged, on Gaussian level q.layer
+ * of octave o (the level vo_fetch_gaussian returns).  This is the exact inverse of the mapping
+ * vo_sift writes its keypoints with -- a power-of-two scaling and one rounding each way, and only
+ * round(xo), round(yo) and scl enter the descriptor -- so describing vo_sift's own keypoints
+ * reproduces vo_sift's descriptors (away from a .5 tie of xo or yo).
+ *
+ * Accepted points (anything else: VO_ERR_ARG naming the index of the first offending point,
+ * decided on the host before anything is enqueued):
+ *   - x, y, scale, angle finite, |x|, |y| < 2^20.  Points outside the image are legal: their
+ *     windows hold fewer samples or none, and a window without a sample gives 128 zeros;
+ *   - 0 <= angle <= 360;
+ *   - 0 <= o < vo_num_octaves(rows, cols, upsample) and 0 <= layer <= L + 2: every level of the
+ *     pyramid, not only the layers 1..L a detection has (SIFTPoints built by hand: layer 0);
+ *   - the uncapped window radius round(VO_SIFT_DESCR_SCL * scl * sqrt(2)f * (VO_SIFT_DESCR_W + 1)
+ *     * 0.5f) in 1 .. VO_SIFT_DESCR_RMAX = 127, about 0.1 <= scl <= 11.9.  The upper bound keeps
+ *     vo_spec.h's proof that the u32 fixed-point bins cannot overflow: it counts the samples of a
+ *     spatial bin from hist_width = 3 scl, which holds only while the cap at 127 does not bind.
+ *     Where the image diagonal caps the radius instead (octave planes with (int)sqrt(rows^2 +
+ *     cols^2) < 127) the plane has fewer than 8100 pixels and a bin cannot collect more samples
+ *     than that: 8100 * 361 * 2^10 < 2^32.
+ * n <= max_keypoints per image; beyond that VO_ERR_CAPACITY.
+ *
+ * vo_check_points is host-only and stateless (no context, no device): VO_OK, or VO_ERR_ARG with
+ * *first_bad (may be NULL) = index of the first point that breaks a rule above; a NULL p or pts
+ * (with n > 0), n < 0 or rows/cols < 1 give VO_ERR_ARG with *first_bad = -1. */
+int vo_check_points(const vo_sift_params* p, int rows, int cols, const vo_keypoint* pts, int n, int* first_bad);
+/* One image (host buffers, image conventions of vo_sift_ex): desc[n][128], row i for point i in
+ * the caller's order.  n = 0 is legal and launches nothing (the context stays as it was).
+ * The scale space runs as for vo_sift; no detection stage runs (no extremum test, refinement,
+ * orientation, selection); the points become descriptor records on the device and one descriptor
+ * launch sized for any accepted scale describes them.  vo_set_strongest and vo_set_distortion do
+ * not apply (the points are already chosen; like vo_sift this replaces one toolbox call).  Refused
+ * (VO_ERR_STATE) while step batches are pending; the loop state (features, pose, landmarks) is
+ * untouched.  Afterwards vo_fetch_gaussian reads this call's scale space, while vo_fetch_keypoints,
+ * vo_fetch_stereo_pairs, vo_fetch_candidate_counts and vo_fetch_detected_count -- results of a
+ * detecting call -- return VO_ERR_STATE until the next call that detects. */
+int vo_describe(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld, int col_major,
+                const vo_keypoint* pts, int n, uint8_t* desc);
+/* The same for n_img images (1 .. 2 x max_batch) of the context's size laid out as vo_step_batch_ex
+ * lays out frames (row-major: image i at imgs + i * rows * ld; col_major: at imgs + i * ld * cols).
+ * Image i's points are pts + i * pts_stride, n_pts[i] <= pts_stride of them, its descriptors
+ * desc + i * pts_stride * 128; rows beyond n_pts[i] are left untouched.  (VO.m:83-84 describes a
+ * left and a right image: two images with their own counts.)  A refused point is reported as
+ * "image i point k" in vo_last_error. */
+int vo_describe_batch(vo_ctx* ctx, const uint8_t* imgs, int ld, int col_major, int n_img,
+                      const vo_keypoint* pts, const int32_t* n_pts, int pts_stride, uint8_t* desc);
 
 /* ---- undistortImage (VO.m:75-76) --------------------------------------- */
 /* One camera's cameraIntrinsics: Brown-Conrady radial + tangential distortion.  The arithmetic
@@ -418,7 +480,10 @@ int vo_sift_match_batch_dev(vo_ctx* ctx, const uint8_t* d_lefts, const uint8_t* 
 
 /* Device-side results of the last batched call, for parity tests:
  * keypoints and descriptors of image i (2*frame + side) and stereo pairs of
- * a frame.  Host output buffers. */
+ * a frame.  Host output buffers.  After vo_describe / vo_describe_batch, which detect nothing,
+ * vo_fetch_keypoints, vo_fetch_stereo_pairs, vo_fetch_candidate_counts and vo_fetch_detected_count
+ * return VO_ERR_STATE until the next detecting call; vo_fetch_gaussian reads the describe call's
+ * scale space. */
 int vo_fetch_keypoints(vo_ctx* ctx, int image, vo_keypoint* kps, uint8_t* desc, int capacity, int* n);
 int vo_fetch_stereo_pairs(vo_ctx* ctx, int frame, uint32_t* pairs, int capacity, int* n);
 /* Extremum candidates of image i in the last batched call (uncapped: above 4 x max_keypoints

@@ -21,6 +21,9 @@
  *        every context they create (vo_set_strongest); 0 = off
  *   [loc, scale, ori, metric, desc, octave, layer] = vo_mex('sift', I)
  *        detectSIFTFeatures + extractFeatures(..,"Method","SIFT")        VO.m:79-84
+ *   desc = vo_mex('describe', I, loc, scale, ori, octave, layer)
+ *        extractFeatures(I, points, "Method", "SIFT") at caller-given points (vo_describe): the
+ *        SIFTPoints properties Location, Scale, Orientation (radians), Octave, Layer
  *   [indexPairs, matchMetric] = vo_mex('match', F1, F2, name, value, ...)
  *        matchFeatures(F1, F2)                                   VO.m:87,283,293,311,323
  *        and its options 'Unique', 'MatchThreshold', 'MaxRatio' (names case-insensitive; 'Method',
@@ -226,6 +229,78 @@ static void cmd_sift(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
         plhs[6] = mxCreateNumericMatrix(n, 1, mxINT32_CLASS, mxREAL);   /* Layer */
         for (int i = 0; i < n; ++i) mxGetInt32s(plhs[6])[i] = kp[i].layer;
     }
+    mxFree(kp);
+    mxFree(d);
+}
+
+/* vo_describe through a weak reference as well: without it 'describe' raises
+ * vo:extractFeatures:unavailable */
+extern __typeof__(vo_describe) vo_describe __attribute__((weak));
+
+/* n x 1 int32 or double column -> int32 values (SIFTPoints.Octave / .Layer are int32) */
+static int32_t* column_i32(const mxArray* a, int n, const char* what)
+{
+    if ((mxGetClassID(a) != mxINT32_CLASS && !mxIsDouble(a)) || mxIsComplex(a) || mxGetNumberOfDimensions(a) != 2 ||
+        (int)mxGetM(a) != n || ((int)mxGetN(a) != 1 && n > 0))
+        mexErrMsgIdAndTxt("vo:badArgument", "%s must be an N x 1 int32 or double column", what);
+    int32_t* v = (int32_t*)mxMalloc(sizeof(int32_t) * ((size_t)n + 1));
+    for (int i = 0; i < n; ++i) {
+        if (mxIsDouble(a)) {
+            const double d = mxGetDoubles(a)[i];
+            if (!(d >= -2147483648.0 && d <= 2147483647.0) || d != (double)(int32_t)d) {
+                mxFree(v);
+                mexErrMsgIdAndTxt("vo:badArgument", "%s must hold integers", what);
+            }
+            v[i] = (int32_t)d;
+        } else {
+            v[i] = mxGetInt32s(a)[i];
+        }
+    }
+    return v;
+}
+
+/* desc = vo_mex('describe', I, loc, scale, ori, octave, layer): extractFeatures(I, points, "Method",
+ * "SIFT") at caller-given points -- loc N x 2 [x y] 1-based, scale N x 1, ori N x 1 in radians as
+ * SIFTPoints.Orientation (libvo takes degrees: (float)((double)ori * (180 / pi))), octave and layer
+ * N x 1 -> N x 128 single, row i for point i.  vo_describe checks the values (vo:badArgument names
+ * the first offending point). */
+static void cmd_describe(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    (void)nlhs;
+    need_args(nrhs, 7, "describe");
+    const mxArray* I = prhs[1];
+    need_real(I, mxUINT8_CLASS, -1, -1, "I");
+    if (!vo_describe)
+        mexErrMsgIdAndTxt("vo:extractFeatures:unavailable", "this libvo has no vo_describe: it describes only the points its own "
+                          "detectSIFTFeatures returned; link a newer libvo");
+    int n = 0, ns = 0, no = 0;
+    float* loc = points_f32(prhs[2], 2, &n, "points.Location");
+    float* scale = points_f32(prhs[3], 1, &ns, "points.Scale");
+    float* ori = points_f32(prhs[4], 1, &no, "points.Orientation");
+    if (ns != n || no != n) {
+        mxFree(loc); mxFree(scale); mxFree(ori);
+        mexErrMsgIdAndTxt("vo:badArgument", "Location, Scale and Orientation differ in length");
+    }
+    int32_t* octave = column_i32(prhs[5], n, "points.Octave");
+    int32_t* layer = column_i32(prhs[6], n, "points.Layer");
+    const int rows = (int)mxGetM(I), cols = (int)mxGetN(I);
+    vo_keypoint* kp = (vo_keypoint*)mxMalloc(sizeof(vo_keypoint) * ((size_t)n + 1));
+    for (int i = 0; i < n; ++i) {
+        kp[i].x = loc[2 * i]; kp[i].y = loc[2 * i + 1];
+        kp[i].scale = scale[i]; kp[i].size = scale[i] * 2.0f;
+        kp[i].angle = (float)((double)ori[i] * (180.0 / 3.14159265358979323846));
+        kp[i].response = 0.0f;
+        kp[i].octave = octave[i]; kp[i].layer = layer[i];
+    }
+    mxFree(loc); mxFree(scale); mxFree(ori); mxFree(octave); mxFree(layer);
+    uint8_t* d = (uint8_t*)mxMalloc((size_t)(n + 1) * VO_DESC_LEN);
+    need_ctx(rows, cols);
+    const int rc = vo_describe(g_ctx, mxGetUint8s(I), rows, cols, rows, 1, kp, n, d);
+    if (rc != VO_OK) { mxFree(kp); mxFree(d); check(rc); }
+    plhs[0] = mxCreateNumericMatrix(n, VO_DESC_LEN, mxSINGLE_CLASS, mxREAL);
+    float* D = n ? mxGetSingles(plhs[0]) : NULL;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < VO_DESC_LEN; ++k) D[(size_t)k * n + i] = (float)d[(size_t)i * VO_DESC_LEN + k];
     mxFree(kp);
     mxFree(d);
 }
@@ -567,6 +642,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], cmd, sizeof cmd))
         mexErrMsgIdAndTxt("vo:nargin", "vo_mex(command, ...): first argument must be a command string");
     if (!strcmp(cmd, "sift")) cmd_sift(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "describe")) cmd_describe(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "undistort")) cmd_undistort(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "distortion")) cmd_distortion(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "strongest")) cmd_strongest(nlhs, plhs, nrhs, prhs);

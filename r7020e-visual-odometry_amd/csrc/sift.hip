@@ -1922,6 +1922,32 @@ __global__ void k_expand(const CandOut* __restrict__ cout, const int* __restrict
     }
 }
 
+// vo_describe: the descriptor records of caller-given points, one thread per point over the flat
+// work list (per-image counts n_kp, rows kp[img][k]) -- k_expand's mapping inverted (vo.h: "Spec").
+// The host has checked every point (vo_check_points): 0 <= o < n_oct, so the shift is defined, and
+// the divisions are by a power of two (exact up to the one rounding of q.x - loc_off).
+__global__ __launch_bounds__(256) void k_points(const vo_keypoint* __restrict__ kp, const int* __restrict__ n_kp,
+                                                KpInt* __restrict__ kpi, int kp_cap, int n_img, int upsample)
+{
+    __shared__ int fpre[VO_FLAT_MAX_IMG + 1];
+    const long total = flat_setup(n_kp, kp_cap, n_img, fpre);
+    for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        int img, k;
+        flat_find(fpre, n_img, t, img, k);
+        const vo_keypoint q = kp[(size_t)img * kp_cap + k];
+        const int o = q.octave + (upsample ? 1 : 0);
+        const float oscale = (float)(1 << o) * (upsample ? 0.5f : 1.0f);
+        const float loc_off = upsample ? 0.75f : 1.0f;
+        KpInt qi;
+        qi.xo = (q.x - loc_off) / oscale;
+        qi.yo = (q.y - loc_off) / oscale;
+        qi.scl = q.scale / oscale;
+        qi.angle = q.angle;
+        qi.o = o; qi.layer = q.layer; qi.pad0 = 0; qi.pad1 = 0;
+        kpi[(size_t)img * kp_cap + k] = qi;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // descriptor: one wave (block of 64) per keypoint
 // ---------------------------------------------------------------------------
@@ -1976,7 +2002,9 @@ __device__ __forceinline__ void desc_tables(const Pyramid* __restrict__ py, KpIn
     int radius = vo_round(hist_width * 1.4142135623730951f * (float)(DW + 1) * 0.5f);
     if (radius > g.dmax) radius = g.dmax;
     if (radius > VO_SIFT_DESCR_RMAX) radius = VO_SIFT_DESCR_RMAX;
-    radius = min(radius, dcap);                 // (never binds: dcap bounds every refined scale)
+    // (never binds: dcap bounds every refined scale of the detecting launch, and the launch for
+    // caller-given points, k_desc_pts, passes VO_SIFT_DESCR_RMAX itself)
+    radius = min(radius, dcap);
     cos_t = cos_t / hist_width;
     sin_t = sin_t / hist_width;
     {
@@ -2059,7 +2087,7 @@ __device__ __forceinline__ void desc_tables(const Pyramid* __restrict__ py, KpIn
 
 // The descriptor of one keypoint by the whole wave (k_desc's body): window tables, sample loop, histogram fold, normalisation, u8 quantisation;
 // writes dst[0..128) and *mdst.  hfx: DCOPIES * DCS words of LDS; dyn: dt_stride(dcap) words.
-template <int DCOPIES>
+template <int DCOPIES, bool ANYPOS = false>
 __device__ __forceinline__ void desc_keypoint(const Pyramid* __restrict__ py, const float* __restrict__ arena, const KpInt q,
                                               int img, int dcap, uint32_t* hfx, uint32_t* dyn, uint8_t* dst, DescMeta* mdst)
 {
@@ -2122,7 +2150,10 @@ __device__ __forceinline__ void desc_keypoint(const Pyramid* __restrict__ py, co
     // row y+1 +8P + 4 B -- no 64-bit address arithmetic per sample; the row offset is a
     // 24-bit multiply (|i| <= RMAX, P < 2^23)
     const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void*)(gim - P - 1), 0, 0x7FFFFFF0, 0x00020000);
-    const int c_off = pyy * P + px;                  // wave-uniform
+    // wave-uniform.  ANYPOS (k_desc_pts): formed in unsigned arithmetic -- a caller-given point may lie
+    // up to 2^21 octave pixels outside the plane, where the product leaves 32 bits; its window then has
+    // no sample and c_off is never used, and with a sample (px, pyy) is within a radius of the plane.
+    const int c_off = ANYPOS ? (int)((uint32_t)pyy * (uint32_t)P + (uint32_t)px) : pyy * P + px;
     auto grad_loads = [&](int i, int j, float* g4) {
         const int vo = 4 * (c_off + __mul24(i, P) + j);
         typedef int i3_t __attribute__((ext_vector_type(3)));
@@ -2263,6 +2294,34 @@ __global__ __launch_bounds__(64, VO_DESC_WAVES) void k_desc(const Pyramid* __res
         const KpInt q = kpi[(size_t)img * kp_cap + k];
         desc_keypoint<DCOPIES>(py, arena, q, img, dcap, hfx, dyn, desc + ((size_t)img * kp_cap + k) * VO_DESC_LEN,
                                meta + (size_t)img * kp_cap + k);
+    }
+}
+
+// k_desc for caller-given points (vo_describe): the same per-keypoint code with the table capacity
+// VO_SIFT_DESCR_RMAX, a compile-time constant here, in place of the pyramid's dcap -- a caller may
+// pass any scale whose window radius is at most 127, far above what a refined scale reaches, and
+// desc_tables' min(radius, dcap) would otherwise change such a descriptor.  dt_stride(127) = 404
+// words (1.6 KB) of dynamic LDS beside the 5.2 KB of histogram copies: 6.8 KB + the image prefix
+// per one-wave workgroup, so the 20 waves per CU of the register budget still fit the CU's 160 KB
+// (up to ~290 images; a larger batch's prefix, 4 KB at 1024 images, leaves 14).
+template <int DCOPIES>
+__global__ __launch_bounds__(64, VO_DESC_WAVES) void k_desc_pts(const Pyramid* __restrict__ py, const float* __restrict__ arena,
+                                                 const KpInt* __restrict__ kpi, const int* __restrict__ n_kp,
+                                                 uint8_t* __restrict__ desc,
+                                                 DescMeta* __restrict__ meta, int kp_cap, int n_img)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hfx[DCOPIES * DCS];
+    extern __shared__ uint32_t dyn[];
+    constexpr int dcap = VO_SIFT_DESCR_RMAX;
+    const int ts = dt_stride(dcap);
+    int* const fpre = reinterpret_cast<int*>(dyn + ts);
+    const long total = flat_setup(n_kp, kp_cap, n_img, fpre);
+    for (long t = blockIdx.x; t < total; t += gridDim.x) {
+        int img, k;
+        flat_find_wave(fpre, n_img, t, img, k);
+        const KpInt q = kpi[(size_t)img * kp_cap + k];
+        desc_keypoint<DCOPIES, true>(py, arena, q, img, dcap, hfx, dyn, desc + ((size_t)img * kp_cap + k) * VO_DESC_LEN,
+                                     meta + (size_t)img * kp_cap + k);
     }
 }
 
@@ -2608,6 +2667,22 @@ void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const v
     // the blurs gain 3 ms in situ, k_desc loses 3-11 ms, profiles/r06_t_ab_desc_lds_pad.txt)
     VO_LAUNCH_NAMED("k_desc", (k_desc<VO_DESC_COPIES>), dim3(kFeatureGrid), dim3(64), dt_bytes + fpre_bytes, s, d_py, A,
                     b.kpi, b.n_kp, b.desc, b.meta, b.kp_cap, n_img);
+}
+
+void sift_enqueue_describe(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img, int n_points,
+                           const vo_sift_params& p, hipStream_t s, const Pyramid* d_py)
+{
+    // the scale space as sift_enqueue builds it, without the extremum test at its tail
+    sift_enqueue_pyramid(py, b, src, n_img, p, s, d_py);
+    sift_enqueue_small(py, b, n_img, s, d_py);
+    if (n_points <= 0) return;
+    VO_LAUNCH(k_points, dim3(std::min(256, (n_points + 255) / 256)), dim3(256), 0, s, b.kp, b.n_kp, b.kpi, b.kp_cap, n_img,
+              p.upsample);
+    const size_t fpre_bytes = sizeof(int) * (size_t)(n_img + 1);
+    const size_t dt_bytes = sizeof(uint32_t) * (size_t)dt_stride(VO_SIFT_DESCR_RMAX);
+    // one workgroup per point up to the detecting launch's grid (grid-stride beyond it)
+    VO_LAUNCH_NAMED("k_desc_pts", (k_desc_pts<VO_DESC_COPIES>), dim3(std::min(kFeatureGrid, n_points)), dim3(64),
+                    dt_bytes + fpre_bytes, s, d_py, b.arena, b.kpi, b.n_kp, b.desc, b.meta, b.kp_cap, n_img);
 }
 
 void sift_enqueue(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img, const vo_sift_params& p,

@@ -118,6 +118,9 @@ struct vo_ctx {
     // ran with it, so its n_det holds the detected counts (otherwise n_kp does)
     int strongest = 0;
     bool sel_used[2] = {false, false};
+    // the last SIFT call was vo_describe / vo_describe_batch: set 0 holds a scale space and the
+    // caller's points, no detections, so the fetches of a detecting call's results are refused
+    bool described = false;
     // vo_match staging
     uint8_t* d_fd[2] = {nullptr, nullptr};
     DescMeta* d_fm[2] = {nullptr, nullptr};
@@ -566,6 +569,7 @@ int vo_sift_ex(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int co
     sift_enqueue(c->py, c->sb, src, 1, c->sp, c->stream, c->d_py, c->strongest);
     c->last_set = 0;                                   // vo_fetch_* now read this result (set 0)
     c->sel_used[0] = c->strongest > 0;
+    c->described = false;
     int n = 0, n_cand = 0, n_det = -1;
     HIPC(c, hipMemcpyAsync(&n, c->sb.n_kp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (c->strongest > 0) HIPC(c, hipMemcpyAsync(&n_det, c->sb.n_det, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -592,6 +596,111 @@ int vo_sift(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, vo_keypoi
             int* n_out)
 {
     return vo_sift_ex(c, img, rows, cols, ld, 0, kps, desc, capacity, n_out);
+}
+
+// ---- extractFeatures at caller-given points (vo.h: "Spec") -----------------------------------
+// nullptr when q is a point vo_describe accepts, else the rule it breaks.  Host arithmetic only; the
+// radius is desc_tables' own float expression (this file is compiled with -ffp-contract=off too),
+// compared as a float so that no scale overflows the conversion.
+static const char* point_refusal(const vo_sift_params& p, int n_oct, const vo_keypoint& q)
+{
+    if (!std::isfinite(q.x) || !std::isfinite(q.y) || !std::isfinite(q.scale) || !std::isfinite(q.angle))
+        return "x, y, scale and angle must be finite";
+    if (!(std::fabs(q.x) < 1048576.0f) || !(std::fabs(q.y) < 1048576.0f)) return "|x|, |y| must be below 2^20";
+    if (!(q.angle >= 0.0f && q.angle <= 360.0f)) return "angle outside [0, 360]";
+    const int up = p.upsample ? 1 : 0;
+    if (q.octave < -up || q.octave >= n_oct - up) return "octave outside the pyramid";
+    if (q.layer < 0 || q.layer > p.n_octave_layers + 2) return "layer outside 0 .. n_octave_layers + 2";
+    const float oscale = (float)(1 << (q.octave + up)) * (up ? 0.5f : 1.0f);
+    const float scl = q.scale / oscale;
+    const float hist_width = VO_SIFT_DESCR_SCL * scl;
+    const float r = rintf(hist_width * 1.4142135623730951f * (float)(VO_SIFT_DESCR_W + 1) * 0.5f);
+    if (!(r >= 1.0f && r <= (float)VO_SIFT_DESCR_RMAX)) return "scale gives a descriptor window radius outside 1 .. 127";
+    return nullptr;
+}
+
+int vo_check_points(const vo_sift_params* p, int rows, int cols, const vo_keypoint* pts, int n, int* first_bad)
+{
+    if (first_bad) *first_bad = -1;
+    if (!p || rows < 1 || cols < 1 || n < 0 || (n > 0 && !pts) || p->n_octave_layers < 1 || p->n_octave_layers > 5)
+        return VO_ERR_ARG;
+    const int n_oct = vo_num_octaves(rows, cols, p->upsample);
+    for (int i = 0; i < n; ++i)
+        if (point_refusal(*p, n_oct, pts[i])) {
+            if (first_bad) *first_bad = i;
+            return VO_ERR_ARG;
+        }
+    return VO_OK;
+}
+
+int vo_describe_batch(vo_ctx* c, const uint8_t* imgs, int ld, int col_major, int n_img, const vo_keypoint* pts,
+                      const int32_t* n_pts, int pts_stride, uint8_t* desc)
+{
+    if (!c || !imgs || !n_pts || n_img < 1 || n_img > 2 * c->max_batch || pts_stride < 0 ||
+        (col_major != 0 && col_major != 1) || ld < (col_major ? c->rows : c->cols))
+        return fail(c, VO_ERR_ARG, "vo_describe: bad arguments");
+    // every refusal before anything is enqueued
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    const int K = c->sb.kp_cap;
+    long total = 0;
+    int max_n = 0;
+    for (int i = 0; i < n_img; ++i) {
+        if (n_pts[i] < 0 || n_pts[i] > pts_stride)
+            return fail(c, VO_ERR_ARG, "vo_describe: image %d has %d points, outside 0 .. pts_stride = %d", i, n_pts[i], pts_stride);
+        if (n_pts[i] > K)
+            return fail(c, VO_ERR_CAPACITY, "vo_describe: image %d has %d points, more than max_keypoints %d", i, n_pts[i], K);
+        total += n_pts[i];
+        max_n = std::max(max_n, n_pts[i]);
+    }
+    if (total > 0 && (!pts || !desc)) return fail(c, VO_ERR_ARG, "vo_describe: bad arguments");
+    for (int i = 0; i < n_img; ++i)
+        for (int k = 0; k < n_pts[i]; ++k) {
+            const char* why = point_refusal(c->sp, c->py.n_oct, pts[(size_t)i * pts_stride + k]);
+            if (why) return fail(c, VO_ERR_ARG, "vo_describe: image %d point %d: %s", i, k, why);
+        }
+    if (total == 0) return VO_OK;                      // nothing to describe: nothing is launched
+    BEGIN_CALL(c);
+    // tightly packed row-major images are one contiguous block: one copy (a 2-D copy of a pageable
+    // buffer goes row by row -- 1.4 s for 512 images of 375 x 1242, profiles/describe_times.txt)
+    if (!col_major && ld == c->cols) {
+        HIPC(c, hipMemcpyAsync(c->d_img, imgs, (size_t)c->rows * c->cols * n_img, hipMemcpyHostToDevice, c->stream));
+    } else {
+        int rc = stage_images(c, imgs, ld, col_major, n_img, c->d_img);
+        if (rc) return rc;
+    }
+    // the points and their counts into the keypoint rows the detecting entries write (set 0)
+    HIPC(c, hipMemcpy2DAsync(c->sb.kp, sizeof(vo_keypoint) * K, pts, sizeof(vo_keypoint) * pts_stride,
+                             sizeof(vo_keypoint) * max_n, n_img, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->sb.n_kp, n_pts, sizeof(int) * n_img, hipMemcpyHostToDevice, c->stream));
+    // consecutive images: slot i = (i & 1 ? right : left) + (i >> 1) * frame_stride
+    const size_t fs = (size_t)c->rows * c->cols;
+    ImageSrc src{c->d_img, c->d_img + fs, 2 * fs, c->cols, 0};
+    sift_enqueue_describe(c->py, c->sb, src, n_img, (int)std::min<long>(total, INT_MAX), c->sp, c->stream, c->d_py);
+    c->last_set = 0;                                   // vo_fetch_gaussian now reads this scale space (set 0)
+    c->sel_used[0] = false;
+    c->described = true;                               // ... and the fetches of a detecting call have nothing to read
+    // row i of image k for point i: full rows-of-stride copies where every image fills its stride
+    // (one image always does), else image by image, leaving the rows beyond n_pts[i] untouched
+    bool full = true;
+    for (int i = 0; i < n_img; ++i) full = full && n_pts[i] == pts_stride;
+    if (full) {
+        HIPC(c, hipMemcpy2DAsync(desc, (size_t)pts_stride * VO_DESC_LEN, c->sb.desc, (size_t)K * VO_DESC_LEN,
+                                 (size_t)pts_stride * VO_DESC_LEN, n_img, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        for (int i = 0; i < n_img; ++i)
+            if (n_pts[i] > 0)
+                HIPC(c, hipMemcpyAsync(desc + (size_t)i * pts_stride * VO_DESC_LEN, c->sb.desc + (size_t)i * K * VO_DESC_LEN,
+                                       (size_t)n_pts[i] * VO_DESC_LEN, hipMemcpyDeviceToHost, c->stream));
+    }
+    return finish(c);
+}
+
+int vo_describe(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int col_major, const vo_keypoint* pts, int n,
+                uint8_t* desc)
+{
+    if (!c || rows != c->rows || cols != c->cols || n < 0) return fail(c, VO_ERR_ARG, "vo_describe: bad arguments");
+    const int32_t cnt = n;
+    return vo_describe_batch(c, img, ld, col_major, 1, pts, &cnt, n, desc);
 }
 
 // ---- undistortImage (VO.m:75-76) -------------------------------------------------------------
@@ -722,6 +831,7 @@ int vo_set_strongest(vo_ctx* c, int n)
 int vo_fetch_detected_count(vo_ctx* c, int image, int* n_detected)
 {
     if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_detected_count: bad image");
+    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_detected_count: the last call described given points and detected nothing");
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
@@ -1090,6 +1200,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
     HIPC(c, hipEventRecord(c->ev_done[set], st));
     if (join) HIPC(c, hipStreamWaitEvent(c->stream, c->ev_done[set], 0));
     c->last_set = set;
+    c->described = false;
     return VO_OK;
 }
 
@@ -1133,6 +1244,7 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
 int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, int capacity, int* n)
 {
     if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_keypoints: bad image");
+    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_keypoints: the last call described given points and detected nothing");
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
@@ -1152,6 +1264,7 @@ int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, in
 int vo_fetch_candidate_counts(vo_ctx* c, int image, int* n_cand, int* n_accepted)
 {
     if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_candidate_counts: bad image");
+    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_candidate_counts: the last call described given points and detected nothing");
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
@@ -1187,6 +1300,7 @@ int vo_fetch_gaussian(vo_ctx* c, int image, int octave, int level, float* out, i
 int vo_fetch_stereo_pairs(vo_ctx* c, int frame, uint32_t* pairs, int capacity, int* n)
 {
     if (!c || frame < 0 || frame >= c->max_batch) return fail(c, VO_ERR_ARG, "vo_fetch_stereo_pairs: bad frame");
+    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_stereo_pairs: the last call described given points and detected nothing");
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));

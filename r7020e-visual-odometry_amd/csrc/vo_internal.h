@@ -199,6 +199,14 @@ void sift_enqueue_small(const Pyramid& py, SiftBuffers& b, int n_img, hipStream_
 void sift_enqueue_features(const Pyramid& py, SiftBuffers& b, int n_img, const vo_sift_params& p, hipStream_t s,
                            const Pyramid* d_py, int strongest = 0);
 
+// vo_describe: the scale space of n_img images (one chain on s, no extremum test), then the
+// descriptors of caller-given points: b.kp holds the points' vo_keypoint rows [img][kp_cap] and
+// b.n_kp their per-image counts (uploaded on s before the call; n_points = their sum, checked by
+// the host against vo_check_points' rules); k_points writes b.kpi from them and k_desc_pts -- the
+// descriptor code with window tables of capacity VO_SIFT_DESCR_RMAX -- b.desc and b.meta.
+void sift_enqueue_describe(const Pyramid& py, SiftBuffers& b, const ImageSrc& src, int n_img, int n_points,
+                           const vo_sift_params& p, hipStream_t s, const Pyramid* d_py);
+
 // ---------------------------------------------------------------------------
 // undistortImage (undistort.hip): k_undistort remaps B frames of one or two cameras in one
 // launch.  Side k reads frame f at in + f * in_stride and writes it at out + f * out_stride, both

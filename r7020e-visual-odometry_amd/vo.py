@@ -109,6 +109,7 @@ EXPORTS = [
     "vo_fetch_candidate_counts", "vo_default_match_opts", "vo_match_ex", "vo_match_f32_ex",
     "vo_undistort", "vo_undistort_batch_dev", "vo_set_distortion", "vo_fetch_rectified",
     "vo_set_strongest", "vo_fetch_detected_count",
+    "vo_check_points", "vo_describe", "vo_describe_batch",
 ]
 
 # the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the eager MSAC kernels kept
@@ -167,6 +168,11 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_fetch_rectified.argtypes = [vp, C.c_int, P(C.c_uint8), C.c_int]
     L.vo_set_strongest.argtypes = [vp, C.c_int]
     L.vo_fetch_detected_count.argtypes = [vp, C.c_int, P(C.c_int)]
+    if hasattr(L, "vo_describe"):        # (absent from an older library timed beside this one: tools/describe_times.py)
+        L.vo_check_points.argtypes = [P(SiftParams), C.c_int, C.c_int, P(Keypoint), C.c_int, P(C.c_int)]
+        L.vo_describe.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(Keypoint), C.c_int, P(C.c_uint8)]
+        L.vo_describe_batch.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(Keypoint), P(C.c_int32), C.c_int,
+                                        P(C.c_uint8)]
     L.vo_track.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int,
                            P(C.c_uint32), C.c_int, P(C.c_int)]
     L.vo_triangulate.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double)]
@@ -282,6 +288,53 @@ def distortion_from_kitti(K, dist) -> Distortion:
     return distortion_from(K, (k[0], k[1], k[4]), (k[2], k[3]))
 
 
+def as_keypoints(points) -> np.ndarray:
+    """A point set as a contiguous KP_DTYPE array (vo_keypoint rows), the form Context.describe
+    takes.  Accepted: a KP_DTYPE array (what sift / detectSIFTFeatures return, or any edit of one),
+    or a structured array / mapping of equal-length columns with at least x, y and scale; angle
+    (degrees), octave and layer default to 0 -- SIFTPoints built by hand: base octave, level 0 --
+    and size to 2 * scale.  Anything else raises VOError(VO_ERR_ARG); the values themselves are
+    checked by the library (check_points)."""
+    if isinstance(points, np.ndarray) and points.dtype == KP_DTYPE:
+        if points.ndim != 1:
+            raise VOError(VO_ERR_ARG, "points: a 1-D keypoint array")
+        return np.ascontiguousarray(points)
+    if isinstance(points, np.ndarray) and points.dtype.names:
+        cols = {k: points[k] for k in points.dtype.names}
+    elif isinstance(points, dict):
+        cols = points
+    else:
+        raise VOError(VO_ERR_ARG, "points: a keypoint array (vo.KP_DTYPE) or columns x, y, scale[, angle, octave, layer]")
+    missing = [k for k in ("x", "y", "scale") if k not in cols]
+    unknown = [k for k in cols if k not in KP_DTYPE.names]
+    if missing or unknown:
+        raise VOError(VO_ERR_ARG, f"points: missing columns {missing}, unknown columns {unknown}")
+    n = len(np.atleast_1d(cols["x"]))
+    out = np.zeros(n, KP_DTYPE)
+    for k, v in cols.items():
+        v = np.atleast_1d(np.asarray(v))
+        if v.shape != (n,):
+            raise VOError(VO_ERR_ARG, f"points: column {k} has shape {v.shape}, not ({n},)")
+        out[k] = v
+    if "size" not in cols:
+        out["size"] = out["scale"] * np.float32(2)
+    return out
+
+
+def check_points(points, rows: int, cols: int, sift: SiftParams | None = None) -> int:
+    """vo_check_points (host only, no device): -1 when every point is one vo_describe accepts on a
+    rows x cols image under SIFT block `sift` (default: the defaults), else the index of the first
+    point that is not."""
+    pts = as_keypoints(points)
+    p = sift or default_sift_params()
+    bad = C.c_int(-1)
+    rc = load_library().vo_check_points(C.byref(p), rows, cols, pts.ctypes.data_as(C.POINTER(Keypoint)), len(pts),
+                                        C.byref(bad))
+    if rc != VO_OK and bad.value < 0:
+        raise VOError(rc, "vo_check_points: bad arguments")
+    return bad.value
+
+
 class Context:
     """One libvo context (one HIP device, fixed image size, up to max_batch frames per call)."""
 
@@ -338,6 +391,46 @@ class Context:
         self._check(self.lib.vo_sift_ex(self.h, _p(img, C.c_uint8), img.shape[0], img.shape[1], ld, col_major,
                                         kps.ctypes.data_as(C.POINTER(Keypoint)), _p(desc, C.c_uint8), cap, C.byref(n)))
         return kps[: n.value].copy(), desc[: n.value].copy()
+
+    # ---- extractFeatures at given points ----
+    def describe(self, img: np.ndarray, points) -> np.ndarray:
+        """SIFT descriptors [len(points), 128] uint8 of caller-given points on `img` (vo_describe),
+        row i for point i.  points: see as_keypoints; x, y, scale, angle, octave and layer are read
+        (the rules are vo_check_points')."""
+        img = np.asarray(img, np.uint8)
+        if img.ndim != 2:
+            raise VOError(VO_ERR_ARG, "describe: a 2-D uint8 image")
+        pts = as_keypoints(points)
+        rows, cols = img.shape
+        if rows > 1 and img.strides[0] == 1 and img.strides[1] >= rows:
+            col_major, ld = 1, img.strides[1]
+        elif img.strides[1] == 1 and img.strides[0] >= cols:
+            col_major, ld = 0, img.strides[0]
+        else:
+            img = np.ascontiguousarray(img)
+            col_major, ld = 0, cols
+        desc = np.zeros((len(pts), 128), np.uint8)
+        self._check(self.lib.vo_describe(self.h, _p(img, C.c_uint8), rows, cols, ld, col_major,
+                                         pts.ctypes.data_as(C.POINTER(Keypoint)), len(pts), _p(desc, C.c_uint8)))
+        return desc
+
+    def describe_batch(self, imgs: np.ndarray, points_list) -> list:
+        """vo_describe_batch: imgs [n_img, rows, cols] (1 .. 2 * max_batch images), points_list one
+        point set per image (their counts may differ, 0 included) -> a list of [n_i, 128] uint8."""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        if imgs.ndim != 3 or len(points_list) != imgs.shape[0]:
+            raise VOError(VO_ERR_ARG, "describe_batch: imgs [n_img, rows, cols] and one point set per image")
+        sets = [as_keypoints(p) for p in points_list]
+        counts = np.array([len(s) for s in sets], np.int32)
+        stride = int(counts.max()) if len(sets) else 0
+        pts = np.zeros((len(sets), max(stride, 1)), KP_DTYPE)
+        for i, s in enumerate(sets):
+            pts[i, : len(s)] = s
+        desc = np.zeros((len(sets), max(stride, 1), 128), np.uint8)
+        self._check(self.lib.vo_describe_batch(self.h, _p(imgs, C.c_uint8), imgs.shape[2], 0, imgs.shape[0],
+                                               pts.ctypes.data_as(C.POINTER(Keypoint)), _p(counts, C.c_int32), stride,
+                                               _p(desc, C.c_uint8)))
+        return [desc[i, : counts[i]].copy() for i in range(len(sets))]
 
     # ---- undistortImage ----
     def undistort(self, img: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.0), col_major: bool = False) -> np.ndarray:
@@ -760,10 +853,22 @@ def undistortImage(I: np.ndarray, K, radial=(0.0, 0.0, 0.0), tangential=(0.0, 0.
 
 def extractFeatures(I: np.ndarray, points=None, Method: str = "SIFT", strongest: int | None = None):
     """extractFeatures(I, points, "Method", "SIFT") (VO.m:83-84) -> (features, validPoints).
-    SIFT descriptors are computed in the same device pass as detection; all
-    points are valid.  strongest=N describes selectStrongest(points, N) only."""
+    With `points` (see as_keypoints) exactly those points are described, in their order
+    (Context.describe): detections that were moved, rescaled or re-oriented, another detector's
+    points, a grid; every point is valid, so validPoints is the given set.  `strongest` does not
+    combine with given points (they are already chosen): VOError(VO_ERR_ARG).
+    points=None detects as well: SIFT descriptors are computed in the same device pass as
+    detection; strongest=N describes selectStrongest(points, N) only."""
     if Method != "SIFT":
         raise VOError(VO_ERR_ARG, "only Method 'SIFT' is on the hot path")
+    if points is not None:
+        if strongest is not None:
+            raise VOError(VO_ERR_ARG, "extractFeatures: strongest applies to detection, not to given points")
+        pts = as_keypoints(points)
+        I = np.asarray(I)
+        if I.ndim != 2 or I.dtype != np.uint8:
+            raise VOError(VO_ERR_ARG, "extractFeatures: a 2-D uint8 image")
+        return _default_ctx(*I.shape).describe(I, pts), pts
     kps, desc = _sift_strongest(I, strongest)
     return desc, kps
 
