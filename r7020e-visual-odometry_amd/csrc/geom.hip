@@ -11,9 +11,7 @@
 //       Grunert P3P, 4th-point disambiguation), a wave per slot score
 //       (lane-strided partial MSAC sums + fixed shuffle tree), then the
 //       sequential adaptive-termination replay of the chunk -- until the replay
-//       stops; msac_final: inlier mask + camera pose.  (The eager kernels
-//       k_msac_hyp / k_msac_score / k_msac_select score every slot first; they
-//       are compiled only into the test build libvo_exp.so, VO_EXPERIMENTAL.)
+//       stops; msac_final: inlier mask + camera pose.
 //   landmarks (VO.m:145-160, CreateLandmarksFromFeatures.m)  k_stereo_pos,
 //       k_lm_filter (any-x-or-y equality test, quirk Q3) + block compaction,
 //       k_lm_tri (odd rows, z gates).  (One fused block per frame measured
@@ -494,17 +492,6 @@ __device__ void msac_hyp_slot(const MsacArgs& a, int f, int s, int n)
     h->valid = 1;
 }
 
-#if VO_EXPERIMENTAL   // eager MSAC: test build only (libvo_exp.so), the cross-check of k_msac
-// one lane per (frame, slot).  grid (ceil(n_hyp/64), B)  (eager form: every slot)
-__global__ __launch_bounds__(64) void k_msac_hyp(MsacArgs a)
-{
-    const int f = blockIdx.y;
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= a.n_hyp) return;
-    msac_hyp_slot(a, f, s, msac_n(a, f));
-}
-#endif  // VO_EXPERIMENTAL
-
 // MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed shuffle tree
 __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s, int n, int lane)
 {
@@ -529,20 +516,6 @@ __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s,
     if (lane == 0) { h->score = part; h->n_in = cnt; }
 }
 
-#if VO_EXPERIMENTAL   // eager MSAC: test build only (libvo_exp.so), the cross-check of k_msac
-// one wave per (frame, slot): MSAC score = 64 lane-strided partials + tree
-__global__ __launch_bounds__(256) void k_msac_score(MsacArgs a, int B)
-{
-    const int lane = threadIdx.x & 63;
-    const long total = (long)B * a.n_hyp;
-    for (long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6); t < total; t += (long)gridDim.x * 4) {
-        const int f = (int)(t / a.n_hyp), s = (int)(t - (long)f * a.n_hyp);
-        if (!a.hyp[(size_t)f * a.n_hyp + s].valid) continue;
-        msac_score_slot(a, f, s, msac_n(a, f), lane);
-    }
-}
-#endif  // VO_EXPERIMENTAL
-
 __device__ int msac_trials_needed_dev(int n_in, int n, double conf)
 {
     double w = (double)n_in / (double)n;
@@ -556,46 +529,6 @@ __device__ int msac_trials_needed_dev(int n_in, int n, double conf)
     if (N < 1.0) return 1;
     return (int)N;
 }
-
-__device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status, int lane);
-
-#if VO_EXPERIMENTAL   // eager MSAC: test build only (libvo_exp.so), the cross-check of k_msac
-// sequential MSAC replay (adaptive trial count) + final inliers/pose.  block 64 per frame
-__global__ __launch_bounds__(64) void k_msac_select(MsacArgs a)
-{
-    __shared__ int s_best;
-    __shared__ int s_status;
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const int n = msac_n(a, f);
-    FrameGeom* g = a.fg + f;
-    if (lane == 0) {
-        int status = VO_OK, best = -1;
-        if (n < 4) status = VO_ERR_TOO_FEW_POINTS;
-        else {
-            int num_trials = a.max_trials, trials = 0, best_in = 0;
-            double best_score = INFINITY;
-            for (int s = 0; s < a.max_trials && s < a.n_hyp && trials < num_trials; ++s) {
-                const MsacHyp* h = a.hyp + (size_t)f * a.n_hyp + s;
-                if (!h->valid) continue;
-                trials++;
-                if (h->score < best_score) {
-                    best_score = h->score; best = s; best_in = h->n_in;
-                    int need = msac_trials_needed_dev(h->n_in, n, a.conf);
-                    if (need < num_trials) num_trials = need;
-                }
-            }
-            if (best < 0 || best_in < 4) status = VO_ERR_NO_CONSENSUS;
-        }
-        s_best = best;
-        s_status = status;
-        g->status = status;
-        g->best = best;
-        g->n_tracked = n;
-    }
-    __syncthreads();
-    msac_final(a, f, n, s_best, s_status, lane);
-}
-#endif  // VO_EXPERIMENTAL
 
 // inlier mask + camera pose of the chosen slot (one wave)
 __device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status, int lane)
@@ -868,18 +801,6 @@ static MsacArgs msac_args(GeomBuffers& g, const double* img, const double* world
 
 static void msac_enqueue(const MsacArgs& a, int B, hipStream_t s)
 {
-#if VO_EXPERIMENTAL
-    // test build: the eager form (every slot generated and scored, then the replay) when
-    // vo_exp_set selects it -- the cross-check of the lazy kernel (tests/test_gpu_geometry.py)
-    if (g_exp_msac_eager) {
-        VO_LAUNCH(k_msac_hyp, dim3((a.n_hyp + 63) / 64, B), dim3(64), 0, s, a);
-        int blocks = (B * a.n_hyp + 3) / 4;
-        if (blocks > 4096) blocks = 4096;
-        VO_LAUNCH(k_msac_score, dim3(blocks), dim3(256), 0, s, a, B);
-        VO_LAUNCH(k_msac_select, dim3(B), dim3(64), 0, s, a);
-        return;
-    }
-#endif
     VO_LAUNCH(k_msac, dim3(B), dim3(VO_MSAC_T), 0, s, a);
 }
 

@@ -441,14 +441,11 @@ hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap)
     b.max_jobs = max_jobs;
     b.row_cap = row_cap;
     b.n_chunks = (row_cap + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
-    hipError_t e = hipMalloc((void**)&b.jobs, sizeof(MatchJob) * max_jobs);
-    if (e != hipSuccess) return e;
     return hipMalloc((void**)&b.partial, sizeof(MatchTop2) * (size_t)max_jobs * b.n_chunks * row_cap);
 }
 
 void match_free(MatchBuffers& b)
 {
-    hipFree(b.jobs);
     hipFree(b.partial);
     b = MatchBuffers();
 }
@@ -481,7 +478,6 @@ void match_ex_free(MatchExBuffers& x)
 MatchBuffers match_view(const MatchBuffers& b, int k0)
 {
     MatchBuffers v = b;
-    v.jobs = b.jobs ? b.jobs + k0 : nullptr;
     v.partial = b.partial + (size_t)k0 * b.n_chunks * b.row_cap;
     v.max_jobs = b.max_jobs - k0;
     return v;

@@ -77,31 +77,30 @@ struct vo_ctx {
     // at the end of sub[0]'s chain, ev_join[p] at the end of this one
     hipStream_t down = nullptr;
     hipEvent_t ev_down[MAX_SUB] = {}, ev_top[MAX_SUB] = {};
-    // Asynchronous batch pipeline (vo_sift_match_batch_dev): calls alternate between two
-    // buffer sets; set 0 is the context's own buffers (sb, mb, stereo jobs, pairs), set 1
-    // is `aux`.  A call's scale space waits only for the previous use of its own set, so
+    // Asynchronous batch pipeline (vo_sift_match_batch_dev): calls alternate between the two
+    // buffer sets.  A call's scale space waits only for the previous use of its own set, so
     // the pyramid of call N+1 overlaps the latency-bound feature stages of call N.
-    // Set 1 is a full replica of set 0's per-frame state (image slots incl. the carried
-    // frame, pair slots incl. the carry slot, stereo + tracking jobs, geometry buffers), so
-    // the full per-frame path can also alternate sets (vo_step_submit_dev).
-    struct AuxSet {
-        SiftBuffers sb;
-        MatchBuffers mb;
-        MatchJob* d_jobs = nullptr;      // [0, M) stereo, [M, 5M) tracking (job_track layout)
-        int* pair_i = nullptr; int* pair_j = nullptr; int* pair_n = nullptr;   // max_batch + 1 slots
+    // Each set is the full per-frame state (image slots incl. the carried frame, pair slots
+    // incl. the carry slot, stereo + tracking jobs, geometry buffers), so the full per-frame
+    // path can also alternate sets (vo_step_submit_dev).  The synchronous single-image and
+    // standalone entries (vo_sift, vo_describe, vo_track, ...) use set 0.
+    struct BufferSet {
+        SiftBuffers sb;                  // 2*max_batch + 2 image slots (last 2 = carried frame)
+        MatchBuffers mb;                 // max_batch partial-result slots (a job's index within its launch)
+        MatchJob* d_jobs = nullptr;      // [0, M) stereo, [M, 5M) tracking (job_stereo / job_track)
+        int* pair_i = nullptr;           // stereo pairs per frame slot [max_batch + 1][kp_cap]
+        int* pair_j = nullptr;
+        int* pair_n = nullptr;           // [max_batch + 1]
         GeomBuffers gb;
-    } aux;
-    hipEvent_t ev_done[2] = {};
-    hipEvent_t ev_arena[2] = {};     // set's scale-space arena read for the last time (after k_desc)
+        hipEvent_t ev_done = nullptr;    // the set's last SIFT + stereo match is done
+        hipEvent_t ev_arena = nullptr;   // set's scale-space arena read for the last time (after k_desc)
+        // the set's last SIFT call ran with vo_set_strongest on, so its n_det holds the detected
+        // counts (otherwise n_kp does)
+        bool sel_used = false;
+    } set[2];
     int next_set = 0, last_set = 0;
     Pyramid py;
     Pyramid* d_py = nullptr;
-    SiftBuffers sb;                  // 2*max_batch + 2 image slots (last 2 = carried frame)
-    MatchBuffers mb;
-    MatchJob* d_jobs = nullptr;      // job tables (see JOB_* offsets)
-    int* d_pair_i = nullptr;         // stereo pairs per frame slot [slots][kp_cap]
-    int* d_pair_j = nullptr;
-    int* d_pair_n = nullptr;         // [slots]
     uint8_t* d_img = nullptr;        // image staging [2*max_batch][rows*cols]
     uint8_t* d_cm = nullptr;         // column-major (MATLAB) image staging, allocated on first use
     size_t cm_cap = 0;
@@ -114,10 +113,8 @@ struct vo_ctx {
     uint8_t* d_rect = nullptr;
     int rect_B = 0;                  // frames of the last batched call that went through d_rect
     // vo_set_strongest: SIFTPoints.selectStrongest(points, strongest) between detection and
-    // description in every entry that detects (0 = off); sel_used[set]: the set's last SIFT call
-    // ran with it, so its n_det holds the detected counts (otherwise n_kp does)
+    // description in every entry that detects (0 = off)
     int strongest = 0;
-    bool sel_used[2] = {false, false};
     // the last SIFT call was vo_describe / vo_describe_batch: set 0 holds a scale space and the
     // caller's points, no detections, so the fetches of a detecting call's results are refused
     bool described = false;
@@ -125,6 +122,7 @@ struct vo_ctx {
     uint8_t* d_fd[2] = {nullptr, nullptr};
     DescMeta* d_fm[2] = {nullptr, nullptr};
     int* d_fn = nullptr;             // [2]
+    MatchJob* d_job_single = nullptr;   // vo_match's one job over the staging above (partials: set 0's slot 0)
     float* d_ff[2] = {nullptr, nullptr};   // vo_match_f32 staging (single descriptors as MATLAB holds them)
     // vo_match_f32 on general (non-u8-valued) features: normalised F1, transposed F2, per-row result
     // (allocated on first use)
@@ -134,7 +132,6 @@ struct vo_ctx {
     MatchExBuffers mx;               // vo_match_ex / vo_match_f32_ex (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
-    GeomBuffers gb;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
     // n & 1; its geometry runs on `stream` while the later batches' SIFT runs on sub[0..1].
     // Up to VO_STEP_DEPTH batches are in flight, so each batch also owns a result slot
@@ -212,10 +209,10 @@ const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_creat
 
 void* vo_stream(vo_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
-// job table layout: [0, B) stereo; [B, B + 4*B) tracking steps; last: vo_match
+// a set's job table: [0, M) stereo; [M, 5M) the four tracking steps (M = max_batch)
 static int job_stereo(const vo_ctx*, int f) { return f; }
 static int job_track(const vo_ctx* c, int step, int f) { return c->max_batch + step * c->max_batch + f; }
-static int job_single(const vo_ctx* c) { return 5 * c->max_batch; }
+static int job_count(const vo_ctx* c) { return 5 * c->max_batch; }
 
 static void destroy_streams(vo_ctx* c)
 {
@@ -231,12 +228,6 @@ static void destroy_streams(vo_ctx* c)
     c->down = nullptr;
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     c->ev_fork = nullptr;
-    for (int k = 0; k < 2; ++k) {
-        if (c->ev_done[k]) hipEventDestroy(c->ev_done[k]);
-        if (c->ev_arena[k]) hipEventDestroy(c->ev_arena[k]);
-        c->ev_arena[k] = nullptr;
-        c->ev_done[k] = nullptr;
-    }
     for (int k = 0; k < VO_STEP_DEPTH; ++k) {
         if (c->sh[k].ev) hipEventDestroy(c->sh[k].ev);
         c->sh[k].ev = nullptr;
@@ -245,14 +236,59 @@ static void destroy_streams(vo_ctx* c)
     c->copy_stream = nullptr;
 }
 
+// Buffer set k: its buffers, its job table (job_stereo / job_track) and its two events.  On failure
+// *what names the step; set_free releases whatever was made.
+static hipError_t set_create(vo_ctx* c, int k, const char** what)
+{
+    vo_ctx::BufferSet& S = c->set[k];
+    const int M = c->max_batch, K = c->sp.max_keypoints, pair_slots = M + 1, n_jobs = job_count(c);
+    hipError_t e;
+    *what = "event";
+    if ((e = hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventCreateWithFlags(&S.ev_arena, hipEventDisableTiming)) != hipSuccess) return e;
+    *what = "sift buffers";
+    if ((e = sift_alloc(S.sb, c->py, K, 4 * K)) != hipSuccess) return e;
+    *what = "match buffers";
+    if ((e = match_alloc(S.mb, M, K)) != hipSuccess) return e;
+    *what = "jobs";
+    if ((e = hipMalloc((void**)&S.d_jobs, sizeof(MatchJob) * n_jobs)) != hipSuccess) return e;
+    *what = "pairs";
+    if ((e = hipMalloc((void**)&S.pair_i, sizeof(int) * (size_t)pair_slots * K)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&S.pair_j, sizeof(int) * (size_t)pair_slots * K)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&S.pair_n, sizeof(int) * pair_slots)) != hipSuccess) return e;
+    if ((e = hipMemset(S.pair_n, 0, sizeof(int) * pair_slots)) != hipSuccess) return e;
+    *what = "geometry buffers";
+    if ((e = geom_alloc(S.gb, M, K, c->rp.max_num_trials)) != hipSuccess) return e;
+    std::vector<MatchJob> jobs(n_jobs);
+    memset(jobs.data(), 0, sizeof(MatchJob) * n_jobs);
+    const size_t dstride = (size_t)K * VO_DESC_LEN;
+    for (int f = 0; f < M; ++f) {
+        MatchJob& J = jobs[job_stereo(c, f)];
+        const int il = 2 * f, ir = 2 * f + 1;
+        J.d1 = S.sb.desc + il * dstride; J.m1 = S.sb.meta + (size_t)il * K; J.idx1 = nullptr; J.n1 = S.sb.n_kp + il;
+        J.d2 = S.sb.desc + ir * dstride; J.m2 = S.sb.meta + (size_t)ir * K; J.idx2 = nullptr; J.n2 = S.sb.n_kp + ir;
+        J.out_i = S.pair_i + (size_t)f * K; J.out_j = S.pair_j + (size_t)f * K; J.out_n = S.pair_n + f;
+        J.cap = K;
+    }
+    geom_fill_track_jobs(S.gb, jobs.data(), M, job_track(c, 0, 0), S.sb, S.pair_i, S.pair_j, S.pair_n, K);
+    *what = "jobs copy";
+    return hipMemcpy(S.d_jobs, jobs.data(), sizeof(MatchJob) * n_jobs, hipMemcpyHostToDevice);
+}
+
+static void set_free(vo_ctx::BufferSet& S)
+{
+    sift_free(S.sb);
+    match_free(S.mb);
+    hipFree(S.d_jobs); hipFree(S.pair_i); hipFree(S.pair_j); hipFree(S.pair_n);
+    geom_free(S.gb);
+    if (S.ev_done) hipEventDestroy(S.ev_done);
+    if (S.ev_arena) hipEventDestroy(S.ev_arena);
+    S = vo_ctx::BufferSet();
+}
+
 static void destroy_buffers(vo_ctx* c)
 {
-    sift_free(c->sb);
-    match_free(c->mb);
-    sift_free(c->aux.sb);
-    match_free(c->aux.mb);
-    hipFree(c->aux.d_jobs); hipFree(c->aux.pair_i); hipFree(c->aux.pair_j); hipFree(c->aux.pair_n);
-    geom_free(c->aux.gb);
+    for (int k = 0; k < 2; ++k) set_free(c->set[k]);
     for (int k = 0; k < VO_STEP_DEPTH; ++k) {
         hipHostFree(c->sh[k].fg); hipHostFree(c->sh[k].nkp); hipHostFree(c->sh[k].ncand); hipHostFree(c->sh[k].np); hipHostFree(c->sh[k].rows);
         hipHostFree(c->sh[k].ndet);
@@ -264,8 +300,7 @@ static void destroy_buffers(vo_ctx* c)
     }
     for (void* p : c->lm_retired) hipFree(p);
     c->lm_retired.clear();
-    geom_free(c->gb);
-    hipFree(c->d_py); hipFree(c->d_jobs); hipFree(c->d_pair_i); hipFree(c->d_pair_j); hipFree(c->d_pair_n);
+    hipFree(c->d_py); hipFree(c->d_job_single);
     hipFree(c->d_rect);
     c->d_rect = nullptr;
     hipFree(c->d_img); hipFree(c->d_cm); hipFree(c->d_fd[0]); hipFree(c->d_fd[1]); hipFree(c->d_fm[0]); hipFree(c->d_fm[1]);
@@ -311,8 +346,9 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         delete c;
         return nullptr;
     };
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail("stream", e);
+    // (every failure frees what was made so far)
+#define TRY(what, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(what, e_); } while (0)
+    TRY("stream", hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int k = 0; k < vo_ctx::MAX_SUB; ++k) {
         // every stream at the default priority: the forked SIFT streams must not rank below the
         // geometry / copy streams of the pipelined loop body (at the lowest priority the full
@@ -320,109 +356,62 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
         // at the highest priority measured within noise.  No CU masks: with masks that bind
         // (contiguous CU ranges), every split of the CUs between the two streams was 9-38 %
         // slower -- both streams are bound per CU and need the whole chip
-        e = hipStreamCreateWithFlags(&c->sub[k], hipStreamNonBlocking);
-        if (e != hipSuccess) return bail("stream", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_o0[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_down[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_top[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
+        TRY("stream", hipStreamCreateWithFlags(&c->sub[k], hipStreamNonBlocking));
+        TRY("event", hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming));
+        TRY("event", hipEventCreateWithFlags(&c->ev_o0[k], hipEventDisableTiming));
+        TRY("event", hipEventCreateWithFlags(&c->ev_down[k], hipEventDisableTiming));
+        TRY("event", hipEventCreateWithFlags(&c->ev_top[k], hipEventDisableTiming));
     }
     // (the down stream at the lowest / highest priority, forked after octave 0: 1-3 % slower than at
     // the default)
-    if ((e = hipStreamCreateWithFlags(&c->down, hipStreamNonBlocking)) != hipSuccess) return bail("stream", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-    for (int k = 0; k < 2; ++k) {
-        if ((e = hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_arena[k], hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-    }
-    if ((e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail("stream", e);
+    TRY("stream", hipStreamCreateWithFlags(&c->down, hipStreamNonBlocking));
+    TRY("event", hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    TRY("stream", hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     const int n_slots = 2 * max_batch + 2;
     const int kp_cap = c->sp.max_keypoints;
     build_pyramid_geometry(c->py, rows, cols, n_slots, c->sp);
-    if ((e = hipMalloc((void**)&c->d_py, sizeof(Pyramid))) != hipSuccess) return bail("pyramid", e);
-    if ((e = hipMemcpy(c->d_py, &c->py, sizeof(Pyramid), hipMemcpyHostToDevice)) != hipSuccess) return bail("pyramid copy", e);
-    if ((e = sift_alloc(c->sb, c->py, kp_cap, 4 * kp_cap)) != hipSuccess) return bail("sift buffers", e);
-    const int n_jobs = 5 * max_batch + 1;
-    if ((e = match_alloc(c->mb, n_jobs, kp_cap)) != hipSuccess) return bail("match buffers", e);
-    if ((e = hipMalloc((void**)&c->d_jobs, sizeof(MatchJob) * n_jobs)) != hipSuccess) return bail("jobs", e);
-    const int pair_slots = max_batch + 1;
-    if ((e = hipMalloc((void**)&c->d_pair_i, sizeof(int) * (size_t)pair_slots * kp_cap)) != hipSuccess) return bail("pairs", e);
-    if ((e = hipMalloc((void**)&c->d_pair_j, sizeof(int) * (size_t)pair_slots * kp_cap)) != hipSuccess) return bail("pairs", e);
-    if ((e = hipMalloc((void**)&c->d_pair_n, sizeof(int) * pair_slots)) != hipSuccess) return bail("pairs", e);
-    if ((e = hipMemset(c->d_pair_n, 0, sizeof(int) * pair_slots)) != hipSuccess) return bail("pairs", e);
-    if ((e = hipMalloc((void**)&c->d_img, (size_t)2 * max_batch * rows * cols)) != hipSuccess) return bail("staging", e);
+    TRY("pyramid", hipMalloc((void**)&c->d_py, sizeof(Pyramid)));
+    TRY("pyramid copy", hipMemcpy(c->d_py, &c->py, sizeof(Pyramid), hipMemcpyHostToDevice));
     for (int k = 0; k < 2; ++k) {
-        if ((e = hipMalloc((void**)&c->d_fd[k], (size_t)kp_cap * VO_DESC_LEN)) != hipSuccess) return bail("staging", e);
-        if ((e = hipMalloc((void**)&c->d_fm[k], sizeof(DescMeta) * kp_cap)) != hipSuccess) return bail("staging", e);
-        if ((e = hipMalloc((void**)&c->d_ff[k], sizeof(float) * kp_cap * VO_DESC_LEN)) != hipSuccess) return bail("staging", e);
+        const char* what = "";
+        const hipError_t e = set_create(c, k, &what);
+        if (e != hipSuccess) return bail((std::string(what) + (k ? " (set 1)" : "")).c_str(), e);
     }
-    if ((e = hipMalloc((void**)&c->d_fn, sizeof(int) * 2)) != hipSuccess) return bail("staging", e);
-    if ((e = hipMalloc((void**)&c->d_bad, sizeof(int))) != hipSuccess) return bail("staging", e);
-    if ((e = hipMalloc((void**)&c->d_mi, sizeof(int) * kp_cap)) != hipSuccess) return bail("staging", e);
-    if ((e = hipMalloc((void**)&c->d_mj, sizeof(int) * kp_cap)) != hipSuccess) return bail("staging", e);
-    if ((e = hipMalloc((void**)&c->d_mn, sizeof(int))) != hipSuccess) return bail("staging", e);
-    if ((e = geom_alloc(c->gb, max_batch, kp_cap, c->rp.max_num_trials)) != hipSuccess) return bail("geometry buffers", e);
-    // job tables
-    std::vector<MatchJob> jobs(n_jobs);
-    memset(jobs.data(), 0, sizeof(MatchJob) * n_jobs);
-    const size_t dstride = (size_t)kp_cap * VO_DESC_LEN;
-    for (int f = 0; f < max_batch; ++f) {
-        MatchJob& J = jobs[job_stereo(c, f)];
-        const int il = 2 * f, ir = 2 * f + 1;
-        J.d1 = c->sb.desc + il * dstride; J.m1 = c->sb.meta + (size_t)il * kp_cap; J.idx1 = nullptr; J.n1 = c->sb.n_kp + il;
-        J.d2 = c->sb.desc + ir * dstride; J.m2 = c->sb.meta + (size_t)ir * kp_cap; J.idx2 = nullptr; J.n2 = c->sb.n_kp + ir;
-        J.out_i = c->d_pair_i + (size_t)f * kp_cap; J.out_j = c->d_pair_j + (size_t)f * kp_cap; J.out_n = c->d_pair_n + f;
-        J.cap = kp_cap;
+    TRY("staging", hipMalloc((void**)&c->d_img, (size_t)2 * max_batch * rows * cols));
+    for (int k = 0; k < 2; ++k) {
+        TRY("staging", hipMalloc((void**)&c->d_fd[k], (size_t)kp_cap * VO_DESC_LEN));
+        TRY("staging", hipMalloc((void**)&c->d_fm[k], sizeof(DescMeta) * kp_cap));
+        TRY("staging", hipMalloc((void**)&c->d_ff[k], sizeof(float) * kp_cap * VO_DESC_LEN));
     }
-    geom_fill_track_jobs(c->gb, jobs.data(), c->max_batch, job_track(c, 0, 0), c->sb, c->d_pair_i, c->d_pair_j, c->d_pair_n,
-                         kp_cap);
-    {
-        MatchJob& J = jobs[job_single(c)];
+    TRY("staging", hipMalloc((void**)&c->d_fn, sizeof(int) * 2));
+    TRY("staging", hipMalloc((void**)&c->d_bad, sizeof(int)));
+    TRY("staging", hipMalloc((void**)&c->d_mi, sizeof(int) * kp_cap));
+    TRY("staging", hipMalloc((void**)&c->d_mj, sizeof(int) * kp_cap));
+    TRY("staging", hipMalloc((void**)&c->d_mn, sizeof(int)));
+    {   // vo_match's job: the two staged descriptor sets (match_ex_buffers builds the exchanged one)
+        MatchJob J;
+        memset(&J, 0, sizeof(J));
         J.d1 = c->d_fd[0]; J.m1 = c->d_fm[0]; J.idx1 = nullptr; J.n1 = c->d_fn;
         J.d2 = c->d_fd[1]; J.m2 = c->d_fm[1]; J.idx2 = nullptr; J.n2 = c->d_fn + 1;
         J.out_i = c->d_mi; J.out_j = c->d_mj; J.out_n = c->d_mn; J.cap = kp_cap;
-    }
-    if ((e = hipMemcpy(c->d_jobs, jobs.data(), sizeof(MatchJob) * n_jobs, hipMemcpyHostToDevice)) != hipSuccess) return bail("jobs copy", e);
-    // second buffer set of the asynchronous pipelines (a full replica of set 0's per-frame state)
-    {
-        vo_ctx::AuxSet& X = c->aux;
-        const int xn = 5 * max_batch;
-        if ((e = sift_alloc(X.sb, c->py, kp_cap, 4 * kp_cap)) != hipSuccess) return bail("sift buffers (set 1)", e);
-        if ((e = match_alloc(X.mb, max_batch, kp_cap)) != hipSuccess) return bail("match buffers (set 1)", e);
-        if ((e = hipMalloc((void**)&X.d_jobs, sizeof(MatchJob) * xn)) != hipSuccess) return bail("jobs (set 1)", e);
-        if ((e = hipMalloc((void**)&X.pair_i, sizeof(int) * (size_t)pair_slots * kp_cap)) != hipSuccess) return bail("pairs", e);
-        if ((e = hipMalloc((void**)&X.pair_j, sizeof(int) * (size_t)pair_slots * kp_cap)) != hipSuccess) return bail("pairs", e);
-        if ((e = hipMalloc((void**)&X.pair_n, sizeof(int) * pair_slots)) != hipSuccess) return bail("pairs", e);
-        if ((e = hipMemset(X.pair_n, 0, sizeof(int) * pair_slots)) != hipSuccess) return bail("pairs", e);
-        if ((e = geom_alloc(X.gb, max_batch, kp_cap, c->rp.max_num_trials)) != hipSuccess) return bail("geometry buffers (set 1)", e);
-        std::vector<MatchJob> xj(xn);
-        memset(xj.data(), 0, sizeof(MatchJob) * xn);
-        for (int f = 0; f < max_batch; ++f) {
-            MatchJob& J = xj[f];
-            const int il = 2 * f, ir = 2 * f + 1;
-            J.d1 = X.sb.desc + il * dstride; J.m1 = X.sb.meta + (size_t)il * kp_cap; J.idx1 = nullptr; J.n1 = X.sb.n_kp + il;
-            J.d2 = X.sb.desc + ir * dstride; J.m2 = X.sb.meta + (size_t)ir * kp_cap; J.idx2 = nullptr; J.n2 = X.sb.n_kp + ir;
-            J.out_i = X.pair_i + (size_t)f * kp_cap; J.out_j = X.pair_j + (size_t)f * kp_cap; J.out_n = X.pair_n + f;
-            J.cap = kp_cap;
-        }
-        geom_fill_track_jobs(X.gb, xj.data(), max_batch, job_track(c, 0, 0), X.sb, X.pair_i, X.pair_j, X.pair_n, kp_cap);
-        if ((e = hipMemcpy(X.d_jobs, xj.data(), sizeof(MatchJob) * xn, hipMemcpyHostToDevice)) != hipSuccess)
-            return bail("jobs copy (set 1)", e);
+        TRY("jobs", hipMalloc((void**)&c->d_job_single, sizeof(MatchJob)));
+        TRY("jobs copy", hipMemcpy(c->d_job_single, &J, sizeof(MatchJob), hipMemcpyHostToDevice));
     }
     for (int k = 0; k < VO_STEP_DEPTH; ++k) {
         vo_ctx::StepHost& H = c->sh[k];
-        if ((e = hipEventCreateWithFlags(&H.ev, hipEventDisableTiming)) != hipSuccess) return bail("event", e);
-        if ((e = hipMalloc((void**)&H.d_pX, sizeof(float) * 3 * max_batch * kp_cap)) != hipSuccess) return bail("packed rows", e);
-        if ((e = hipMalloc((void**)&H.d_pkeep, (size_t)max_batch * kp_cap)) != hipSuccess) return bail("packed rows", e);
-        if ((e = hipHostMalloc((void**)&H.fg, sizeof(FrameGeom) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.nkp, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.ncand, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.ndet, sizeof(int) * 2 * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.np, sizeof(int) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.rows, sizeof(int) * max_batch, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.pX, sizeof(float) * 3 * max_batch * kp_cap, 0)) != hipSuccess) return bail("pinned", e);
-        if ((e = hipHostMalloc((void**)&H.pkeep, (size_t)max_batch * kp_cap, 0)) != hipSuccess) return bail("pinned", e);
+        TRY("event", hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
+        TRY("packed rows", hipMalloc((void**)&H.d_pX, sizeof(float) * 3 * max_batch * kp_cap));
+        TRY("packed rows", hipMalloc((void**)&H.d_pkeep, (size_t)max_batch * kp_cap));
+        TRY("pinned", hipHostMalloc((void**)&H.fg, sizeof(FrameGeom) * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.nkp, sizeof(int) * 2 * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.ncand, sizeof(int) * 2 * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.ndet, sizeof(int) * 2 * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.np, sizeof(int) * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.rows, sizeof(int) * max_batch, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.pX, sizeof(float) * 3 * max_batch * kp_cap, 0));
+        TRY("pinned", hipHostMalloc((void**)&H.pkeep, (size_t)max_batch * kp_cap, 0));
     }
+#undef TRY
     return c;
 }
 
@@ -504,7 +493,7 @@ static int begin_call(vo_ctx* c, bool quiesce = true, bool step = false)
         return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
     g_prof = c->prof.on ? &c->prof : nullptr;
     if (quiesce)
-        for (int k = 0; k < 2; ++k) hipStreamWaitEvent(c->stream, c->ev_done[k], 0);
+        for (int k = 0; k < 2; ++k) hipStreamWaitEvent(c->stream, c->set[k].ev_done, 0);
     return VO_OK;
 }
 #define BEGIN_CALL(...) do { int rc_ = begin_call(__VA_ARGS__); if (rc_) return rc_; } while (0)
@@ -566,28 +555,28 @@ int vo_sift_ex(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int co
     int rc_stage = stage_images(c, img, ld, col_major, 1, c->d_img);
     if (rc_stage) return rc_stage;
     ImageSrc src{c->d_img, c->d_img, (size_t)rows * cols, cols, 0};
-    sift_enqueue(c->py, c->sb, src, 1, c->sp, c->stream, c->d_py, c->strongest);
+    sift_enqueue(c->py, c->set[0].sb, src, 1, c->sp, c->stream, c->d_py, c->strongest);
     c->last_set = 0;                                   // vo_fetch_* now read this result (set 0)
-    c->sel_used[0] = c->strongest > 0;
+    c->set[0].sel_used = c->strongest > 0;
     c->described = false;
     int n = 0, n_cand = 0, n_det = -1;
-    HIPC(c, hipMemcpyAsync(&n, c->sb.n_kp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (c->strongest > 0) HIPC(c, hipMemcpyAsync(&n_det, c->sb.n_det, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(&n_cand, c->sb.n_cand, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&n, c->set[0].sb.n_kp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (c->strongest > 0) HIPC(c, hipMemcpyAsync(&n_det, c->set[0].sb.n_det, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&n_cand, c->set[0].sb.n_cand, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     int rc = finish(c);
     if (rc) return rc;
     if (n_out) *n_out = n;
-    int m = std::min(std::min(n, c->sb.kp_cap), capacity);
+    int m = std::min(std::min(n, c->set[0].sb.kp_cap), capacity);
     if (m > 0) {
-        if (kps) HIPC(c, hipMemcpy(kps, c->sb.kp, sizeof(vo_keypoint) * m, hipMemcpyDeviceToHost));
-        if (desc) HIPC(c, hipMemcpy(desc, c->sb.desc, (size_t)m * VO_DESC_LEN, hipMemcpyDeviceToHost));
+        if (kps) HIPC(c, hipMemcpy(kps, c->set[0].sb.kp, sizeof(vo_keypoint) * m, hipMemcpyDeviceToHost));
+        if (desc) HIPC(c, hipMemcpy(desc, c->set[0].sb.desc, (size_t)m * VO_DESC_LEN, hipMemcpyDeviceToHost));
     }
-    if (n_cand > c->sb.cand_cap)
+    if (n_cand > c->set[0].sb.cand_cap)
         return fail(c, VO_ERR_CAPACITY, "vo_sift: %d extremum candidates exceed the candidate list (%d = 4 x max_keypoints)",
-                    n_cand, c->sb.cand_cap);
+                    n_cand, c->set[0].sb.cand_cap);
     if (n_det < 0) n_det = n;                          // selection off: the detected count
-    if (n_det > c->sb.kp_cap)
-        return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed max_keypoints %d", n_det, c->sb.kp_cap);
+    if (n_det > c->set[0].sb.kp_cap)
+        return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed max_keypoints %d", n_det, c->set[0].sb.kp_cap);
     if (n > capacity) return fail(c, VO_ERR_CAPACITY, "vo_sift: %d keypoints exceed capacity %d", n, capacity);
     return VO_OK;
 }
@@ -641,7 +630,7 @@ int vo_describe_batch(vo_ctx* c, const uint8_t* imgs, int ld, int col_major, int
         return fail(c, VO_ERR_ARG, "vo_describe: bad arguments");
     // every refusal before anything is enqueued
     if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
-    const int K = c->sb.kp_cap;
+    const int K = c->set[0].sb.kp_cap;
     long total = 0;
     int max_n = 0;
     for (int i = 0; i < n_img; ++i) {
@@ -669,27 +658,27 @@ int vo_describe_batch(vo_ctx* c, const uint8_t* imgs, int ld, int col_major, int
         if (rc) return rc;
     }
     // the points and their counts into the keypoint rows the detecting entries write (set 0)
-    HIPC(c, hipMemcpy2DAsync(c->sb.kp, sizeof(vo_keypoint) * K, pts, sizeof(vo_keypoint) * pts_stride,
+    HIPC(c, hipMemcpy2DAsync(c->set[0].sb.kp, sizeof(vo_keypoint) * K, pts, sizeof(vo_keypoint) * pts_stride,
                              sizeof(vo_keypoint) * max_n, n_img, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->sb.n_kp, n_pts, sizeof(int) * n_img, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].sb.n_kp, n_pts, sizeof(int) * n_img, hipMemcpyHostToDevice, c->stream));
     // consecutive images: slot i = (i & 1 ? right : left) + (i >> 1) * frame_stride
     const size_t fs = (size_t)c->rows * c->cols;
     ImageSrc src{c->d_img, c->d_img + fs, 2 * fs, c->cols, 0};
-    sift_enqueue_describe(c->py, c->sb, src, n_img, (int)std::min<long>(total, INT_MAX), c->sp, c->stream, c->d_py);
+    sift_enqueue_describe(c->py, c->set[0].sb, src, n_img, (int)std::min<long>(total, INT_MAX), c->sp, c->stream, c->d_py);
     c->last_set = 0;                                   // vo_fetch_gaussian now reads this scale space (set 0)
-    c->sel_used[0] = false;
+    c->set[0].sel_used = false;
     c->described = true;                               // ... and the fetches of a detecting call have nothing to read
     // row i of image k for point i: full rows-of-stride copies where every image fills its stride
     // (one image always does), else image by image, leaving the rows beyond n_pts[i] untouched
     bool full = true;
     for (int i = 0; i < n_img; ++i) full = full && n_pts[i] == pts_stride;
     if (full) {
-        HIPC(c, hipMemcpy2DAsync(desc, (size_t)pts_stride * VO_DESC_LEN, c->sb.desc, (size_t)K * VO_DESC_LEN,
+        HIPC(c, hipMemcpy2DAsync(desc, (size_t)pts_stride * VO_DESC_LEN, c->set[0].sb.desc, (size_t)K * VO_DESC_LEN,
                                  (size_t)pts_stride * VO_DESC_LEN, n_img, hipMemcpyDeviceToHost, c->stream));
     } else {
         for (int i = 0; i < n_img; ++i)
             if (n_pts[i] > 0)
-                HIPC(c, hipMemcpyAsync(desc + (size_t)i * pts_stride * VO_DESC_LEN, c->sb.desc + (size_t)i * K * VO_DESC_LEN,
+                HIPC(c, hipMemcpyAsync(desc + (size_t)i * pts_stride * VO_DESC_LEN, c->set[0].sb.desc + (size_t)i * K * VO_DESC_LEN,
                                        (size_t)n_pts[i] * VO_DESC_LEN, hipMemcpyDeviceToHost, c->stream));
     }
     return finish(c);
@@ -806,9 +795,33 @@ int vo_fetch_rectified(vo_ctx* c, int image, uint8_t* out, int capacity)
     if (capacity < 0 || (size_t)capacity < fs) return fail(c, VO_ERR_CAPACITY, "vo_fetch_rectified: capacity %d < %zu", capacity, fs);
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
+    HIPC(c, hipEventSynchronize(c->set[c->last_set].ev_done));
     const uint8_t* src = c->d_rect + ((size_t)(image & 1) * c->max_batch + (image >> 1)) * fs;
     HIPC(c, hipMemcpy(out, src, fs, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
+// The vo_fetch_* entries' shared start: wait for the last call's results, then pick the buffer set
+// that holds image slot `image`.  Image slots below 2 * max_batch (and the frames' pair slots with
+// them) are read from the last call's set (last_set: either set holds whole batches); the two carry
+// slots, 2 * max_batch and 2 * max_batch + 1, always from set 0.
+static int fetch_set(vo_ctx* c, int image, vo_ctx::BufferSet** S)
+{
+    hipSetDevice(c->device);
+    HIPC(c, hipStreamSynchronize(c->stream));
+    HIPC(c, hipEventSynchronize(c->set[c->last_set].ev_done));
+    *S = &c->set[image < 2 * c->max_batch ? c->last_set : 0];
+    return VO_OK;
+}
+
+// m accepted pairs from two device index arrays as rows of 1-based (i, j)
+static int read_pairs(vo_ctx* c, const int* d_i, const int* d_j, int m, uint32_t* pairs)
+{
+    if (m <= 0 || !pairs) return VO_OK;
+    std::vector<int> ii(m), jj(m);
+    HIPC(c, hipMemcpy(ii.data(), d_i, sizeof(int) * m, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(jj.data(), d_j, sizeof(int) * m, hipMemcpyDeviceToHost));
+    for (int k = 0; k < m; ++k) { pairs[2 * k] = (uint32_t)ii[k] + 1; pairs[2 * k + 1] = (uint32_t)jj[k] + 1; }
     return VO_OK;
 }
 
@@ -821,8 +834,7 @@ int vo_set_strongest(vo_ctx* c, int n)
     if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_set_strongest: step batches pending (vo_step_collect first)");
     if (n > 0) {
         hipSetDevice(c->device);
-        HIPC(c, sift_alloc_select(c->sb));
-        HIPC(c, sift_alloc_select(c->aux.sb));
+        for (int k = 0; k < 2; ++k) HIPC(c, sift_alloc_select(c->set[k].sb));
     }
     c->strongest = n;
     return VO_OK;
@@ -830,15 +842,13 @@ int vo_set_strongest(vo_ctx* c, int n)
 
 int vo_fetch_detected_count(vo_ctx* c, int image, int* n_detected)
 {
-    if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_detected_count: bad image");
+    if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_detected_count: bad image");
     if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_detected_count: the last call described given points and detected nothing");
-    hipSetDevice(c->device);
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
-    const bool aux = c->last_set == 1 && image < 2 * c->max_batch;
-    const SiftBuffers& B = aux ? c->aux.sb : c->sb;
+    vo_ctx::BufferSet* S = nullptr;
+    int rc = fetch_set(c, image, &S);
+    if (rc) return rc;
     int cnt = 0;
-    HIPC(c, hipMemcpy(&cnt, (c->sel_used[aux ? 1 : 0] ? B.n_det : B.n_kp) + image, sizeof(int), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&cnt, (S->sel_used ? S->sb.n_det : S->sb.n_kp) + image, sizeof(int), hipMemcpyDeviceToHost));
     if (n_detected) *n_detected = cnt;
     return VO_OK;
 }
@@ -850,19 +860,13 @@ static int match_staged(vo_ctx* c, int n1, int n2, uint32_t* pairs, int capacity
     HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
     desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
-    match_launch(c->mb, c->d_jobs + job_single(c), 1, c->mp, c->stream);
+    match_launch(c->set[0].mb, c->d_job_single, 1, c->mp, c->stream);
     int P = 0;
     HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     int rc = finish(c);
     if (rc) return rc;
     if (n_pairs) *n_pairs = P;
-    int m = std::min(P, capacity);
-    if (m > 0 && pairs) {
-        std::vector<int> ii(m), jj(m);
-        HIPC(c, hipMemcpy(ii.data(), c->d_mi, sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(jj.data(), c->d_mj, sizeof(int) * m, hipMemcpyDeviceToHost));
-        for (int k = 0; k < m; ++k) { pairs[2 * k] = (uint32_t)ii[k] + 1; pairs[2 * k + 1] = (uint32_t)jj[k] + 1; }
-    }
+    if ((rc = read_pairs(c, c->d_mi, c->d_mj, std::min(P, capacity), pairs))) return rc;
     if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
     return VO_OK;
 }
@@ -870,7 +874,7 @@ static int match_staged(vo_ctx* c, int n1, int n2, uint32_t* pairs, int capacity
 int vo_match(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, uint32_t* pairs, int capacity, int* n_pairs)
 {
     if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "vo_match: bad arguments");
-    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match: more rows than max_keypoints");
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match: more rows than max_keypoints");
     BEGIN_CALL(c);
     if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
     if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
@@ -886,7 +890,7 @@ static int stage_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F
         return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
     if ((n1 && ld1 < (col_major ? n1 : VO_DESC_LEN)) || (n2 && ld2 < (col_major ? n2 : VO_DESC_LEN)))
         return fail(c, VO_ERR_ARG, "%s: leading dimension too small", who);
-    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
     BEGIN_CALL(c);
     HIPC(c, hipMemsetAsync(c->d_bad, 0, sizeof(int), c->stream));
     const float* src[2] = {F1, F2};
@@ -895,7 +899,7 @@ static int stage_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F
         if (!n[s]) continue;
         // the matrix as it lies in host memory (MATLAB: n x 128 column-major, ld = n), one copy
         const size_t elems = col_major ? (size_t)ld[s] * (VO_DESC_LEN - 1) + n[s] : (size_t)ld[s] * (n[s] - 1) + VO_DESC_LEN;
-        if (elems > (size_t)c->sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "%s: matrix exceeds staging", who);
+        if (elems > (size_t)c->set[0].sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "%s: matrix exceeds staging", who);
         HIPC(c, hipMemcpyAsync(c->d_ff[s], src[s], sizeof(float) * elems, hipMemcpyHostToDevice, c->stream));
         pack_f32_desc_launch(c->d_ff[s], n[s], ld[s], col_major, c->d_fd[s], c->d_bad, c->stream);
     }
@@ -909,11 +913,11 @@ static int f32_buffers(vo_ctx* c, const char* who)
     if (c->d_fa && c->d_fbt && c->d_fres) return VO_OK;
     // all three or none: a failed allocation leaves the context without any of them, so the
     // next call allocates again instead of launching on a null buffer
-    const size_t fb = sizeof(float) * (size_t)c->sb.kp_cap * VO_DESC_LEN;
+    const size_t fb = sizeof(float) * (size_t)c->set[0].sb.kp_cap * VO_DESC_LEN;
     float* fa = nullptr; float* fbt = nullptr; int* fres = nullptr;
     hipError_t e;
     if ((e = hipMalloc((void**)&fa, fb)) != hipSuccess || (e = hipMalloc((void**)&fbt, fb)) != hipSuccess ||
-        (e = hipMalloc((void**)&fres, sizeof(int) * c->sb.kp_cap)) != hipSuccess) {
+        (e = hipMalloc((void**)&fres, sizeof(int) * c->set[0].sb.kp_cap)) != hipSuccess) {
         hipFree(fa); hipFree(fbt); hipFree(fres);
         return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     }
@@ -974,7 +978,7 @@ static int match_ex_buffers(vo_ctx* c, const char* who)
     memset(&J, 0, sizeof(J));
     J.d1 = c->d_fd[1]; J.m1 = c->d_fm[1]; J.n1 = c->d_fn + 1;
     J.d2 = c->d_fd[0]; J.m2 = c->d_fm[0]; J.n2 = c->d_fn;
-    const hipError_t e = match_ex_alloc(c->mx, c->mb, J);
+    const hipError_t e = match_ex_alloc(c->mx, c->set[0].mb, J);
     if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return VO_OK;
 }
@@ -989,19 +993,14 @@ static int match_staged_ex(vo_ctx* c, int n1, int n2, const vo_match_params& p, 
     HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
     desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
-    match_launch_ex(c->mb, c->d_jobs + job_single(c), c->mx, p, unique, c->stream);
+    match_launch_ex(c->set[0].mb, c->d_job_single, c->mx, p, unique, c->stream);
     int P = 0;
     HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     rc = finish(c);
     if (rc) return rc;
     if (n_pairs) *n_pairs = P;
     const int m = std::min(P, capacity);
-    if (m > 0 && pairs) {
-        std::vector<int> ii(m), jj(m);
-        HIPC(c, hipMemcpy(ii.data(), c->d_mi, sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(jj.data(), c->d_mj, sizeof(int) * m, hipMemcpyDeviceToHost));
-        for (int k = 0; k < m; ++k) { pairs[2 * k] = (uint32_t)ii[k] + 1; pairs[2 * k + 1] = (uint32_t)jj[k] + 1; }
-    }
+    if ((rc = read_pairs(c, c->d_mi, c->d_mj, m, pairs))) return rc;
     if (m > 0 && metric) HIPC(c, hipMemcpy(metric, c->mx.metric, sizeof(float) * m, hipMemcpyDeviceToHost));
     if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
     return VO_OK;
@@ -1015,7 +1014,7 @@ int vo_match_ex(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2,
     int unique = 0;
     int rc = match_opts_resolve(c, opts, &p, &unique, "vo_match_ex");
     if (rc) return rc;
-    if (n1 > c->sb.kp_cap || n2 > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match_ex: more rows than max_keypoints");
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match_ex: more rows than max_keypoints");
     BEGIN_CALL(c);
     if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
     if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
@@ -1061,8 +1060,6 @@ int vo_match_f32_ex(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2
     return VO_OK;
 }
 
-// SIFT + stereo match on B frames already in device memory.
-// buffers of set `set` of the asynchronous batch pipeline
 // vo_pair_stats.flags / vo_step_out.flags of one frame's n images: VO_FLAG_KEYPOINTS if an
 // image detected more keypoints than max_keypoints, VO_FLAG_CANDIDATES if its extremum test
 // (k_ext_inner's partial candidates included) produced more candidates than the list holds,
@@ -1075,19 +1072,6 @@ static int capacity_flags(const SiftBuffers& sb, const int* nkp, const int* ncan
         if (ncand[i] > sb.cand_cap) fl |= VO_FLAG_CANDIDATES;
     }
     return fl;
-}
-
-struct SetRef {
-    SiftBuffers* sb; MatchBuffers* mb; MatchJob* jobs; int* pair_i; int* pair_j; int* pair_n;
-    GeomBuffers* gb; MatchJob* track_jobs;
-};
-static SetRef set_ref(vo_ctx* c, int set)
-{
-    if (set == 0)
-        return {&c->sb, &c->mb, c->d_jobs + job_stereo(c, 0), c->d_pair_i, c->d_pair_j, c->d_pair_n, &c->gb,
-                c->d_jobs + job_track(c, 0, 0)};
-    return {&c->aux.sb, &c->aux.mb, c->aux.d_jobs, c->aux.pair_i, c->aux.pair_j, c->aux.pair_n, &c->aux.gb,
-            c->aux.d_jobs + job_track(c, 0, 0)};
 }
 
 // SIFT of 2B images + stereo matching of B frames into buffer set `set`.  The frames are
@@ -1129,7 +1113,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
 {
     const size_t fs = (size_t)c->rows * c->cols;
     const int parts = std::min(c->n_sub, B);
-    SetRef S = set_ref(c, set);
+    vo_ctx::BufferSet& S = c->set[set];
     hipStream_t sp = c->sub[0], st = c->sub[1];
     // (a synchronous profiled call -- bench.py's isolated pass -- keeps the scale space one chain
     // and starts the features after all of it, so its per-kernel durations stay undisturbed)
@@ -1145,11 +1129,11 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
     // the set's arena free: its previous call's last reader (k_desc) is done -- the stereo match
     // of that call (descriptors only) may still run; everything else of the set is written by st,
     // in order behind it
-    HIPC(c, hipStreamWaitEvent(sp, c->ev_arena[set], 0));
+    HIPC(c, hipStreamWaitEvent(sp, S.ev_arena, 0));
     const int o_small = sift_small_octave(c->py);
     const bool undist = c->ud_on[0] || c->ud_on[1];           // vo_set_distortion
     if (undist) c->rect_B = B;
-    c->sel_used[set] = c->strongest > 0;
+    S.sel_used = c->strongest > 0;
     // scale space on sp; octave 0's extremum test on st as soon as octave 0 is built (beside the
     // scale space of octaves 1..), the other octaves' on st after the scale space -- the split
     // that balances the two streams
@@ -1174,7 +1158,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
             pr = U[1].out;
         }
         ImageSrc src{pl, pr, fs, c->cols, 0};
-        SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
+        SiftBuffers v = sift_view(S.sb, c->py, 2 * f0, 2 * nf);
         ScaleChains ch;
         ch.down = sd;
         ch.ev_fork = c->ev_down[p];
@@ -1185,7 +1169,7 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
     }
     for (int p = 0; p < parts; ++p) {
         const int f0 = B * p / parts, nf = B * (p + 1) / parts - f0;
-        SiftBuffers v = sift_view(*S.sb, c->py, 2 * f0, 2 * nf);
+        SiftBuffers v = sift_view(S.sb, c->py, 2 * f0, 2 * nf);
         HIPC(c, hipStreamWaitEvent(st, iso ? c->ev_join[p] : c->ev_o0[p], 0));
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 0, 1);
         // the end of both chains (one chain gave both by ev_join alone)
@@ -1194,11 +1178,11 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, 1, o_small);
         sift_enqueue_extrema(c->py, v, 2 * nf, c->sp, st, c->d_py, o_small, c->py.n_oct);
         sift_enqueue_features(c->py, v, 2 * nf, c->sp, st, c->d_py, c->strongest);
-        if (p == parts - 1) HIPC(c, hipEventRecord(c->ev_arena[set], st));
-        match_launch(match_view(*S.mb, f0), S.jobs + f0, nf, c->mp, st);
+        if (p == parts - 1) HIPC(c, hipEventRecord(S.ev_arena, st));
+        match_launch(match_view(S.mb, f0), S.d_jobs + job_stereo(c, f0), nf, c->mp, st);
     }
-    HIPC(c, hipEventRecord(c->ev_done[set], st));
-    if (join) HIPC(c, hipStreamWaitEvent(c->stream, c->ev_done[set], 0));
+    HIPC(c, hipEventRecord(S.ev_done, st));
+    if (join) HIPC(c, hipStreamWaitEvent(c->stream, S.ev_done, 0));
     c->last_set = set;
     c->described = false;
     return VO_OK;
@@ -1220,22 +1204,22 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
         if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
         return VO_OK;
     }
-    SetRef S = set_ref(c, set);
+    const vo_ctx::BufferSet& S = c->set[set];
     std::vector<int> nk(2 * B), nc(2 * B), np(B);
     std::vector<int> nd;                     // detected counts: the flags' input (selection off: nk)
-    HIPC(c, hipMemcpyAsync(nk.data(), S.sb->n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(nk.data(), S.sb.n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     if (c->strongest > 0) {
         nd.resize(2 * B);
-        HIPC(c, hipMemcpyAsync(nd.data(), S.sb->n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(nd.data(), S.sb.n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     }
-    HIPC(c, hipMemcpyAsync(nc.data(), S.sb->n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(nc.data(), S.sb.n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(np.data(), S.pair_n, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     rc = finish(c);
     if (rc) return rc;
     if (stats) {
         for (int f = 0; f < B; ++f) {
             stats[f].n_left = nk[2 * f]; stats[f].n_right = nk[2 * f + 1]; stats[f].n_stereo = np[f];
-            stats[f].flags = capacity_flags(c->sb, (nd.empty() ? nk : nd).data() + 2 * f, nc.data() + 2 * f, 2);
+            stats[f].flags = capacity_flags(c->set[0].sb, (nd.empty() ? nk : nd).data() + 2 * f, nc.data() + 2 * f, 2);
         }
     }
     return VO_OK;
@@ -1243,13 +1227,12 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
 
 int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, int capacity, int* n)
 {
-    if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_keypoints: bad image");
+    if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_keypoints: bad image");
     if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_keypoints: the last call described given points and detected nothing");
-    hipSetDevice(c->device);
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
-    // batch results live in the last call's buffer set (set 1 holds stereo frames only)
-    const SiftBuffers& B = (c->last_set == 1 && image < 2 * c->max_batch) ? c->aux.sb : c->sb;
+    vo_ctx::BufferSet* S = nullptr;
+    int rc = fetch_set(c, image, &S);
+    if (rc) return rc;
+    const SiftBuffers& B = S->sb;
     int cnt = 0;
     HIPC(c, hipMemcpy(&cnt, B.n_kp + image, sizeof(int), hipMemcpyDeviceToHost));
     if (n) *n = cnt;
@@ -1263,12 +1246,12 @@ int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, in
 
 int vo_fetch_candidate_counts(vo_ctx* c, int image, int* n_cand, int* n_accepted)
 {
-    if (!c || image < 0 || image >= c->sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_candidate_counts: bad image");
+    if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_candidate_counts: bad image");
     if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_candidate_counts: the last call described given points and detected nothing");
-    hipSetDevice(c->device);
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
-    const SiftBuffers& B = (c->last_set == 1 && image < 2 * c->max_batch) ? c->aux.sb : c->sb;
+    vo_ctx::BufferSet* S = nullptr;
+    int rc = fetch_set(c, image, &S);
+    if (rc) return rc;
+    const SiftBuffers& B = S->sb;
     int v[2] = {0, 0};
     HIPC(c, hipMemcpy(&v[0], B.n_cand + image, sizeof(int), hipMemcpyDeviceToHost));
     HIPC(c, hipMemcpy(&v[1], B.n_acc + image, sizeof(int), hipMemcpyDeviceToHost));
@@ -1279,13 +1262,13 @@ int vo_fetch_candidate_counts(vo_ctx* c, int image, int* n_cand, int* n_accepted
 
 int vo_fetch_gaussian(vo_ctx* c, int image, int octave, int level, float* out, int capacity, int* rows, int* cols)
 {
-    if (!c || image < 0 || image >= c->sb.n_img || octave < 0 || octave >= c->py.n_oct || level < 0 ||
+    if (!c || image < 0 || image >= c->set[0].sb.n_img || octave < 0 || octave >= c->py.n_oct || level < 0 ||
         level >= c->py.L + 3)
         return fail(c, VO_ERR_ARG, "vo_fetch_gaussian: bad image/octave/level");
-    hipSetDevice(c->device);
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
-    const SiftBuffers& B = (c->last_set == 1 && image < 2 * c->max_batch) ? c->aux.sb : c->sb;
+    vo_ctx::BufferSet* S = nullptr;
+    int rc = fetch_set(c, image, &S);
+    if (rc) return rc;
+    const SiftBuffers& B = S->sb;
     const OctGeom& g = c->py.oct[octave];
     if (rows) *rows = g.rows;
     if (cols) *cols = g.cols;
@@ -1301,21 +1284,14 @@ int vo_fetch_stereo_pairs(vo_ctx* c, int frame, uint32_t* pairs, int capacity, i
 {
     if (!c || frame < 0 || frame >= c->max_batch) return fail(c, VO_ERR_ARG, "vo_fetch_stereo_pairs: bad frame");
     if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_stereo_pairs: the last call described given points and detected nothing");
-    hipSetDevice(c->device);
-    HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipEventSynchronize(c->ev_done[c->last_set]));
-    SetRef S = set_ref(c, c->last_set);
+    vo_ctx::BufferSet* S = nullptr;
+    int rc = fetch_set(c, 2 * frame, &S);                  // the frame's images and its pair slot: one set
+    if (rc) return rc;
     int P = 0;
-    HIPC(c, hipMemcpy(&P, S.pair_n + frame, sizeof(int), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&P, S->pair_n + frame, sizeof(int), hipMemcpyDeviceToHost));
     if (n) *n = P;
-    int m = std::min(P, capacity);
-    if (m > 0 && pairs) {
-        std::vector<int> ii(m), jj(m);
-        HIPC(c, hipMemcpy(ii.data(), S.pair_i + (size_t)frame * c->sb.kp_cap, sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(jj.data(), S.pair_j + (size_t)frame * c->sb.kp_cap, sizeof(int) * m, hipMemcpyDeviceToHost));
-        for (int k = 0; k < m; ++k) { pairs[2 * k] = (uint32_t)ii[k] + 1; pairs[2 * k + 1] = (uint32_t)jj[k] + 1; }
-    }
-    return VO_OK;
+    const size_t row = (size_t)frame * S->sb.kp_cap;
+    return read_pairs(c, S->pair_i + row, S->pair_j + row, std::min(P, capacity), pairs);
 }
 
 }  // extern "C"
@@ -1333,11 +1309,11 @@ static vo_calib calib_of(const double P1[12], const double P2[12], const double*
 
 static StepArgs step_args(vo_ctx* c, int B, int set = 0)
 {
-    SetRef S = set_ref(c, set);
+    vo_ctx::BufferSet& S = c->set[set];
     StepArgs a;
-    a.sb = S.sb;
+    a.sb = &S.sb;
     a.pair_i = S.pair_i; a.pair_j = S.pair_j; a.pair_n = S.pair_n;
-    a.max_frames = c->max_batch; a.B = B; a.kp_cap = c->sb.kp_cap;
+    a.max_frames = c->max_batch; a.B = B; a.kp_cap = c->set[0].sb.kp_cap;
     a.first_has_prev = c->have_features ? 1 : 0;
     a.frame_index0 = c->frame_index;
     a.calib = c->calib;
@@ -1370,19 +1346,20 @@ static void lm_world(const double* pose, const float* X, double* out)
 // pair slot M), which frame 0 of the next batch tracks against.
 static int enqueue_carry(vo_ctx* c, int from, int f, int to)
 {
-    const int M = c->max_batch, K = c->sb.kp_cap;
-    SetRef A = set_ref(c, from), Z = set_ref(c, to);
+    const int M = c->max_batch, K = c->set[0].sb.kp_cap;
+    const vo_ctx::BufferSet& A = c->set[from];
+    const vo_ctx::BufferSet& Z = c->set[to];
     for (int side = 0; side < 2; ++side) {
         const int src = 2 * f + side, dst = 2 * M + side;
-        HIPC(c, hipMemcpyAsync(Z.sb->kp + (size_t)dst * K, A.sb->kp + (size_t)src * K, sizeof(vo_keypoint) * K,
+        HIPC(c, hipMemcpyAsync(Z.sb.kp + (size_t)dst * K, A.sb.kp + (size_t)src * K, sizeof(vo_keypoint) * K,
                                hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(Z.sb->desc + (size_t)dst * K * VO_DESC_LEN, A.sb->desc + (size_t)src * K * VO_DESC_LEN,
+        HIPC(c, hipMemcpyAsync(Z.sb.desc + (size_t)dst * K * VO_DESC_LEN, A.sb.desc + (size_t)src * K * VO_DESC_LEN,
                                (size_t)K * VO_DESC_LEN, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(Z.sb->meta + (size_t)dst * K, A.sb->meta + (size_t)src * K, sizeof(DescMeta) * K,
+        HIPC(c, hipMemcpyAsync(Z.sb.meta + (size_t)dst * K, A.sb.meta + (size_t)src * K, sizeof(DescMeta) * K,
                                hipMemcpyDeviceToDevice, c->stream));
-        HIPC(c, hipMemcpyAsync(Z.sb->n_kp + dst, A.sb->n_kp + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        HIPC(c, hipMemcpyAsync(Z.sb.n_kp + dst, A.sb.n_kp + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
         if (c->strongest > 0)
-            HIPC(c, hipMemcpyAsync(Z.sb->n_det + dst, A.sb->n_det + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+            HIPC(c, hipMemcpyAsync(Z.sb.n_det + dst, A.sb.n_det + src, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPC(c, hipMemcpyAsync(Z.pair_i + (size_t)M * K, A.pair_i + (size_t)f * K, sizeof(int) * K, hipMemcpyDeviceToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(Z.pair_j + (size_t)M * K, A.pair_j + (size_t)f * K, sizeof(int) * K, hipMemcpyDeviceToDevice, c->stream));
@@ -1409,22 +1386,22 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     if (c->pending.size() >= VO_STEP_DEPTH)
         return fail(c, VO_ERR_STATE, "vo_step_submit_dev: %d batches already pending (collect first)", VO_STEP_DEPTH);
     const int set = c->next_step_set, slot = c->next_slot;
-    SetRef S = set_ref(c, set);
+    vo_ctx::BufferSet& S = c->set[set];
     for (const vo_ctx::Pending& q : c->pending)         // batch n-2 (same set), still in flight
         if (q.set == set) HIPC(c, hipStreamWaitEvent(c->sub[1], c->sh[q.slot].ev, 0));
     int rc = enqueue_sift_stereo(c, set, d_l, d_r, B, true, false, fork);   // `stream` waits for this set's SIFT
     if (rc) return rc;
     StepArgs a = step_args(c, B, set);
-    geom_enqueue(*S.gb, *S.mb, S.track_jobs, a, c->mp, c->stream);
+    geom_enqueue(S.gb, S.mb, S.d_jobs + job_track(c, 0, 0), a, c->mp, c->stream);
     vo_ctx::StepHost& H = c->sh[slot];
-    HIPC(c, hipMemcpyAsync(H.fg, S.gb->fg, sizeof(FrameGeom) * B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(H.nkp, S.sb->n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(H.fg, S.gb.fg, sizeof(FrameGeom) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(H.nkp, S.sb.n_kp, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     if (c->strongest > 0)
-        HIPC(c, hipMemcpyAsync(H.ndet, S.sb->n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(H.ncand, S.sb->n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(H.ndet, S.sb.n_det, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(H.ncand, S.sb.n_cand, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(H.np, S.pair_n, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(H.rows, S.gb->lm_rows, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
-    lm_pack_launch(*S.gb, B, H.d_pX, H.d_pkeep, c->stream);
+    HIPC(c, hipMemcpyAsync(H.rows, S.gb.lm_rows, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
+    lm_pack_launch(S.gb, B, H.d_pX, H.d_pkeep, c->stream);
     if ((rc = enqueue_carry(c, set, B - 1, set ^ 1))) return rc;
     HIPC(c, hipEventRecord(H.ev, c->stream));
     hipError_t e = hipGetLastError();
@@ -1442,7 +1419,7 @@ static int collect_batch(vo_ctx* c, vo_step_out* outs, int capacity, int* n_out)
     if (c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_step_collect: no batch pending");
     const vo_ctx::Pending P = c->pending.front();
     if (capacity < P.B) return fail(c, VO_ERR_CAPACITY, "vo_step_collect: %d frames pending, capacity %d", P.B, capacity);
-    const int K = c->sb.kp_cap, B = P.B;
+    const int K = c->set[0].sb.kp_cap, B = P.B;
     const vo_ctx::StepHost& H = c->sh[P.slot];
     if (c->prof.on) {                                  // profiling: events of every stream are collected
         g_prof = &c->prof;
@@ -1505,7 +1482,7 @@ static int collect_batch(vo_ctx* c, vo_step_out* outs, int capacity, int* n_out)
         vo_step_out& o = outs[f];
         memset(&o, 0, sizeof(o));
         o.n_left = H.nkp[2 * f]; o.n_right = H.nkp[2 * f + 1]; o.n_stereo = H.np[f];
-        o.flags = capacity_flags(c->sb, (P.sel ? H.ndet : H.nkp) + 2 * f, H.ncand + 2 * f, 2);
+        o.flags = capacity_flags(c->set[0].sb, (P.sel ? H.ndet : H.nkp) + 2 * f, H.ncand + 2 * f, 2);
         memcpy(o.rel_pose, I4, sizeof(I4));
         const bool tracked = f > 0 || P.first_tracked;
         if (c->lm_camera) {
@@ -1615,11 +1592,11 @@ int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* wo
         if (q.set == c->last_step_set)
             return fail(c, VO_ERR_STATE, "vo_fetch_tracks: the collected batch's buffer set is reused by a pending batch");
     hipSetDevice(c->device);
-    SetRef S = set_ref(c, c->last_step_set);
-    const int K = c->sb.kp_cap;
+    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    const int K = c->set[0].sb.kp_cap;
     int n = 0, nd = 0;
-    HIPC(c, hipMemcpy(&n, S.gb->list_n + 4 * frame + 3, sizeof(int), hipMemcpyDeviceToHost));
-    HIPC(c, hipMemcpy(&nd, S.sb->n_kp + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&n, S.gb.list_n + 4 * frame + 3, sizeof(int), hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(&nd, S.sb.n_kp + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
     n = std::min(std::max(n, 0), K);
     nd = std::min(std::max(nd, 0), K);
     if (n_tracked) *n_tracked = n;
@@ -1628,9 +1605,9 @@ int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* wo
     if (m > 0 && (old_l || cur_l || world)) {
         std::vector<float> op((size_t)m * 4);
         std::vector<double> ip((size_t)m * 2);
-        HIPC(c, hipMemcpy(op.data(), S.gb->oldpos + (size_t)frame * K * 4, sizeof(float) * 4 * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(ip.data(), S.gb->imgpt + (size_t)frame * K * 2, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
-        if (world) HIPC(c, hipMemcpy(world, S.gb->world + (size_t)frame * K * 3, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(op.data(), S.gb.oldpos + (size_t)frame * K * 4, sizeof(float) * 4 * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(ip.data(), S.gb.imgpt + (size_t)frame * K * 2, sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+        if (world) HIPC(c, hipMemcpy(world, S.gb.world + (size_t)frame * K * 3, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
         for (int k = 0; k < m; ++k) {
             if (old_l) { old_l[2 * k] = op[4 * k]; old_l[2 * k + 1] = op[4 * k + 1]; }
             if (cur_l) { cur_l[2 * k] = (float)ip[2 * k]; cur_l[2 * k + 1] = (float)ip[2 * k + 1]; }
@@ -1638,7 +1615,7 @@ int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* wo
     }
     if (det && md > 0) {
         std::vector<vo_keypoint> kp(md);
-        HIPC(c, hipMemcpy(kp.data(), S.sb->kp + (size_t)(2 * frame) * K, sizeof(vo_keypoint) * md, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(kp.data(), S.sb.kp + (size_t)(2 * frame) * K, sizeof(vo_keypoint) * md, hipMemcpyDeviceToHost));
         for (int k = 0; k < md; ++k) { det[2 * k] = kp[k].x; det[2 * k + 1] = kp[k].y; }
     }
     return VO_OK;
@@ -1775,8 +1752,7 @@ int vo_reset(vo_ctx* c)
     c->landmarks.clear();
     c->lm_n = 0;
     c->lm_frame_off.assign(1, 0);
-    HIPC(c, hipMemset(c->d_pair_n + c->max_batch, 0, sizeof(int)));
-    HIPC(c, hipMemset(c->aux.pair_n + c->max_batch, 0, sizeof(int)));
+    for (int k = 0; k < 2; ++k) HIPC(c, hipMemset(c->set[k].pair_n + c->max_batch, 0, sizeof(int)));
     return VO_OK;
 }
 
@@ -1791,10 +1767,10 @@ int vo_set_frame_index(vo_ctx* c, long frame_index)
 // loop state of vo_step (call vo_reset before stepping again).
 static int upload_desc(vo_ctx* c, int slot, const uint8_t* d, int n)
 {
-    const int K = c->sb.kp_cap;
-    if (n) HIPC(c, hipMemcpyAsync(c->sb.desc + (size_t)slot * K * VO_DESC_LEN, d, (size_t)n * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
-    desc_meta_launch(c->sb.desc + (size_t)slot * K * VO_DESC_LEN, c->sb.meta + (size_t)slot * K, n, c->stream);
-    HIPC(c, hipMemcpyAsync(c->sb.n_kp + slot, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int K = c->set[0].sb.kp_cap;
+    if (n) HIPC(c, hipMemcpyAsync(c->set[0].sb.desc + (size_t)slot * K * VO_DESC_LEN, d, (size_t)n * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    desc_meta_launch(c->set[0].sb.desc + (size_t)slot * K * VO_DESC_LEN, c->set[0].sb.meta + (size_t)slot * K, n, c->stream);
+    HIPC(c, hipMemcpyAsync(c->set[0].sb.n_kp + slot, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));   // &n is a stack value
     return VO_OK;
 }
@@ -1803,12 +1779,12 @@ int vo_track(vo_ctx* c, const uint8_t* old_l, const uint8_t* old_r, int n_old, c
              const uint8_t* cur_r, int n_cr, uint32_t* idx_out, int capacity, int* K_out)
 {
     if (!c || n_old < 0 || n_cl < 0 || n_cr < 0) return fail(c, VO_ERR_ARG, "vo_track: bad arguments");
-    const int K = c->sb.kp_cap, M = c->max_batch;
+    const int K = c->set[0].sb.kp_cap, M = c->max_batch;
     if (n_old > K || n_cl > K || n_cr > K) return fail(c, VO_ERR_CAPACITY, "vo_track: more rows than max_keypoints");
     BEGIN_CALL(c);
     c->have_features = false;
     c->last_set = 0;                                   // set 0's descriptor slots are overwritten
-    c->sel_used[0] = false;
+    c->set[0].sel_used = false;
     int rc;
     if ((rc = upload_desc(c, 2 * M, old_l, n_old))) return rc;
     if ((rc = upload_desc(c, 2 * M + 1, old_r, n_old))) return rc;
@@ -1817,23 +1793,23 @@ int vo_track(vo_ctx* c, const uint8_t* old_l, const uint8_t* old_r, int n_old, c
     std::vector<int> iota(std::max(n_old, 1));
     for (int k = 0; k < n_old; ++k) iota[k] = k;
     if (n_old) {
-        HIPC(c, hipMemcpy(c->d_pair_i + (size_t)M * K, iota.data(), sizeof(int) * n_old, hipMemcpyHostToDevice));
-        HIPC(c, hipMemcpy(c->d_pair_j + (size_t)M * K, iota.data(), sizeof(int) * n_old, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->set[0].pair_i + (size_t)M * K, iota.data(), sizeof(int) * n_old, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(c->set[0].pair_j + (size_t)M * K, iota.data(), sizeof(int) * n_old, hipMemcpyHostToDevice));
     }
-    HIPC(c, hipMemcpy(c->d_pair_n + M, &n_old, sizeof(int), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(c->set[0].pair_n + M, &n_old, sizeof(int), hipMemcpyHostToDevice));
     StepArgs a = step_args(c, 1);
-    track_enqueue(c->gb, c->mb, c->d_jobs + job_track(c, 0, 0), a, c->mp, c->stream);
+    track_enqueue(c->set[0].gb, c->set[0].mb, c->set[0].d_jobs + job_track(c, 0, 0), a, c->mp, c->stream);
     int n = 0;
-    HIPC(c, hipMemcpyAsync(&n, c->gb.list_n + 3, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&n, c->set[0].gb.list_n + 3, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     rc = finish(c);
     if (rc) return rc;
     if (K_out) *K_out = n;
     const int m = std::min(n, capacity);
     if (m > 0 && idx_out) {
         std::vector<int> ol(m), cl(m), cr(m);
-        HIPC(c, hipMemcpy(ol.data(), track_list(c->gb, 0, TL_OLF), sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(cl.data(), track_list(c->gb, 0, TL_CLF), sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPC(c, hipMemcpy(cr.data(), track_list(c->gb, 0, TL_CRF), sizeof(int) * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(ol.data(), track_list(c->set[0].gb, 0, TL_OLF), sizeof(int) * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(cl.data(), track_list(c->set[0].gb, 0, TL_CLF), sizeof(int) * m, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(cr.data(), track_list(c->set[0].gb, 0, TL_CRF), sizeof(int) * m, hipMemcpyDeviceToHost));
         for (int k = 0; k < m; ++k) {
             idx_out[3 * k] = (uint32_t)ol[k] + 1;
             idx_out[3 * k + 1] = (uint32_t)cl[k] + 1;
@@ -1849,7 +1825,7 @@ int vo_triangulate(vo_ctx* c, const float* x1, const float* x2, int n, const dou
     if (!c || n < 0 || (n && (!x1 || !x2 || !X)) || !P1 || !P2) return fail(c, VO_ERR_ARG, "vo_triangulate: bad arguments");
     BEGIN_CALL(c);
     const vo_calib cal = calib_of(P1, P2, nullptr);
-    const int K = c->sb.kp_cap;
+    const int K = c->set[0].sb.kp_cap;
     std::vector<float> q((size_t)std::min(n, K) * 4 + 4);
     for (int b = 0; b < n; b += K) {
         const int m = std::min(K, n - b);
@@ -1857,9 +1833,9 @@ int vo_triangulate(vo_ctx* c, const float* x1, const float* x2, int n, const dou
             q[4 * k] = x1[2 * (b + k)]; q[4 * k + 1] = x1[2 * (b + k) + 1];
             q[4 * k + 2] = x2[2 * (b + k)]; q[4 * k + 3] = x2[2 * (b + k) + 1];
         }
-        HIPC(c, hipMemcpyAsync(c->gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
-        triangulate_launch(c->gb.oldpos, m, cal, c->gb.world, c->stream);
-        HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, c->gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(c->set[0].gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
+        triangulate_launch(c->set[0].gb.oldpos, m, cal, c->set[0].gb.world, c->stream);
+        HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, c->set[0].gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
         int rc = finish(c);
         if (rc) return rc;
         g_prof = c->prof.on ? &c->prof : nullptr;
@@ -1872,22 +1848,22 @@ int vo_estworldpose(vo_ctx* c, const double* img, const double* world, int n, co
                     const vo_ransac_params* params, uint32_t frame_key, double T[16], uint8_t* inliers, int* n_inliers)
 {
     if (!c || n < 0 || (n && (!img || !world)) || !K9 || !T) return fail(c, VO_ERR_ARG, "vo_estworldpose: bad arguments");
-    if (n > c->sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_estworldpose: %d points exceed max_keypoints", n);
+    if (n > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_estworldpose: %d points exceed max_keypoints", n);
     const vo_ransac_params rp = params ? *params : c->rp;
-    if (rp.max_num_trials > c->gb.n_hyp)
+    if (rp.max_num_trials > c->set[0].gb.n_hyp)
         return fail(c, VO_ERR_ARG, "vo_estworldpose: MaxNumTrials %d exceeds the context's %d hypothesis slots (vo_create ransac.max_num_trials)",
-                    rp.max_num_trials, c->gb.n_hyp);
+                    rp.max_num_trials, c->set[0].gb.n_hyp);
     if (n_inliers) *n_inliers = 0;
     if (n < 4) return fail(c, VO_ERR_TOO_FEW_POINTS, "estworldpose: need at least 4 points, got %d", n);
     BEGIN_CALL(c);
     c->have_features = false;
-    HIPC(c, hipMemcpyAsync(c->gb.imgpt, img, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->gb.world, world, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].gb.imgpt, img, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].gb.world, world, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_fn, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    estworldpose_launch(c->gb, c->gb.imgpt, c->gb.world, c->d_fn, K9, rp, frame_key, c->stream);
+    estworldpose_launch(c->set[0].gb, c->set[0].gb.imgpt, c->set[0].gb.world, c->d_fn, K9, rp, frame_key, c->stream);
     FrameGeom g;
-    HIPC(c, hipMemcpyAsync(&g, c->gb.fg, sizeof(g), hipMemcpyDeviceToHost, c->stream));
-    if (inliers) HIPC(c, hipMemcpyAsync(inliers, c->gb.inliers, n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&g, c->set[0].gb.fg, sizeof(g), hipMemcpyDeviceToHost, c->stream));
+    if (inliers) HIPC(c, hipMemcpyAsync(inliers, c->set[0].gb.inliers, n, hipMemcpyDeviceToHost, c->stream));
     int rc = finish(c);
     if (rc) return rc;
     memcpy(T, g.T, sizeof(g.T));
@@ -1903,7 +1879,7 @@ int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const
     if (!c || S < 0 || Kn < 0 || !pose || (S && (!l_pos || !r_pos)) || (Kn && (!old_l || !old_r)))
         return fail(c, VO_ERR_ARG, "vo_landmarks: bad arguments");
     if (!c->has_calib) return fail(c, VO_ERR_STATE, "vo_landmarks: no calibration");
-    const int K = c->sb.kp_cap;
+    const int K = c->set[0].sb.kp_cap;
     if (S > K || Kn > K) return fail(c, VO_ERR_CAPACITY, "vo_landmarks: more rows than max_keypoints");
     BEGIN_CALL(c);
     c->have_features = false;
@@ -1911,19 +1887,19 @@ int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const
     for (int j = 0; j < S; ++j) { sp[4 * j] = l_pos[2 * j]; sp[4 * j + 1] = l_pos[2 * j + 1]; sp[4 * j + 2] = r_pos[2 * j]; sp[4 * j + 3] = r_pos[2 * j + 1]; }
     for (int k = 0; k < Kn; ++k) { op[4 * k] = old_l[2 * k]; op[4 * k + 1] = old_l[2 * k + 1]; op[4 * k + 2] = old_r[2 * k]; op[4 * k + 3] = old_r[2 * k + 1]; }
     int cnt[2] = {S, Kn};
-    HIPC(c, hipMemcpyAsync(c->gb.spos, sp.data(), sizeof(float) * 4 * S, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->gb.oldpos, op.data(), sizeof(float) * 4 * Kn, hipMemcpyHostToDevice, c->stream));
-    HIPC(c, hipMemcpyAsync(c->gb.s_n, &cnt[0], sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].gb.spos, sp.data(), sizeof(float) * 4 * S, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].gb.oldpos, op.data(), sizeof(float) * 4 * Kn, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->set[0].gb.s_n, &cnt[0], sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_fn, &cnt[1], sizeof(int), hipMemcpyHostToDevice, c->stream));
-    landmarks_launch(c->gb, c->d_fn, c->calib, c->stream);
+    landmarks_launch(c->set[0].gb, c->d_fn, c->calib, c->stream);
     int rows = 0;
-    HIPC(c, hipMemcpyAsync(&rows, c->gb.lm_rows, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&rows, c->set[0].gb.lm_rows, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     int rc = finish(c);
     if (rc) return rc;
     std::vector<float> X((size_t)rows * 3);
     std::vector<uint8_t> keep(rows);
-    HIPC(c, hipMemcpy(X.data(), c->gb.lm_X, sizeof(float) * 3 * rows, hipMemcpyDeviceToHost));
-    HIPC(c, hipMemcpy(keep.data(), c->gb.lm_keep, rows, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(X.data(), c->set[0].gb.lm_X, sizeof(float) * 3 * rows, hipMemcpyDeviceToHost));
+    HIPC(c, hipMemcpy(keep.data(), c->set[0].gb.lm_keep, rows, hipMemcpyDeviceToHost));
     if (rows_out) *rows_out = rows;
     if (out) {
         for (int m = 0; m < rows && m < capacity; ++m) {
@@ -1936,20 +1912,3 @@ int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const
 }
 
 }  // extern "C"
-
-#if VO_EXPERIMENTAL
-// ---------------------------------------------------------------------------
-// Test build only (libvo_exp.so, make exp): selects the eager MSAC kernels, which the product
-// library does not contain, so their parity test can run them against k_msac.  Process-wide;
-// read at enqueue.  The first argument selected the fused octave kernel (removed, last present
-// in c014ac4) and is ignored.
-// ---------------------------------------------------------------------------
-namespace vo {
-int g_exp_msac_eager = 0;
-}
-extern "C" int vo_exp_set(int /*fused_octave*/, int msac_eager)
-{
-    vo::g_exp_msac_eager = msac_eager ? 1 : 0;
-    return VO_OK;
-}
-#endif

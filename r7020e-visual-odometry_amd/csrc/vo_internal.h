@@ -222,11 +222,6 @@ struct UndistortSide {
 void undistort_launch(const UndistortSide* sides, int n_sides, int rows, int cols, int B, size_t in_stride,
                       size_t out_stride, hipStream_t s);
 
-#if VO_EXPERIMENTAL
-// test build only (libvo_exp.so): the eager MSAC kernels (geom.hip), selected by
-// vo_exp_set; the product libvo.so has neither the kernels nor a switch
-extern int g_exp_msac_eager;
-#endif
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize, 160 KB) once per (kernel, device)
 void raise_lds_limit(const void* fn);
 
@@ -249,7 +244,6 @@ struct MatchJob {
 struct MatchTop2 { float best; int idx; float second; int pad; };
 
 struct MatchBuffers {
-    MatchJob* jobs = nullptr;        // device copy of the jobs [max_jobs]
     MatchTop2* partial = nullptr;    // [max_jobs][n_chunks][row_cap]
     int max_jobs = 0, row_cap = 0, n_chunks = 0;
 };

@@ -112,11 +112,6 @@ EXPORTS = [
     "vo_check_points", "vo_describe", "vo_describe_batch",
 ]
 
-# the test build (csrc `make exp`, -DVO_EXPERIMENTAL=1): libvo plus the eager MSAC kernels kept
-# as a cross-check of k_msac, selected by its extra export vo_exp_set.  Only their parity test
-# loads it (load_experimental_library); the product path never does.
-EXP_LIBPATH = PKG / "lib" / "libvo_exp.so"
-
 _libs: dict = {}
 
 
@@ -209,24 +204,6 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_landmarks_world_dev.argtypes = [vp, P(C.c_double), C.c_int, vp, C.c_long, P(C.c_long)]
     L.vo_kernel_times.argtypes = [vp, P(C.c_char_p), P(C.c_double), P(C.c_int), C.c_int, P(C.c_int)]
     _libs[key] = L
-    return L
-
-
-def experimental_library_path() -> Path:
-    """libvo_exp.so beside the product library in use: the in-tree test build, or -- when
-    $VO_LIBPATH points at another libvo.so (a variant build) -- the libvo_exp.so next to it, so an
-    experimental cross-check compares a build with its own test build."""
-    lp = os.environ.get("VO_LIBPATH")
-    return Path(lp).resolve().parent / "libvo_exp.so" if lp else EXP_LIBPATH
-
-
-def load_experimental_library():
-    """The test build libvo_exp.so (experimental_library_path()) with `vo_exp_set(ignored,
-    msac_eager)` bound; pass it to Context(lib=...).  Raises VOError if it is not built."""
-    L = load_library(experimental_library_path())
-    if not hasattr(L, "vo_exp_set"):
-        raise VOError(VO_ERR_STATE, f"{experimental_library_path()} lacks vo_exp_set (not a VO_EXPERIMENTAL build)")
-    L.vo_exp_set.argtypes = [C.c_int, C.c_int]
     return L
 
 

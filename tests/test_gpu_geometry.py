@@ -2,8 +2,6 @@
 oracle: find_remaining_points (index sets), triangulate (f64 bit-exact),
 estworldpose (pose bit-exact, inlier masks bit-exact), landmarks, and the whole
 VO.m loop over a synthetic sequence (batched and frame-by-frame)."""
-import os
-
 import numpy as np
 import pytest
 
@@ -81,12 +79,11 @@ def test_estworldpose_bit_exact(vo, oracle, seed):
 
 
 @pytest.mark.parametrize("outlier_frac,max_trials", [(0.6, 1000), (0.75, 2048), (0.2, 10), (0.5, 100), (0.9, 130)])
-def test_estworldpose_lazy_chunks_equal_oracle_and_eager(vo, oracle, outlier_frac, max_trials):
+def test_estworldpose_lazy_chunks_equal_oracle(vo, oracle, outlier_frac, max_trials):
     """k_msac walks the slots in chunks of 64 and stops at the chunk where the adaptive replay
     stops: at high outlier ratios the replay runs over several chunks (or all of them), at
     small MaxNumTrials the last chunk is partial.  Results equal the oracle's sequential MSAC
-    and the eager kernels (every slot generated and scored; compiled only into the test build
-    libvo_exp.so, selected by vo_exp_set) bit for bit."""
+    over every slot (the eager algorithm) bit for bit."""
     rng = np.random.default_rng(int(outlier_frac * 100) + max_trials)
     uv, Xw, K = _pose_problem(rng, n=500, outlier_frac=outlier_frac)
     rp = vo.default_ransac_params()
@@ -94,22 +91,14 @@ def test_estworldpose_lazy_chunks_equal_oracle_and_eager(vo, oracle, outlier_fra
     orp = oracle.ransac_params()
     orp.max_num_trials = max_trials
     ref = oracle.estworldpose(uv, Xw, K, params=orp, frame_key=7)
-    if os.environ.get("VO_LIBPATH") and not vo.experimental_library_path().exists():
-        pytest.skip("variant build without its own libvo_exp.so")
-    exp = vo.load_experimental_library()
-    for eager, lib in ((0, None), (1, exp)):
-        ctx = vo.Context(375, 1242, 1, ransac=rp, lib=lib)
-        if lib is not None:
-            lib.vo_exp_set(0, 1)
-        try:
-            st, T, inl, nin = ctx.estworldpose(uv, Xw, K, params=rp, frame_key=7, raise_on_failure=False)
-        finally:
-            if lib is not None:
-                lib.vo_exp_set(0, 0)
-            ctx.close()
-        assert st == ref[0], (eager, st, ref[0])
-        if st == 0:
-            assert np.array_equal(T, ref[1]) and np.array_equal(inl, ref[2]) and nin == ref[3]
+    ctx = vo.Context(375, 1242, 1, ransac=rp)
+    try:
+        st, T, inl, nin = ctx.estworldpose(uv, Xw, K, params=rp, frame_key=7, raise_on_failure=False)
+    finally:
+        ctx.close()
+    assert st == ref[0], (st, ref[0])
+    if st == 0:
+        assert np.array_equal(T, ref[1]) and np.array_equal(inl, ref[2]) and nin == ref[3]
 
 
 def test_estworldpose_too_few_points(vo, oracle):

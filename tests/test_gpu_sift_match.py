@@ -45,6 +45,58 @@ def test_sift_match_batch_bit_exact(vo, oracle, syn):
         assert np.array_equal(pairs, ref)
 
 
+def test_fetches_follow_the_last_batch_onto_set_1(vo, oracle, syn):
+    """Batched calls alternate between the context's two buffer sets, and every vo_fetch_* reads
+    the set of the last call.  The same two pairs submitted twice: the second call lands on set 1,
+    where the keypoints, descriptors and stereo pairs equal the oracle's bit for bit and the
+    candidate counts, detected count and a Gaussian level equal what set 0 gave for the first."""
+    import torch
+    B, rows, cols = 2, 160, 240
+    L, R = syn.independent_pairs(B, rows, cols)
+    imgs = [L[0], R[0], L[1], R[1]]
+    ref = [oracle.sift(im) for im in imgs]
+    ref_pairs = [oracle.match(ref[2 * f][1], ref[2 * f + 1][1]) for f in range(B)]
+    assert min(len(k) for k, _ in ref) >= 100, [len(k) for k, _ in ref]
+    assert min(len(p) for p in ref_pairs) >= 10, [len(p) for p in ref_pairs]
+    dl = torch.from_numpy(L).cuda()
+    dr = torch.from_numpy(R).cuda()
+    torch.cuda.synchronize()
+    ctx = vo.Context(rows, cols, B)
+    ctx.set_strongest(0)
+
+    def side_fetches():
+        return (ctx.fetch_candidate_counts(3), ctx.fetch_detected_count(3), ctx.fetch_gaussian(3, 1, 2))
+
+    ctx.sift_match_batch_dev(dl.data_ptr(), dr.data_ptr(), B, stats=False)      # set 0
+    cand0, det0, g0 = side_fetches()
+    ctx.sift_match_batch_dev(dl.data_ptr(), dr.data_ptr(), B, stats=False)      # set 1
+    for i in range(2 * B):
+        k, d = ctx.fetch_keypoints(i)
+        _same_kps(k, ref[i][0])
+        assert np.array_equal(d, ref[i][1]), i
+    for f in range(B):
+        assert np.array_equal(ctx.fetch_stereo_pairs(f), ref_pairs[f]), f
+    cand1, det1, g1 = side_fetches()
+    assert cand1 == cand0 and cand0[0] > 0
+    assert det1 == det0 == len(ref[3][0])
+    assert g1.shape == g0.shape and np.array_equal(g1, g0) and g0.any()
+    # the two sets now hold the same results; the frames in the other order go to set 0, so a
+    # fetch that read the wrong set would return the other frame
+    sl = torch.from_numpy(L[::-1].copy()).cuda()
+    sr = torch.from_numpy(R[::-1].copy()).cuda()
+    torch.cuda.synchronize()
+    ctx.sift_match_batch_dev(sl.data_ptr(), sr.data_ptr(), B, stats=False)
+    assert len({len(k) for k, _ in ref}) == 2 * B                               # the images differ
+    for i in range(2 * B):
+        k, d = ctx.fetch_keypoints(i)
+        _same_kps(k, ref[i ^ 2][0])
+        assert np.array_equal(d, ref[i ^ 2][1]), i
+        assert ctx.fetch_detected_count(i) == len(ref[i ^ 2][0]), i
+    for f in range(B):
+        assert np.array_equal(ctx.fetch_stereo_pairs(f), ref_pairs[f ^ 1]), f
+    ctx.close()
+
+
 def test_match_host_bit_exact(vo, oracle):
     rng = np.random.default_rng(3)
     base = rng.integers(0, 120, (700, 128)).astype(np.uint8)
