@@ -6,7 +6,8 @@
 //                         (octave 0's base: x2 upsample of the u8 image fused); DoG planes
 //                         are never stored, D_i = G_{i+1} - G_i is formed where it is read
 //   k_base_src/k_blur_fused  the generic path (untabled radii, planes shorter than a band):
-//                         row + column passes through one LDS tile
+//                         the octave-0 source as a float plane, then row + column passes
+//                         through one LDS tile.  blur_plan.h decides between the two forms
 //   k_down                next octave base = G[o-1][L](2y, 2x), where the level-L blur did
 //                         not store it
 //   k_small_pyr           the LDS-sized octaves, every level, in one launch
@@ -25,6 +26,7 @@
 //                         (fixed-point LDS atomics), norms as a wave tree
 // Every float expression follows oracle/sift_ref.c operation for operation.
 #include "vo_internal.h"
+#include "blur_plan.h"
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
@@ -223,16 +225,15 @@ __global__ __launch_bounds__(256) void k_base_src(ImageSrc isrc, int in_rows, in
 }
 
 // ---------------------------------------------------------------------------
-// Fused separable blur of one scale level + DoG (one launch per level).
+// Tiled separable blur of one float plane per image (one launch per level).
 // A 64x64 output tile and its radius-r halo are staged once in LDS; the row
-// pass writes a (64+2r) x 64 LDS image, the column pass writes G_i and
-// D_{i-1} = G_i - G_{i-1} (G_{i-1} is the tile centre already in LDS).
+// pass writes a (64+2r) x 64 LDS image, the column pass writes G_i.
 // Register blocking: each thread produces 8 consecutive outputs along the
 // filter direction from 8+2r values loaded once (LDS reads / output ~10
 // instead of ~54).  RAD > 0 instantiates the radius (full unroll, static
 // register indices); RAD == 0 is the generic runtime-radius path.
-// MODE 0: float source plane (+DoG); 1: octave-0 base from the u8 image with
-// the x2 upsample computed on the fly; 2: octave-0 base from u8, no upsample.
+// The source is always a float plane: the octave-0 base reaches this kernel through
+// k_base_src's plane.
 // Accumulation order per output = oracle_blur: acc = k0*s0;
 // acc = fmaf(kj, s[-j] + s[+j], acc), j = 1..r (row pass, then column pass).
 // ---------------------------------------------------------------------------
@@ -244,10 +245,9 @@ __global__ __launch_bounds__(256) void k_base_src(ImageSrc isrc, int in_rows, in
 __host__ __device__ constexpr int ft_iw(int r) { return (FT_W + 2 * r + 3) & ~3; }   // padded to 16 B
 __host__ __device__ constexpr int ft_lds_floats(int r) { return (FT_H + 2 * r) * ft_iw(r) + (FT_H + 2 * r) * FT_HW; }
 
-template <int RAD, int MODE>
+template <int RAD>
 __global__ __launch_bounds__(256) void k_blur_fused(const float* __restrict__ src, size_t plane, size_t dplane, int pitch, int R, int C,
-                                                    float* __restrict__ g_out, float* __restrict__ d_out, Kern K,
-                                                    ImageSrc isrc, int in_rows, int in_cols)
+                                                    float* __restrict__ g_out, Kern K)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int r = RAD > 0 ? RAD : K.r;
@@ -255,8 +255,6 @@ __global__ __launch_bounds__(256) void k_blur_fused(const float* __restrict__ sr
     float* in = sm;
     float* hb = sm + IH * IW;
     const int img = blockIdx.z, x0 = blockIdx.x * FT_W, y0 = blockIdx.y * FT_H, tid = threadIdx.x;
-    const uint8_t* base8 = nullptr;
-    if (MODE != 0) base8 = ((img & 1) ? isrc.right : isrc.left) + (size_t)(img >> 1) * isrc.frame_stride;
     const float* srcp = src + img * plane;
     // ---- stage the input tile (reflect-101 only for tiles touching a border) ----
     const int LW = FT_W + 2 * r;
@@ -267,11 +265,7 @@ __global__ __launch_bounds__(256) void k_blur_fused(const float* __restrict__ sr
         const int y = interior ? ylo + rr : vo_reflect101(ylo + rr, R);
         for (int cc = lane; cc < LW; cc += 64) {
             const int x = interior ? xlo + cc : vo_reflect101(xlo + cc, C);
-            float v;
-            if (MODE == 0) v = srcp[(size_t)y * pitch + x];
-            else if (MODE == 1) v = up_sample(base8, isrc.ld, in_rows, in_cols, y, x);
-            else v = (float)base8[y * isrc.ld + x];
-            in[rr * IW + cc] = v;
+            in[rr * IW + cc] = srcp[(size_t)y * pitch + x];
         }
     }
     __syncthreads();
@@ -332,18 +326,14 @@ __global__ __launch_bounds__(256) void k_blur_fused(const float* __restrict__ sr
 #pragma unroll
             for (int i = 0; i < FT_V; ++i) {
                 const int y = y0 + y0l + i;
-                if (y < R) {
-                    const size_t o = img * dplane + (size_t)y * pitch + x;
-                    g_out[o] = out[i];
-                    if (MODE == 0 && d_out) d_out[o] = out[i] - in[(y0l + i + r) * IW + c + r];
-                }
+                if (y < R) g_out[img * dplane + (size_t)y * pitch + x] = out[i];
             }
         }
     }
 }
 
 // ---------------------------------------------------------------------------
-// Streaming level blur (MODE 0, compiled radius): one wave per (image, band of
+// Streaming level blur (compiled radius): one wave per (image, band of
 // TH output rows, strip of 256 columns).  The wave walks the band's TH + 2r
 // input rows top to bottom; each lane owns 4 consecutive columns.
 //   - input rows are prefetched P rows ahead into registers (one 16-B load per
@@ -386,9 +376,6 @@ __device__ inline int xcd_remap(int bid, int n)
     return xcd < rm ? xcd * (q + 1) + idx : rm * (q + 1) + (xcd - rm) * q + idx;
 }
 
-#define BS_P 4            // prefetch depth (rows); 6 for the octave-0 base measured the same
-
-
 // Scale-space kernels raise their wave priority.  The feature stream's kernels (k_desc,
 // k_orient) are VALU-bound and run beside the scale space of the next batch; a SIMD arbitrates
 // VALU issue by priority, then age, so a freshly dispatched blur wave next to older descriptor
@@ -400,8 +387,7 @@ __device__ __forceinline__ void vo_ss_prio()
 {
     if constexpr (VO_SS_SETPRIO > 0) __builtin_amdgcn_s_setprio(VO_SS_SETPRIO);
 }
-// halo floats each side, rounded up to whole CPL-column vectors; staged row length
-__host__ __device__ constexpr int bs_rh(int r, int cpl) { return (r + cpl - 1) / cpl * cpl; }
+// staged row length (bs_rh, blur_plan.h: halo floats each side)
 __host__ __device__ constexpr int bs_rw(int r, int cpl) { return 64 * cpl + 2 * bs_rh(r, cpl); }
 // Row-window exchange of the streaming blur.  Each lane holds CPL consecutive columns of the
 // input row; the row pass needs r columns either side.  Halo-lane layout (bs_hl: 4-column lanes,
@@ -412,13 +398,7 @@ __host__ __device__ constexpr int bs_rw(int r, int cpl) { return 64 * cpl + 2 * 
 // LDS exchange cost 2 ds_write_b128 (13 LDS cycles each, at half rate from one wave) + (1 +
 // 2 rh/4) ds_read_b128, which base_probe measured at ~180 of the octave-0 base kernel's ~430 us.
 // (r >= 6, and the r = 5 level with 2-column lanes, keep the LDS exchange: measured faster)
-constexpr int kBlurDppMaxR = 5;
-__host__ __device__ constexpr bool bs_hl(int r, int cpl, int tag)
-{
-    return cpl == 4 && r <= kBlurDppMaxR && !(tag & 32);
-}
-// output columns per strip
-__host__ __device__ constexpr int bs_sw(int r, int cpl, int tag) { return 64 * cpl - (bs_hl(r, cpl, tag) ? 2 * bs_rh(r, cpl) : 0); }
+// bs_hl and the strip's output columns bs_sw are in blur_plan.h, beside the grid they size.
 
 enum : int { VO_DPP_WAVE_SHL1 = 0x130, VO_DPP_WAVE_SHR1 = 0x138 };
 template <int CTRL>
@@ -462,10 +442,6 @@ __device__ __forceinline__ void vo_dpp_window(const vec_t& vm, float* w)
 // the P steps of 16-B stores issued before it -- the base kernel's stream of 1 GB of stores was
 // paced by its tiny u8 loads.  With the loads gone the loop never waits on vmcnt.
 struct U8Src { const uint8_t* p; int ld, rows, cols; };
-#ifndef VO_BASE_MAX_TH
-#define VO_BASE_MAX_TH 96         // 8.7 KB of staged rows: 16 one-wave workgroups per CU fit (128: 11.1 KB, 14)
-#endif
-constexpr int kBaseMaxTH = VO_BASE_MAX_TH;                    // band height bound of the staged form
 // staged row length in dwords: the upsampled span of a wave (64 CPL columns + 2 RH halo) needs
 // (64 CPL + 2 RH) / 2 + 3 source bytes; + 3 for the row's misalignment, + 4 for the word pair
 __host__ __device__ constexpr int bs_u8_dw(int r, int cpl) { return ((64 * cpl + 2 * bs_rh(r, cpl)) / 2 + 3 + 3 + 4 + 3) / 4; }
@@ -826,10 +802,10 @@ __device__ __forceinline__ void blur_stream_body(const float* __restrict__ sp, i
 #undef VO_BS_LOAD
 }
 
-// TAG: 0 level blur, 1 octave-0 base from a float plane, 5 octave-0 base with the x2
-// upsample of the u8 image fused (isrc); instrumentation variants used only by
-// tools/blur_probe.hip: 2 cached stores, 8 no row pass, 16 no column pass,
-// 32 no LDS staging, 64 no halo loads.  CPL: columns per lane (4 or 2).
+// TAG (named in blur_plan.h): 0 level blur, 1 octave-0 base from a float plane, 5 octave-0
+// base with the x2 upsample of the u8 image fused (isrc); instrumentation variants used only
+// by tools/blur_probe.hip and tools/base_probe.hip: 2 cached stores, 8 no row pass, 16 no
+// column pass, 32 no LDS staging, 64 no halo loads.  CPL: columns per lane (4 or 2).
 #ifndef VO_BLUR_OCC3_MAXR
 #define VO_BLUR_OCC3_MAXR 6       // radii up to this run at 3 waves per SIMD (168 VGPRs), larger at 2
 #endif
@@ -986,14 +962,14 @@ __global__ __launch_bounds__(VO_SMALL_T) void k_small_pyr(const Pyramid* __restr
             for (int t = tid; t < C + 2 * r; t += VO_SMALL_T) cidx[t] = vo_reflect101(t - r, C);
             __syncthreads();
             float* const gl = gplane + g.g_off[i];
-            switch (r) {                                                  // the default sigmas' radii
+            switch (r) {                                                  // the compiled radii
 #define VO_SMALL_R(RR)                                                                        \
     case RR:                                                                                  \
         small_pass<RR>(cur, tmp, nullptr, 0, R, C, true, kk, cidx, tid);                      \
         __syncthreads();                                                                      \
         small_pass<RR>(tmp, nxt, gl, g.pitch, R, C, false, kk, ridx, tid);                    \
         break;
-            VO_SMALL_R(5) VO_SMALL_R(6) VO_SMALL_R(8) VO_SMALL_R(10) VO_SMALL_R(13)
+            VO_BLUR_RADII(VO_SMALL_R)
 #undef VO_SMALL_R
             default:
                 for (int e = tid; e < RC; e += VO_SMALL_T) {                 // row pass
@@ -2352,84 +2328,45 @@ void raise_lds_limit(const void* fn)
     done.push_back({fn, dev});
 }
 
-// -> true when the streaming kernel ran (it stores K.nb, the next octave's base, if set)
-template <int RAD, int MODE>
-static bool launch_blur_r(dim3 grid, hipStream_t s, const float* src, size_t plane, size_t dplane, int pitch, int R, int C,
-                          float* g, float* d, const Kern& K, const ImageSrc& isrc, int in_rows, int in_cols, const char* name)
+// One blur of n_img planes as its plan (blur_plan.h) says.  Streamed: k_blur_stream, which also
+// stores K.nb, the next octave's base, if set; src == nullptr for the u8 base, which reads isrc.
+// Tiled: k_blur_fused, for kernel radii without a streaming instantiation and planes shorter than
+// one band (tiny images; GPU edge tests).  A streamed base is labelled "k_blur_base", every other
+// launch "k_blur_fused".
+template <int RAD>
+static void launch_blur_r(const BlurPlan& pl, int n_img, hipStream_t s, const float* src, size_t plane, size_t dplane, int pitch,
+                          int R, int C, float* g, const Kern& K, const ImageSrc& isrc, int in_rows, int in_cols)
 {
-    const size_t lds = sizeof(float) * ft_lds_floats(K.r);
-    if constexpr (MODE == 0 && RAD > 0) {
-        // band height: a multiple of P, at most 128 rows, lowered on small octaves until the
-        // launch has ~2048 waves (8 per CU; 1024 measured ~1.5 % slower) -- small planes are
-        // latency-bound.  Level blurs of planes at most 1400 columns wide use 2 columns per
-        // lane (128-column strips, half the ring registers): more waves and fewer idle lanes
-        // at the narrow octaves, where the kernel is latency-bound rather than HBM-bound.
-#ifndef VO_CPL2_MAXC
-#define VO_CPL2_MAXC 1400
-#endif
-#ifndef VO_BLUR_MAX_TH
-#define VO_BLUR_MAX_TH 128
-#endif
-#ifndef VO_BLUR_WAVES
-#define VO_BLUR_WAVES 2048
-#endif
-        constexpr int kMaxTH = VO_BLUR_MAX_TH, kWaveTarget = VO_BLUR_WAVES, kCpl2MaxC = VO_CPL2_MAXC;
-        const bool base = name[7] == 'b';
-        // (2 columns per lane for the octave-0 levels of radius >= 13 / 10 / 8 too -- fewer registers,
-        // so more of them fit beside the tracking matches of the full path: configs[1] -0.8 / -0.9 /
-        // -4.3 %, full path within noise, profiles/r06_v_ab_fullpath_cpl_refine.txt)
-        const int cpl = (!base && C <= kCpl2MaxC) ? 2 : 4;
-        const int n_strips = (C + 64 * cpl - 1) / (64 * cpl);
-        const long rows_total = (long)R * n_strips * grid.z;
-        // (the staged octave-0 base stages at most kBaseMaxTH-row bands: its LDS is sized for them)
-        int TH = (int)std::min<long>(base ? std::min(kMaxTH, kBaseMaxTH) : kMaxTH, rows_total / kWaveTarget);
-        TH = std::max(BS_P, TH / BS_P * BS_P);
-        if (R >= TH && R > RAD + BS_P + 2) {             // (one reflection fold per band edge)
-            const int n_bands = (R + TH - 1) / TH;
+    if constexpr (RAD > 0) {
+        if (pl.streamed) {
+            const char* name = pl.role == BlurRole::Level ? "k_blur_fused" : "k_blur_base";
 #define VO_BS_GO(T, CP)                                                                                        \
-    do {                                                                                                       \
-        const int ns_ = (C + bs_sw(RAD, CP, T) - 1) / bs_sw(RAD, CP, T);                                       \
-        VO_LAUNCH_NAMED(name, (k_blur_stream<RAD, T, CP>), dim3(ns_ * n_bands * (int)grid.z), dim3(64), 0, s, src, plane, \
-                        dplane, pitch, R, C, g, K, ns_, n_bands, TH, isrc, in_rows, in_cols);                     \
-    } while (0)
-            if (base && src == nullptr) VO_BS_GO(5, 4);      // "k_blur_base" from the u8 image (x2 upsample fused)
-            else if (base) VO_BS_GO(1, 4);
-            else if (cpl == 2) VO_BS_GO(0, 2);
-            else VO_BS_GO(0, 4);
+    VO_LAUNCH_NAMED(name, (k_blur_stream<RAD, T, CP>), dim3(pl.n_strips * pl.n_bands * n_img), dim3(64), 0, s, src, plane, \
+                    dplane, pitch, R, C, g, K, pl.n_strips, pl.n_bands, pl.th, isrc, in_rows, in_cols)
+            if (pl.tag == kTagBaseU8) VO_BS_GO(kTagBaseU8, 4);
+            else if (pl.tag == kTagBase) VO_BS_GO(kTagBase, 4);
+            else if (pl.cpl == 2) VO_BS_GO(kTagLevel, 2);
+            else VO_BS_GO(kTagLevel, 4);
 #undef VO_BS_GO
-            return true;
+            return;
         }
     }
-    // generic tiled form: kernel radii without a streaming instantiation, planes shorter than
-    // one band (tiny images; GPU edge tests), and the non-upsampled / split octave-0 base
-    if (lds > 64 * 1024) raise_lds_limit((const void*)k_blur_fused<RAD, MODE>);
-    VO_LAUNCH_NAMED(MODE == 0 ? "k_blur_fused" : "k_blur_base", (k_blur_fused<RAD, MODE>), grid, dim3(256), lds, s, src,
-                    plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols);
-    return false;
+    const size_t lds = sizeof(float) * ft_lds_floats(K.r);
+    if (lds > 64 * 1024) raise_lds_limit((const void*)k_blur_fused<RAD>);
+    VO_LAUNCH_NAMED("k_blur_fused", (k_blur_fused<RAD>), dim3((C + FT_W - 1) / FT_W, (R + FT_H - 1) / FT_H, n_img), dim3(256), lds, s,
+                    src, plane, dplane, pitch, R, C, g, K);
 }
 
-template <int MODE>
-static bool launch_blur(dim3 grid, hipStream_t s, const float* src, size_t plane, size_t dplane, int pitch, int R, int C, float* g,
-                        float* d, const Kern& K, const ImageSrc& isrc, int in_rows, int in_cols,
-                        const char* name = MODE == 0 ? "k_blur_fused" : "k_blur_base")
+static void launch_blur(const BlurPlan& pl, int n_img, hipStream_t s, const float* src, size_t plane, size_t dplane, int pitch,
+                        int R, int C, float* g, const Kern& K, const ImageSrc& isrc, int in_rows, int in_cols)
 {
     switch (K.r) {
-    case 5: return launch_blur_r<5, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
-    case 6: return launch_blur_r<6, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
-    case 8: return launch_blur_r<8, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
-    case 10: return launch_blur_r<10, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
-    case 13: return launch_blur_r<13, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
-    default: return launch_blur_r<0, MODE>(grid, s, src, plane, dplane, pitch, R, C, g, d, K, isrc, in_rows, in_cols, name);
+#define VO_BLUR_CASE(RR) \
+    case RR: return launch_blur_r<RR>(pl, n_img, s, src, plane, dplane, pitch, R, C, g, K, isrc, in_rows, in_cols);
+        VO_BLUR_RADII(VO_BLUR_CASE)
+#undef VO_BLUR_CASE
+    default: return launch_blur_r<0>(pl, n_img, s, src, plane, dplane, pitch, R, C, g, K, isrc, in_rows, in_cols);
     }
-}
-
-// launch_blur_r lowers the band height of a level blur below VO_BLUR_MAX_TH when the plane is too
-// small for VO_BLUR_WAVES waves at full bands: such an octave is latency-bound rather than HBM-bound
-static bool blur_latency_bound(int R, int C, int n_img)
-{
-    const int cpl = C <= VO_CPL2_MAXC ? 2 : 4;
-    const long n_strips = (C + 64 * cpl - 1) / (64 * cpl);
-    return (long)R * n_strips * n_img / VO_BLUR_WAVES < VO_BLUR_MAX_TH;
 }
 
 static float ext_threshold(const Pyramid& py, const vo_sift_params& p)
@@ -2506,53 +2443,52 @@ void sift_enqueue_pyramid(const Pyramid& py, SiftBuffers& b, const ImageSrc& src
     const int o_small = sp.o_small;
     const bool forked = ch.down != nullptr && ch.down != s;
     int o_fork = std::min(1, o_small - 1);
-    while (o_fork + 1 < o_small && !blur_latency_bound(py.oct[o_fork + 1].rows, py.oct[o_fork + 1].cols, n_img)) ++o_fork;
+    while (o_fork + 1 < o_small &&
+           blur_plan(BlurRole::Level, py.oct[o_fork + 1].rows, py.oct[o_fork + 1].cols, n_img, py.krad[1]).full_bands)
+        ++o_fork;
     bool base_done = false;                            // octave o's base already stored
     for (int o = 0; o < py.n_oct; ++o) {
         const OctGeom& g = py.oct[o];
         const int R = g.rows, C = g.cols;
         if (o == o_small) break;                       // octaves o_small.. : sift_enqueue_small
         if (forked && o == o_fork + 1) s = ch.down;    // (k_down, where level L was not streamed, included)
-        dim3 gf((C + FT_W - 1) / FT_W, (R + FT_H - 1) / FT_H, n_img);
         if (o == 0) {
-            Kern K0 = make_kern(py, 0);
+            const Kern K0 = make_kern(py, 0);
             const int rows = p.upsample ? R / 2 : R, cols = p.upsample ? C / 2 : C;
-            const int r0 = K0.r;
-            const bool stream_r = r0 == 5 || r0 == 6 || r0 == 8 || r0 == 10 || r0 == 13;
-            if (p.upsample && stream_r && R >= 64) {
-                // level-0 blur straight from the u8 image, x2 upsample formed while staging rows
-                launch_blur<0>(gf, s, nullptr, 0, py.istride, g.pitch, R, C, A + g.g_off[0], nullptr, K0, src, rows, cols,
-                               "k_blur_base");
-            } else {
-                // u8 (x2 upsampled) -> float source plane in the scratch buffer, then the level-0 blur
+            // level-0 blur straight from the u8 image, x2 upsample formed while staging rows ...
+            BlurPlan pl = blur_plan(p.upsample ? BlurRole::BaseU8 : BlurRole::BaseFloat, R, C, n_img, K0.r);
+            const bool from_u8 = pl.role == BlurRole::BaseU8 && pl.streamed;
+            if (!from_u8) {
+                // ... or u8 (x2 upsampled) -> float source plane in the scratch buffer, then the level-0 blur
                 const dim3 qg((g.pitch / 4 + 255) / 256, R, n_img);
                 if (p.upsample)
                     VO_LAUNCH(k_base_src<true>, qg, dim3(256), 0, s, src, rows, cols, b.tmp, g.plane, g.pitch, R, C, n_img);
                 else
                     VO_LAUNCH(k_base_src<false>, qg, dim3(256), 0, s, src, rows, cols, b.tmp, g.plane, g.pitch, R, C, n_img);
-                launch_blur<0>(gf, s, b.tmp, g.plane, py.istride, g.pitch, R, C, A + g.g_off[0], nullptr, K0, src, 0, 0,
-                               "k_blur_base");
+                pl = blur_plan(BlurRole::BaseFloat, R, C, n_img, K0.r);
             }
-        } else if (!base_done) {                       // (otherwise a streamed level-L blur wrote it)
+            launch_blur(pl, n_img, s, from_u8 ? nullptr : b.tmp, from_u8 ? 0 : g.plane, py.istride, g.pitch, R, C,
+                        A + g.g_off[0], K0, src, from_u8 ? rows : 0, from_u8 ? cols : 0);
+        } else if (!base_done) {                       // (otherwise the streamed level-L blur wrote it)
             const OctGeom& pg = py.oct[o - 1];
             VO_LAUNCH(k_down, dim3((C + 255) / 256, R, n_img), dim3(256), 0, s, A + pg.g_off[L], py.istride, pg.pitch,
                       A + g.g_off[0], py.istride, g.pitch, C);
         }
-        base_done = false;
         for (int i = 1; i < L + 3; ++i) {
             Kern K = make_kern(py, i);
-            // level L stores the next octave's base from its store path (no k_down pass: that
-            // re-read the even rows of G_L whole, 1.5x its algorithmic bytes); k_small_pyr
-            // decimates its own first base
-            const bool emit = i == L && o + 1 < o_small;
-            if (emit) {
-                const OctGeom& ng = py.oct[o + 1];
-                K.nb = A + ng.g_off[0];
-                K.nb_pitch = ng.pitch; K.nb_rows = ng.rows; K.nb_cols = ng.cols;
+            const BlurPlan pl = blur_plan(BlurRole::Level, R, C, n_img, K.r);
+            // a streamed level L stores the next octave's base from its store path (no k_down
+            // pass: that re-read the even rows of G_L whole, 1.5x its algorithmic bytes);
+            // k_small_pyr decimates its own first base
+            if (i == L) {
+                base_done = pl.streamed && o + 1 < o_small;
+                if (base_done) {
+                    const OctGeom& ng = py.oct[o + 1];
+                    K.nb = A + ng.g_off[0];
+                    K.nb_pitch = ng.pitch; K.nb_rows = ng.rows; K.nb_cols = ng.cols;
+                }
             }
-            const bool streamed = launch_blur<0>(gf, s, A + g.g_off[i - 1], py.istride, py.istride, g.pitch, R, C,
-                                                 A + g.g_off[i], nullptr, K, src, 0, 0);
-            if (emit) base_done = streamed;
+            launch_blur(pl, n_img, s, A + g.g_off[i - 1], py.istride, py.istride, g.pitch, R, C, A + g.g_off[i], K, src, 0, 0);
             if (forked && o == o_fork && i == L) {               // the down chain may start
                 hipEventRecord(ch.ev_fork, s);
                 hipStreamWaitEvent(ch.down, ch.ev_fork, 0);

@@ -84,8 +84,8 @@ template <int TAG>
 static float run(const uint8_t* u8, float* dst, size_t plane, int pitch, int R, int C, int n_img, int TH, const Kern& K,
                  hipStream_t st = 0)
 {
-    constexpr int SW = bs_sw(5, 4, TAG);                  // output columns per strip (halo-lane layout: 240)
-    const int n_strips = (C + SW - 1) / SW, n_bands = (R + TH - 1) / TH;
+    // strips of bs_sw(5, 4, TAG) output columns (halo-lane layout: 240)
+    const int n_strips = blur_grid_strips(C, 5, 4, TAG), n_bands = blur_bands(R, TH);
     const int blocks = n_strips * n_bands * n_img;
     const size_t fs = (size_t)(R / 2) * (C / 2);
     ImageSrc isrc{u8, u8 + fs * (n_img / 2), fs, C / 2, 0};
@@ -168,10 +168,10 @@ int main()
     }
     for (int TH : {32, 64, 96}) {                          // the staged base takes bands of <= kBaseMaxTH (96) rows
         const float ms = store_only(k_store_strip<0>, TH, 256) / 100.0f;
-        const float t0 = run<5>(u8, dst, plane, pitch, R, C, n, TH, K);
-        const float t8 = run<5 | 8>(u8, dst, plane, pitch, R, C, n, TH, K);
-        const float t24 = run<5 | 24>(u8, dst, plane, pitch, R, C, n, TH, K);
-        const float t56 = run<5 | 56>(u8, dst, plane, pitch, R, C, n, TH, K);
+        const float t0 = run<kTagBaseU8>(u8, dst, plane, pitch, R, C, n, TH, K);
+        const float t8 = run<kTagBaseU8 | kTagNoRowPass>(u8, dst, plane, pitch, R, C, n, TH, K);
+        const float t24 = run<kTagBaseU8 | kTagNoRowPass | kTagNoColPass>(u8, dst, plane, pitch, R, C, n, TH, K);
+        const float t56 = run<kTagBaseU8 | kTagNoRowPass | kTagNoColPass | kTagNoLds>(u8, dst, plane, pitch, R, C, n, TH, K);
         printf("TH %3d: store-only %6.1f us (%5.2f TB/s) | base %6.1f us (%5.2f TB/s) | no-row %6.1f | no row/col %6.1f | "
                "no row/col/LDS %6.1f\n", TH, 100.0f * ms, gb / (100.0f * ms) * 1e3, t0, gb / t0 * 1e3, t8, t24, t56);
     }
@@ -190,7 +190,7 @@ int main()
             if (e != hipSuccess) { printf("%s 1/%d: %s\n", contig ? "contiguous" : "interleaved", div, hipGetErrorString(e)); continue; }
             printf("%s CU mask 1/%d: VALU-bound %7.1f us | base %6.1f us (TH 96) | store-only %6.1f us\n",
                    contig ? "contiguous" : "interleaved", div, run_valu(reinterpret_cast<float*>(u8), st),
-                   div <= 8 ? run<5>(u8, dst, plane, pitch, R, C, n, 96, K, st) : 0.0f, div <= 8 ? store_only_s(st) : 0.0f);
+                   div <= 8 ? run<kTagBaseU8>(u8, dst, plane, pitch, R, C, n, 96, K, st) : 0.0f, div <= 8 ? store_only_s(st) : 0.0f);
         }
     return 0;
 }

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64) void k_copy_strip(const float* __restrict__ a, 
 template <int RAD, int TAG, int CPL = 4>
 static float run(const float* src, float* dst, size_t plane, int pitch, int R, int C, int n_img, int TH, const Kern& K)
 {
-    const int n_strips = (C + 64 * CPL - 1) / (64 * CPL), n_bands = (R + TH - 1) / TH;
+    const int n_strips = blur_grid_strips(C, RAD, CPL, TAG), n_bands = blur_bands(R, TH);   // as blur_plan.h launches it
     const int blocks = n_strips * n_bands * n_img;
     ImageSrc isrc{};
     hipEvent_t a, b;
@@ -77,16 +77,18 @@ static void probe(const float* src, float* dst, size_t plane, int pitch, int R, 
     for (int j = 0; j <= RAD; ++j) K.k[j] = 1.0f / (2 * RAD + 1);
     const double mb = 8.0 * (double)R * C * n / 1e6;     // algorithmic: 4 B in + 4 B out per px
     const int TH = getenv("TH") ? atoi(getenv("TH")) : 48;
-    float t0 = run<RAD, 0>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t8 = run<RAD, 8>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t16 = run<RAD, 16>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t24 = run<RAD, 24>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t2 = run<RAD, 2>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t56 = run<RAD, 56>(src, dst, plane, pitch, R, C, n, TH, K);
-    float t120 = run<RAD, 120>(src, dst, plane, pitch, R, C, n, TH, K);
-    float c0 = run<RAD, 0, 2>(src, dst, plane, pitch, R, C, n, TH, K);
-    float c24 = run<RAD, 24, 2>(src, dst, plane, pitch, R, C, n, TH, K);
-    float c56 = run<RAD, 56, 2>(src, dst, plane, pitch, R, C, n, TH, K);
+    constexpr int kNoCompute = kTagNoRowPass | kTagNoColPass;       // 24
+    constexpr int kNoComputeNoLds = kNoCompute | kTagNoLds;         // 56
+    float t0 = run<RAD, kTagLevel>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t8 = run<RAD, kTagNoRowPass>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t16 = run<RAD, kTagNoColPass>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t24 = run<RAD, kNoCompute>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t2 = run<RAD, kTagCachedStores>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t56 = run<RAD, kNoComputeNoLds>(src, dst, plane, pitch, R, C, n, TH, K);
+    float t120 = run<RAD, kNoComputeNoLds | kTagNoHalo>(src, dst, plane, pitch, R, C, n, TH, K);
+    float c0 = run<RAD, kTagLevel, 2>(src, dst, plane, pitch, R, C, n, TH, K);
+    float c24 = run<RAD, kNoCompute, 2>(src, dst, plane, pitch, R, C, n, TH, K);
+    float c56 = run<RAD, kNoComputeNoLds, 2>(src, dst, plane, pitch, R, C, n, TH, K);
     printf("r=%2d  full %6.1f us (%5.0f GB/s) | no-row %6.1f | no-col %6.1f | neither %6.1f | cached %6.1f | "
            "no compute+no LDS %6.1f | +no halo %6.1f\n", RAD, t0, mb / t0 * 1e3, t8, t16, t24, t2, t56, t120);
     printf("      CPL=2 full %6.1f us (%5.0f GB/s) | neither %6.1f | no compute+no LDS %6.1f\n", c0, mb / c0 * 1e3, c24, c56);
