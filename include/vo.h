@@ -27,6 +27,9 @@
  *                          gathers), fused on device
  *   vo_triangulate         triangulate(x1, x2, P1, P2)  VO.m:113-116,
  *                          CreateLandmarksFromFeatures.m:7
+ *   vo_triangulate_ex      [worldPoints, reprojectionErrors, validIndex] = triangulate(...):
+ *   vo_fetch_track_quality the toolbox call's other two outputs, and the same two for the
+ *                          loop's own triangulation of the tracked points (VO.m:113-116)
  *   vo_estworldpose        estworldpose(imagePts, worldPts, intrinsics)
  *                          VO.m:123-127 (P3P + MSAC)
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
@@ -358,7 +361,40 @@ int vo_track(vo_ctx* ctx,
 int vo_triangulate(vo_ctx* ctx, const float* x1, const float* x2, int n,
                    const double P1[12], const double P2[12], double* X);
 
-/* estworldpose: img [n][2] double (1-based pixels), world [n][3] double,
+/* ---- triangulate's reprojectionErrors and validIndex -------------------- */
+/* [worldPoints, reprojectionErrors, validIndex] = triangulate(x1, x2, P1, P2): what a caller filters
+ * triangulations with (VO.m's own crude form: CreateLandmarksFromFeatures.m:9-15 drops z < 0, z > 80).
+ *
+ * Spec (vo_spec.h vo_tri_quality, shared by the device and the CPU reference).  For point k with
+ * X = (X0, X1, X2) the doubles vo_triangulate returns -- the single-rounded values the caller
+ * sees, not the unrounded null vector, so both outputs can be reproduced from X, x1, x2, P1 and P2
+ * alone -- and for view i with P = Pi and (u, v) = xi[k] widened to double, in f64 basic operations
+ * in this order, no contraction:
+ *   h0 = ((P[0]*X0 + P[1]*X1) + P[2]*X2) + P[3]
+ *   h1 = ((P[4]*X0 + P[5]*X1) + P[6]*X2) + P[7]
+ *   w  = ((P[8]*X0 + P[9]*X1) + P[10]*X2) + P[11]
+ *   du = h0 / w - u;   dv = h1 / w - v;   e_i = sqrt(du*du + dv*dv)
+ *   reproj_err[k] = (float)((e_1 + e_2) * 0.5)   mean reprojection distance over the two views, in
+ *                                                pixels; single, as the toolbox returns for single points
+ *   valid[k]      = (w_1 > 0) && (w_2 > 0)       the sign of each view's third homogeneous coordinate:
+ *                                                for P = K [R t] the depth in that camera, the
+ *                                                toolbox's "in front of both cameras"
+ * Nothing is clamped.  A NaN w fails the comparison, so valid is 0; reproj_err is whatever IEEE
+ * arithmetic gives: NaN or +-inf where X is not finite (a non-finite pixel coordinate, a point that
+ * overflows single) or a w is 0.  A zero-disparity pair triangulates to a finite point beyond 1e17
+ * on the side its rounding falls, with a small error.  A point behind the cameras (negative
+ * disparity) reprojects perfectly -- only valid tells.
+ *
+ * reproj_err [n] and valid [n] may each be NULL; with both NULL this is vo_triangulate exactly.  X is
+ * bit-equal to vo_triangulate's in every case.  Same chunk loop over max_keypoints rows, same
+ * argument errors, refused (VO_ERR_STATE) while step batches are pending; n = 0 is legal and
+ * launches nothing.  The first call that asks for either output allocates the context's quality
+ * buffers (5 bytes per keypoint slot); a context that never asks allocates and launches nothing. */
+int vo_triangulate_ex(vo_ctx* ctx, const float* x1, const float* x2, int n,
+                      const double P1[12], const double P2[12],
+                      double* X, float* reproj_err, uint8_t* valid);
+
+/* estworldpose:img [n][2] double (1-based pixels), world [n][3] double,
  * K 3x3 -> T 4x4 camera pose in world (rigidtform3d.A), inliers[n] (0/1),
  * *n_inliers.  frame_key is mixed into the Philox key.  Returns
  * VO_ERR_TOO_FEW_POINTS (n < 4) or VO_ERR_NO_CONSENSUS like MATLAB throws. */
@@ -426,6 +462,18 @@ int vo_steps_pending(const vo_ctx* ctx);
  * (l_pos, VO.m:79).  Any output pointer may be NULL. */
 int vo_fetch_tracks(vo_ctx* ctx, int frame, float* old_l, float* cur_l, double* world, float* det, int capacity,
                     int* n_tracked, int* n_det);
+/* The quality of the same tracked points: row k belongs to row k of vo_fetch_tracks for the same
+ * frame.  old_r [capacity][2] is the right-image position of the old stereo pair (with old_l the
+ * pair VO.m:113-116 triangulates into world[k]); reproj_err [capacity] and valid [capacity] are
+ * vo_triangulate_ex's two outputs for world[k] from (old_l[k], old_r[k]) under the context's
+ * calibration P1, P2 -- a quality measure for what goes into estworldpose.  The loop itself does not
+ * use them: the kernel runs at this call, on the collected buffer set, and no step launches it.
+ * State rules as vo_fetch_tracks: VO_ERR_STATE for a frame outside the last collected batch and
+ * once that batch's buffer set is reused by a pending batch; any output pointer may be NULL;
+ * *n_tracked is clamped to max_keypoints.  A frame without tracked points (frame 1) launches
+ * nothing.  Synchronises like the other vo_fetch_* calls. */
+int vo_fetch_track_quality(vo_ctx* ctx, int frame, float* old_r, float* reproj_err, uint8_t* valid,
+                           int capacity, int* n_tracked);
 
 /* Landmarks accumulated so far ([rows][3] double, world frame). */
 int vo_get_landmarks(vo_ctx* ctx, double* out, int capacity, int* rows);

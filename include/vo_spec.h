@@ -459,4 +459,39 @@ VO_HD uint8_t vo_undistort_u8(double t00, double t01, double t10, double t11, do
     return (uint8_t)o;
 }
 
+/* ------------------------------------------------------------------------ */
+/* triangulate's second and third outputs (reprojectionErrors, validIndex)   */
+/* of one point.  X is the point as vo_triangulate returns it -- the doubles */
+/* already rounded through single, not the unrounded null vector -- so a     */
+/* caller reproduces both values from the outputs alone.  (u1, v1), (u2, v2) */
+/* are the single pixel positions, P1 / P2 3x4 row-major.  f64 basic ops in  */
+/* the order written, no contraction.  Per view:                             */
+/*   h0 = ((P[0] X0 + P[1] X1) + P[2] X2) + P[3],  h1 likewise on row 1,     */
+/*   w on row 2;  e = sqrt((h0 / w - u)^2 + (h1 / w - v)^2)                  */
+/* *err = (float)((e1 + e2) * 0.5), the mean reprojection distance; returns  */
+/* valid = w1 > 0 && w2 > 0 (for P = K [R t]: in front of both cameras).     */
+/* Nothing is clamped: a NaN w fails the comparison (valid 0), and err is    */
+/* what IEEE arithmetic gives (NaN or +-inf for a non-finite X or w = 0).    */
+/* ------------------------------------------------------------------------ */
+VO_HD double vo_tri_view_err(const double* X, double u, double v, const double* P, double* w_out)
+{
+    double h0 = ((P[0] * X[0] + P[1] * X[1]) + P[2] * X[2]) + P[3];
+    double h1 = ((P[4] * X[0] + P[5] * X[1]) + P[6] * X[2]) + P[7];
+    double w = ((P[8] * X[0] + P[9] * X[1]) + P[10] * X[2]) + P[11];
+    double du = h0 / w - u;
+    double dv = h1 / w - v;
+    *w_out = w;
+    return sqrt(du * du + dv * dv);
+}
+
+VO_HD int vo_tri_quality(const double* X, float u1, float v1, float u2, float v2, const double* P1, const double* P2,
+                         float* err)
+{
+    double w1, w2;
+    double e1 = vo_tri_view_err(X, (double)u1, (double)v1, P1, &w1);
+    double e2 = vo_tri_view_err(X, (double)u2, (double)v2, P2, &w2);
+    *err = (float)((e1 + e2) * 0.5);
+    return (w1 > 0.0) && (w2 > 0.0);
+}
+
 #endif /* VO_SPEC_H */

@@ -28,8 +28,10 @@
  *        matchFeatures(F1, F2)                                   VO.m:87,283,293,311,323
  *        and its options 'Unique', 'MatchThreshold', 'MaxRatio' (names case-insensitive; 'Method',
  *        'Metric', 'Prenormalized' only at their defaults; anything else: vo:matchFeatures:options)
- *   X = vo_mex('triangulate', x1, x2, P1, P2)
+ *   [X, reprojectionErrors, validIndex] = vo_mex('triangulate', x1, x2, P1, P2)
  *        triangulate                              VO.m:113-116, CreateLandmarksFromFeatures.m:7
+ *        one output: vo_triangulate; two or three: vo_triangulate_ex (N x 1 single mean reprojection
+ *        distance in pixels, N x 1 logical "in front of both cameras")
  *   [A, inliers, status] = vo_mex('estworldpose', imagePoints, worldPoints, K, opts)
  *        estworldpose (P3P + MSAC)                                       VO.m:123-127
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
@@ -510,10 +512,18 @@ static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]
     mxFree(mt);
 }
 
+/* vo_triangulate_ex through a weak reference: with a libvo that lacks it the one-output call runs
+ * as before and [worldPoints, reprojectionErrors, validIndex] raises vo:triangulate:unavailable */
+extern __typeof__(vo_triangulate_ex) vo_triangulate_ex __attribute__((weak));
+
+/* [worldPoints, reprojectionErrors, validIndex] = vo_mex('triangulate', x1, x2, P1, P2) */
 static void cmd_triangulate(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
 {
-    (void)nlhs;
     need_args(nrhs, 5, "triangulate");
+    if (nlhs > 3) mexErrMsgIdAndTxt("vo:badArgument", "triangulate returns at most [worldPoints, reprojectionErrors, validIndex]");
+    if (nlhs > 1 && !vo_triangulate_ex)
+        mexErrMsgIdAndTxt("vo:triangulate:unavailable", "this libvo has no vo_triangulate_ex: worldPoints = triangulate(...) only, "
+                          "or link a newer libvo");
     int n = 0, n2 = 0;
     float* x1 = points_f32(prhs[1], 2, &n, "matchedPoints1");
     float* x2 = points_f32(prhs[2], 2, &n2, "matchedPoints2");
@@ -523,7 +533,22 @@ static void cmd_triangulate(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     to_row_major(prhs[4], P2, 3, 4, "cameraMatrix2");
     need_ctx(0, 0);
     double* X = (double*)mxMalloc(sizeof(double) * 3 * ((size_t)n + 1));
-    check(vo_triangulate(g_ctx, x1, x2, n, P1, P2, X));
+    if (nlhs > 1) {
+        float* err = (float*)mxMalloc(sizeof(float) * ((size_t)n + 1));
+        uint8_t* ok = (uint8_t*)mxMalloc((size_t)n + 1);
+        check(vo_triangulate_ex(g_ctx, x1, x2, n, P1, P2, X, err, nlhs > 2 ? ok : NULL));
+        plhs[1] = mxCreateNumericMatrix(n, 1, mxSINGLE_CLASS, mxREAL);      /* reprojectionErrors */
+        memcpy(mxGetSingles(plhs[1]), err, sizeof(float) * (size_t)n);
+        if (nlhs > 2) {
+            plhs[2] = mxCreateLogicalMatrix(n, 1);                           /* validIndex */
+            mxLogical* L = mxGetLogicals(plhs[2]);
+            for (int i = 0; i < n; ++i) L[i] = ok[i] != 0;
+        }
+        mxFree(err);
+        mxFree(ok);
+    } else {
+        check(vo_triangulate(g_ctx, x1, x2, n, P1, P2, X));
+    }
     plhs[0] = mxCreateNumericMatrix(n, 3, mxSINGLE_CLASS, mxREAL);     /* single, as for single inputs */
     float* o = mxGetSingles(plhs[0]);
     for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) o[(size_t)a * n + i] = (float)X[3 * i + a];

@@ -202,6 +202,29 @@ __global__ void k_tri_list(const float* __restrict__ pos, int n, CalibDev cal, d
     }
 }
 
+// triangulate's reprojectionErrors / validIndex (vo_spec.h vo_tri_quality) of triangulated quads:
+// one lane per point, grid (blocks, frames).  Frame f: n[f * n_stride] points (clamped to cap),
+// quads pos + f * cap * 4, points X + f * cap * 3; err / valid are one frame's [cap] entries per
+// frame.  Launched only by vo_triangulate_ex and vo_fetch_track_quality, never by a step.
+__global__ void k_tri_quality(const float* __restrict__ pos, const double* __restrict__ X, const int* __restrict__ n,
+                              int n_stride, int n_val, int cap, CalibDev cal, float* __restrict__ err,
+                              uint8_t* __restrict__ valid)
+{
+    const int f = blockIdx.y;
+    int m = n ? n[(size_t)f * n_stride] : n_val;
+    m = m < 0 ? 0 : (m > cap ? cap : m);
+    const float4* q = reinterpret_cast<const float4*>(pos) + (size_t)f * cap;
+    const double* Xf = X + (size_t)f * cap * 3;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < m; k += gridDim.x * blockDim.x) {
+        const float4 p = q[k];
+        const double Y[3] = {Xf[3 * k], Xf[3 * k + 1], Xf[3 * k + 2]};
+        float e;
+        const int ok = vo_tri_quality(Y, p.x, p.y, p.z, p.w, cal.P1, cal.P2, &e);
+        err[(size_t)f * cap + k] = e;
+        valid[(size_t)f * cap + k] = (uint8_t)ok;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // P3P (oracle_p3p) — Grunert's quartic by polynomial algebra, deterministic
 // bracketing/bisection root finder (template recursion = the oracle's).
@@ -892,6 +915,15 @@ void triangulate_launch(const float* pos, int n, const vo_calib& c, double* X, h
     int blocks = (n + 63) / 64;
     if (blocks > 1024) blocks = 1024;
     VO_LAUNCH(k_tri_list, dim3(blocks), dim3(64), 0, s, pos, n, calib_dev(c), X);
+}
+
+void tri_quality_launch(const float* pos, const double* X, const int* n, int n_stride, int n_val, int frames, int cap,
+                        const vo_calib& c, float* err, uint8_t* valid, hipStream_t s)
+{
+    if (frames <= 0 || cap <= 0 || (!n && n_val <= 0)) return;
+    int blocks = ((n || n_val > cap ? cap : n_val) + 63) / 64;
+    if (blocks > 1024) blocks = 1024;
+    VO_LAUNCH(k_tri_quality, dim3(blocks, frames), dim3(64), 0, s, pos, X, n, n_stride, n_val, cap, calib_dev(c), err, valid);
 }
 
 void estworldpose_launch(GeomBuffers& g, const double* img, const double* world, const int* n, const double K[9],

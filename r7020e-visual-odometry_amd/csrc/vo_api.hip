@@ -112,6 +112,10 @@ struct vo_ctx {
     vo_bc_cam ud_cam[2] = {};
     uint8_t* d_rect = nullptr;
     int rect_B = 0;                  // frames of the last batched call that went through d_rect
+    // vo_triangulate_ex / vo_fetch_track_quality: one frame's reprojection errors and validity flags
+    // ([kp_cap] each), allocated by the first call that asks for either
+    float* d_tq_err = nullptr;
+    uint8_t* d_tq_valid = nullptr;
     // vo_set_strongest: SIFTPoints.selectStrongest(points, strongest) between detection and
     // description in every entry that detects (0 = off)
     int strongest = 0;
@@ -303,6 +307,8 @@ static void destroy_buffers(vo_ctx* c)
     hipFree(c->d_py); hipFree(c->d_job_single);
     hipFree(c->d_rect);
     c->d_rect = nullptr;
+    hipFree(c->d_tq_err); hipFree(c->d_tq_valid);
+    c->d_tq_err = nullptr; c->d_tq_valid = nullptr;
     hipFree(c->d_img); hipFree(c->d_cm); hipFree(c->d_fd[0]); hipFree(c->d_fd[1]); hipFree(c->d_fm[0]); hipFree(c->d_fm[1]);
     hipFree(c->d_ff[0]); hipFree(c->d_ff[1]); hipFree(c->d_bad);
     hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
@@ -1621,6 +1627,53 @@ int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* wo
     return VO_OK;
 }
 
+// the quality buffers of vo_triangulate_ex / vo_fetch_track_quality, at the first call that needs them
+static int tri_quality_buffers(vo_ctx* c)
+{
+    const int K = c->set[0].sb.kp_cap;
+    if (!c->d_tq_err) HIPC(c, hipMalloc((void**)&c->d_tq_err, sizeof(float) * K));
+    if (!c->d_tq_valid) HIPC(c, hipMalloc((void**)&c->d_tq_valid, (size_t)K));
+    return VO_OK;
+}
+
+int vo_fetch_track_quality(vo_ctx* c, int frame, float* old_r, float* reproj_err, uint8_t* valid, int capacity, int* n_tracked)
+{
+    if (!c || capacity < 0) return fail(c, VO_ERR_ARG, "vo_fetch_track_quality: bad arguments");
+    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
+        return fail(c, VO_ERR_STATE, "vo_fetch_track_quality: frame %d not in the last collected batch", frame);
+    for (const vo_ctx::Pending& q : c->pending)
+        if (q.set == c->last_step_set)
+            return fail(c, VO_ERR_STATE, "vo_fetch_track_quality: the collected batch's buffer set is reused by a pending batch");
+    hipSetDevice(c->device);
+    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    const int K = c->set[0].sb.kp_cap;
+    int n = 0;
+    HIPC(c, hipMemcpy(&n, S.gb.list_n + 4 * frame + 3, sizeof(int), hipMemcpyDeviceToHost));
+    n = std::min(std::max(n, 0), K);
+    if (n_tracked) *n_tracked = n;
+    const int m = std::min(n, capacity);
+    if (m <= 0) return VO_OK;
+    if (old_r) {
+        std::vector<float> op((size_t)m * 4);
+        HIPC(c, hipMemcpy(op.data(), S.gb.oldpos + (size_t)frame * K * 4, sizeof(float) * 4 * m, hipMemcpyDeviceToHost));
+        for (int k = 0; k < m; ++k) { old_r[2 * k] = op[4 * k + 2]; old_r[2 * k + 1] = op[4 * k + 3]; }
+    }
+    if (reproj_err || valid) {
+        // the collected batch's geometry is complete (vo_step_collect waited for it) and a pending
+        // batch works on the other set, so the kernel runs on the copy stream, which holds no work
+        // between calls, beside whatever `stream` still has queued
+        int rc = tri_quality_buffers(c);
+        if (rc) return rc;
+        tri_quality_launch(S.gb.oldpos + (size_t)frame * K * 4, S.gb.world + (size_t)frame * K * 3, S.gb.list_n + 4 * frame + 3, 4,
+                           0, 1, K, c->calib, c->d_tq_err, c->d_tq_valid, c->copy_stream);
+        if (reproj_err) HIPC(c, hipMemcpyAsync(reproj_err, c->d_tq_err, sizeof(float) * m, hipMemcpyDeviceToHost, c->copy_stream));
+        if (valid) HIPC(c, hipMemcpyAsync(valid, c->d_tq_valid, (size_t)m, hipMemcpyDeviceToHost, c->copy_stream));
+        HIPC(c, hipStreamSynchronize(c->copy_stream));
+        HIPC(c, hipGetLastError());
+    }
+    return VO_OK;
+}
+
 int vo_get_landmarks(vo_ctx* c, double* out, int capacity, int* rows)
 {
     if (!c) return VO_ERR_ARG;
@@ -1836,6 +1889,41 @@ int vo_triangulate(vo_ctx* c, const float* x1, const float* x2, int n, const dou
         HIPC(c, hipMemcpyAsync(c->set[0].gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
         triangulate_launch(c->set[0].gb.oldpos, m, cal, c->set[0].gb.world, c->stream);
         HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, c->set[0].gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+        int rc = finish(c);
+        if (rc) return rc;
+        g_prof = c->prof.on ? &c->prof : nullptr;
+    }
+    g_prof = nullptr;
+    return VO_OK;
+}
+
+int vo_triangulate_ex(vo_ctx* c, const float* x1, const float* x2, int n, const double P1[12], const double P2[12], double* X,
+                      float* reproj_err, uint8_t* valid)
+{
+    if (!reproj_err && !valid) return vo_triangulate(c, x1, x2, n, P1, P2, X);
+    if (!c || n < 0 || (n && (!x1 || !x2 || !X)) || !P1 || !P2) return fail(c, VO_ERR_ARG, "vo_triangulate_ex: bad arguments");
+    BEGIN_CALL(c);
+    if (n == 0) { g_prof = nullptr; return VO_OK; }
+    {
+        int rc = tri_quality_buffers(c);
+        if (rc) { g_prof = nullptr; return rc; }
+    }
+    const vo_calib cal = calib_of(P1, P2, nullptr);
+    const int K = c->set[0].sb.kp_cap;
+    const GeomBuffers& gb = c->set[0].gb;
+    std::vector<float> q((size_t)std::min(n, K) * 4 + 4);
+    for (int b = 0; b < n; b += K) {
+        const int m = std::min(K, n - b);
+        for (int k = 0; k < m; ++k) {
+            q[4 * k] = x1[2 * (b + k)]; q[4 * k + 1] = x1[2 * (b + k) + 1];
+            q[4 * k + 2] = x2[2 * (b + k)]; q[4 * k + 3] = x2[2 * (b + k) + 1];
+        }
+        HIPC(c, hipMemcpyAsync(gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
+        triangulate_launch(gb.oldpos, m, cal, gb.world, c->stream);
+        tri_quality_launch(gb.oldpos, gb.world, nullptr, 0, m, 1, K, cal, c->d_tq_err, c->d_tq_valid, c->stream);
+        HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+        if (reproj_err) HIPC(c, hipMemcpyAsync(reproj_err + b, c->d_tq_err, sizeof(float) * m, hipMemcpyDeviceToHost, c->stream));
+        if (valid) HIPC(c, hipMemcpyAsync(valid + b, c->d_tq_valid, (size_t)m, hipMemcpyDeviceToHost, c->stream));
         int rc = finish(c);
         if (rc) return rc;
         g_prof = c->prof.on ? &c->prof : nullptr;

@@ -96,6 +96,12 @@ void lm_world_launch(const double* poses, const long long* off, int n_frames, co
 // Standalone launchers used by the single-call ABI functions (frame slot 0).
 // pos: [n][4] (x1, y1, x2, y2) device floats.
 void triangulate_launch(const float* pos, int n, const vo_calib& c, double* X, hipStream_t s);
+// triangulate's reprojectionErrors / validIndex (vo_spec.h vo_tri_quality) for `frames` frames of
+// quads pos [frames][cap][4] and their triangulated points X [frames][cap][3]: frame f has
+// n[f * n_stride] points, or n_val when n is NULL (counts are clamped to cap).  err / valid
+// [frames][cap].  The layout of g.oldpos / g.world with g.list_n + 3, stride 4.
+void tri_quality_launch(const float* pos, const double* X, const int* n, int n_stride, int n_val, int frames, int cap,
+                        const vo_calib& c, float* err, uint8_t* valid, hipStream_t s);
 void estworldpose_launch(GeomBuffers& g, const double* img, const double* world, const int* n, const double K[9],
                          const vo_ransac_params& rp, uint32_t frame_key, hipStream_t s);
 // landmark filter + CreateLandmarksFromFeatures on g.spos/g.s_n (frame 0) vs

@@ -110,6 +110,7 @@ EXPORTS = [
     "vo_undistort", "vo_undistort_batch_dev", "vo_set_distortion", "vo_fetch_rectified",
     "vo_set_strongest", "vo_fetch_detected_count",
     "vo_check_points", "vo_describe", "vo_describe_batch",
+    "vo_triangulate_ex", "vo_fetch_track_quality",
 ]
 
 _libs: dict = {}
@@ -171,6 +172,9 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_track.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int,
                            P(C.c_uint32), C.c_int, P(C.c_int)]
     L.vo_triangulate.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double)]
+    L.vo_triangulate_ex.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_double), P(C.c_double), P(C.c_double),
+                                    P(C.c_float), P(C.c_uint8)]
+    L.vo_fetch_track_quality.argtypes = [vp, C.c_int, P(C.c_float), P(C.c_float), P(C.c_uint8), C.c_int, P(C.c_int)]
     L.vo_estworldpose.argtypes = [vp, P(C.c_double), P(C.c_double), C.c_int, P(C.c_double), P(RansacParams),
                                   C.c_uint32, P(C.c_double), P(C.c_uint8), P(C.c_int)]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
@@ -580,15 +584,30 @@ class Context:
         return idx[: n.value].copy()
 
     # ---- triangulate ----
-    def triangulate(self, x1, x2, P1, P2) -> np.ndarray:
+    def triangulate(self, x1, x2, P1, P2, quality=False):
+        """worldPoints [n, 3].  quality=True is [worldPoints, reprojectionErrors, validIndex] =
+        triangulate(...) (vo_triangulate_ex): -> (X, err float32 [n], valid bool [n]), err the mean
+        reprojection distance in pixels, valid the points in front of both cameras.  quality="err" /
+        "valid" asks the library for that output alone (the other is None)."""
         x1 = np.ascontiguousarray(x1, np.float32).reshape(-1, 2)
         x2 = np.ascontiguousarray(x2, np.float32).reshape(-1, 2)
         P1 = np.ascontiguousarray(P1, np.float64)
         P2 = np.ascontiguousarray(P2, np.float64)
-        X = np.zeros((x1.shape[0], 3))
-        self._check(self.lib.vo_triangulate(self.h, _p(x1, C.c_float), _p(x2, C.c_float), x1.shape[0],
-                                            _p(P1, C.c_double), _p(P2, C.c_double), _p(X, C.c_double)))
-        return X
+        n = x1.shape[0]
+        X = np.zeros((n, 3))
+        if not quality:
+            self._check(self.lib.vo_triangulate(self.h, _p(x1, C.c_float), _p(x2, C.c_float), n,
+                                                _p(P1, C.c_double), _p(P2, C.c_double), _p(X, C.c_double)))
+            return X
+        if quality not in (True, "err", "valid"):
+            raise VOError(VO_ERR_ARG, "triangulate: quality is False, True, 'err' or 'valid'")
+        err = np.zeros(n, np.float32) if quality in (True, "err") else None
+        valid = np.zeros(n, np.uint8) if quality in (True, "valid") else None
+        self._check(self.lib.vo_triangulate_ex(self.h, _p(x1, C.c_float), _p(x2, C.c_float), n, _p(P1, C.c_double),
+                                               _p(P2, C.c_double), _p(X, C.c_double),
+                                               _p(err, C.c_float) if err is not None else None,
+                                               _p(valid, C.c_uint8) if valid is not None else None))
+        return X, err, valid.astype(bool) if valid is not None else None
 
     # ---- estworldpose ----
     def estworldpose(self, imagePoints, worldPoints, K, params: RansacParams | None = None, frame_key: int = 0,
@@ -674,6 +693,21 @@ class Context:
                                              _p(det, C.c_float), cap, C.byref(nt), C.byref(nd)))
         k, n = nt.value, nd.value
         return {"old_l": old[:k].copy(), "cur_l": cur[:k].copy(), "world": world[:k].copy(), "det": det[:n].copy()}
+
+    def fetch_track_quality(self, frame: int):
+        """Quality of fetch_tracks(frame)'s rows, row for row (vo_fetch_track_quality): -> (old_r [K, 2]
+        the old stereo pair's right-image positions, err float32 [K] mean reprojection distance of
+        world[k] in pixels, valid bool [K] in front of both cameras), under the context's P1, P2."""
+        nt = C.c_int(0)
+        self._check(self.lib.vo_fetch_track_quality(self.h, frame, None, None, None, 0, C.byref(nt)))
+        cap = max(nt.value, 1)
+        old_r = np.zeros((cap, 2), np.float32)
+        err = np.zeros(cap, np.float32)
+        valid = np.zeros(cap, np.uint8)
+        self._check(self.lib.vo_fetch_track_quality(self.h, frame, _p(old_r, C.c_float), _p(err, C.c_float),
+                                                    _p(valid, C.c_uint8), cap, C.byref(nt)))
+        k = nt.value
+        return old_r[:k].copy(), err[:k].copy(), valid[:k].astype(bool)
 
     def step(self, left: np.ndarray, right: np.ndarray):
         return self.step_batch(left[None], right[None])[0]
