@@ -32,6 +32,9 @@
  *                          loop's own triangulation of the tracked points (VO.m:113-116)
  *   vo_estworldpose        estworldpose(imagePts, worldPts, intrinsics)
  *                          VO.m:123-127 (P3P + MSAC)
+ *   vo_refine_pose         bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose,
+ *   vo_set_pose_refinement intrinsics) on estworldpose's pose and inliers (VO.m:123-130): as a
+ *   vo_fetch_pose_refinement call, and as an optional stage of the loop body
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
  *                          CreateLandmarksFromFeatures.m:1-21
  *   vo_step / vo_step_batch the whole loop body VO.m:70-161 (features stay
@@ -402,6 +405,67 @@ int vo_estworldpose(vo_ctx* ctx, const double* img, const double* world, int n,
                     const double K[9], const vo_ransac_params* params, uint32_t frame_key,
                     double T[16], uint8_t* inliers, int* n_inliers);
 
+/* ---- bundleAdjustmentMotion: pose refinement after estworldpose --------- */
+/* refinedPose = bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose, intrinsics), the call
+ * the toolbox's stereo visual-odometry recipe makes right after estworldpose (VO.m:123-130 takes
+ * estworldpose's pose as it is: the pose of the best three-point sample).  Motion-only bundle
+ * adjustment: least squares on the squared pixel reprojection error over the used points, the
+ * points held fixed, by Levenberg-Marquardt.
+ *
+ * Spec (vo_spec.h vo_refine_*, shared by the device and the CPU reference; f64, + - * / and sqrt in
+ * the order written there, no contraction, so both give the same bytes):
+ *  - the state is the extrinsics R, t (Xc = R X + t); T (rigidtform3d.A, as vo_estworldpose returns
+ *    it) converts with R = T[0:3,0:3]', t = -R T[0:3,3] and back as vo_estworldpose builds its T;
+ *  - used set U = { k : use[k] != 0 and zc_k > 0 at T_in }, fixed for the call; n_used = |U|;
+ *  - a pass at a pose sums, over U, J'J (21 numbers), J'r (6) and r'r for the residual
+ *    r = projection - img[k] (K upper triangular: fx, skew, cx, fy, cy) and its Jacobian under the
+ *    left perturbation Xc' = Xc + w x Xc + v; a point of U with !(zc > 0) at that pose adds nothing
+ *    and marks the pass `behind`.  Sums run in 64 partials (partial l: points k = l mod 64,
+ *    ascending) joined by the tree p[i] += p[i + off], off = 32 .. 1;
+ *  - a step solves (H + lambda diag(H)) d = -g by a 6x6 Cholesky (a pivot not > 0: no step,
+ *    lambda *= 10) and retracts with the unit quaternion (1, w / 2) / sqrt(1 + |w|^2 / 4):
+ *    R' = dR R, t' = dR t + v;
+ *  - the loop makes one pass per trial while passes < max_iterations: the candidate is accepted iff
+ *    its pass is not `behind` and its cost c' < c (then lambda = max(lambda / 10, 1e-12), and the loop
+ *    ends CONVERGED when c - c' <= relative_tolerance * c or c' <= absolute_tolerance * n_used),
+ *    otherwise lambda *= 10; lambda > 1e12 ends it with DAMPING, the pass budget with MAX_ITER.
+ * cost_final <= cost_initial always, and the output is the last accepted pose; with no accepted step
+ * (accepted == 0) T_out is T_in bit for bit.  n_used < 3 (TOO_FEW) and a non-finite first pass
+ * (DEGENERATE) return the input pose; their one pass counts (passes = 1). */
+#define VO_REFINE_CONVERGED   0
+#define VO_REFINE_MAX_ITER    1
+#define VO_REFINE_DAMPING     2
+#define VO_REFINE_DEGENERATE -1
+#define VO_REFINE_TOO_FEW    -3
+
+typedef struct {
+    int32_t max_iterations;      /* passes over the points, 1 .. 100; default 20 (MaxIterations) */
+    double  relative_tolerance;  /* finite, >= 0; default 1e-9 (RelativeTolerance) */
+    double  absolute_tolerance;  /* px^2 per used point, finite, >= 0; default 0 (AbsoluteTolerance) */
+    double  lambda0;             /* first damping, 1e-12 .. 1e12; default 1e-3 */
+} vo_refine_params;
+
+typedef struct {
+    int32_t status;              /* VO_REFINE_* */
+    int32_t n_used, passes, accepted;
+    double  cost_initial, cost_final;   /* sum of squared pixel residuals over U */
+} vo_refine_stats;
+
+void vo_default_refine_params(vo_refine_params* p);
+
+/* img [n][2] double (1-based pixels), world [n][3] double, use [n] (NULL = all), K 3x3, T_in 4x4 the
+ * pose to start from (vo_estworldpose's T) -> T_out 4x4, *stats (may be NULL).  p NULL = defaults.
+ * Buffers and capacity as vo_estworldpose (frame slot 0 of buffer set 0; n > max_keypoints is
+ * VO_ERR_CAPACITY; like the other standalone calls it ends the loop state of vo_step).
+ * VO_ERR_ARG, checked on the host before anything is enqueued and naming the first offending
+ * index: a non-finite value in img, world, K or T_in; a last row of T_in other than 0 0 0 1;
+ * parameters outside the ranges above.  VO_ERR_STATE while step batches are pending.  n = 0 is
+ * legal and launches nothing: T_out = T_in, TOO_FEW with n_used 0, passes 1, costs 0.
+ * Returns VO_OK whenever it ran: the refinement's own outcome is stats->status. */
+int vo_refine_pose(vo_ctx* ctx, const double* img, const double* world, int n, const uint8_t* use,
+                   const double K[9], const double T_in[16], const vo_refine_params* p,
+                   double T_out[16], vo_refine_stats* stats);
+
 /* new-landmark filter (VO.m:145-158) + CreateLandmarksFromFeatures.
  * l_pos/r_pos [S][2] current stereo-matched locations; old_l/old_r [K][2]
  * remaining_old_features locations; pose 4x4 world pose.  Appends rows to
@@ -474,6 +538,24 @@ int vo_fetch_tracks(vo_ctx* ctx, int frame, float* old_l, float* cur_l, double* 
  * nothing.  Synchronises like the other vo_fetch_* calls. */
 int vo_fetch_track_quality(vo_ctx* ctx, int frame, float* old_r, float* reproj_err, uint8_t* valid,
                            int capacity, int* n_tracked);
+
+/* bundleAdjustmentMotion as a stage of the loop body (VO.m:123-130).  With p non-NULL every entry
+ * that runs the loop body (vo_step, vo_step_batch*, vo_step_submit_dev / vo_step_collect) launches
+ * the refinement kernel after the MSAC kernel, on the same stream, for the batch's frames whose MSAC
+ * status is VO_OK: vo_refine_pose on the frame's tracked points (vo_fetch_tracks' cur_l and world)
+ * with the MSAC inlier mask as `use`, starting from the MSAC pose and replacing it.
+ * vo_step_out.rel_pose and .pose are then the refined ones (the pose chain and the landmarks' world
+ * transform follow); status, n_inliers and the mask stay MSAC's.  p NULL turns it off.  Off (the
+ * default) launches and allocates nothing, and every result is that of a context that never set it.
+ * The first non-NULL call allocates the per-frame stats (max_batch x 32 bytes per buffer set).
+ * VO_ERR_ARG for parameters out of range, VO_ERR_STATE while step batches are pending; the setting
+ * survives vo_reset. */
+int vo_set_pose_refinement(vo_ctx* ctx, const vo_refine_params* p);
+/* The refinement's stats of frame `frame` of the last collected batch.  State rules of
+ * vo_fetch_tracks (VO_ERR_STATE for a frame outside that batch and once its buffer set is reused by
+ * a pending batch); VO_ERR_STATE when that batch ran with the refinement off.  A frame whose MSAC
+ * failed, or frame 1, was not refined: TOO_FEW with n_used 0, passes 0. */
+int vo_fetch_pose_refinement(vo_ctx* ctx, int frame, vo_refine_stats* out);
 
 /* Landmarks accumulated so far ([rows][3] double, world frame). */
 int vo_get_landmarks(vo_ctx* ctx, double* out, int capacity, int* rows);

@@ -494,4 +494,267 @@ VO_HD int vo_tri_quality(const double* X, float u1, float v1, float u2, float v2
     return (w1 > 0.0) && (w2 > 0.0);
 }
 
+/* ------------------------------------------------------------------------ */
+/* bundleAdjustmentMotion after estworldpose (VO.m:123-130): motion-only     */
+/* bundle adjustment, Levenberg-Marquardt on the squared pixel residuals of  */
+/* the used points with the points held fixed.  One definition for the       */
+/* kernel (k_refine_pose, geom.hip) and the CPU reference                    */
+/* (tests/pose_refine_ref), equal by bytes: f64 only, + - * / and sqrt in    */
+/* the order written, no contraction, no libm.  include/vo.h has the         */
+/* interface-level description.                                              */
+/*                                                                           */
+/* State: extrinsics R (3x3 row-major), t with Xc = R X + t -- MsacHyp's     */
+/* convention.  A pose given as rigidtform3d.A converts with                 */
+/* vo_refine_from_T and back with vo_refine_to_T (msac_final's expressions). */
+/* Used set U = { k : use[k] != 0 and zc_k > 0 at the initial pose }, fixed  */
+/* for the call: every pass re-evaluates zc_k at the initial pose from its   */
+/* third row (z0 = R0[6..8], t0[2]) instead of storing a mask.               */
+/* ------------------------------------------------------------------------ */
+#define VO_REFINE_CONVERGED   0
+#define VO_REFINE_MAX_ITER    1
+#define VO_REFINE_DAMPING     2
+#define VO_REFINE_DEGENERATE -1
+#define VO_REFINE_TOO_FEW    -3
+#define VO_REFINE_LAMBDA_MIN 1e-12
+#define VO_REFINE_LAMBDA_MAX 1e12
+#define VO_REFINE_NSUM 28           /* 21 of H's upper triangle row-major, 6 of g, the cost */
+#define VO_REFINE_LANES 64          /* partial sums: partial l adds the points k = l (mod 64), ascending */
+
+#if defined(__HIPCC__)
+#define VO_UNROLL _Pragma("unroll")
+#else
+#define VO_UNROLL
+#endif
+
+VO_HD void vo_refine_from_T(const double* T, double* R, double* t)
+{
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        R[3 * i] = T[i]; R[3 * i + 1] = T[4 + i]; R[3 * i + 2] = T[8 + i];
+    }
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) t[i] = -(R[3 * i] * T[3] + R[3 * i + 1] * T[7] + R[3 * i + 2] * T[11]);
+}
+
+VO_HD void vo_refine_to_T(const double* R, const double* t, double* T)
+{
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        T[4 * i] = R[i]; T[4 * i + 1] = R[3 + i]; T[4 * i + 2] = R[6 + i];
+        T[4 * i + 3] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
+    }
+    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+}
+
+/* One point of one pass at the pose (R, t).  Returns 1 when the point is in U (0: it adds nothing).
+ * A point of U with !(zc > 0) at this pose adds nothing and sets *behind.  Otherwise, with K read as
+ * reproj_err2_dev reads it (fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5]):
+ *   residual  ru = (fx xn + s yn + cx) - u,  rv = (fy yn + cy) - v,   xn = xc / zc, yn = yc / zc
+ *   rows of the Jacobian for the left perturbation Xc' = Xc + w x Xc + v:  (Xc x a, a), (Xc x b, b)
+ *   with a = (fx / zc, s / zc, -(fx xn + s yn) / zc),  b = (0, fy / zc, -(fy yn) / zc)
+ * and acc[0..20] += Ju_i Ju_j + Jv_i Jv_j (i <= j, row-major), acc[21..26] += Ju_i ru + Jv_i rv,
+ * acc[27] += ru ru + rv rv. */
+VO_HD int vo_refine_point(const double* R, const double* t, const double* z0, const double* K, const double* X,
+                          const double* uv, int use, double* acc, int* behind)
+{
+    double zi = z0[0] * X[0] + z0[1] * X[1] + z0[2] * X[2] + z0[3];
+    if (!use || !(zi > 0.0)) return 0;
+    double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    double yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    double zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    if (!(zc > 0.0)) { *behind = 1; return 1; }
+    double xn = xc / zc, yn = yc / zc;
+    double pu = K[0] * xn + K[1] * yn;
+    double pv = K[4] * yn;
+    double ru = (pu + K[2]) - uv[0];
+    double rv = (pv + K[5]) - uv[1];
+    double a0 = K[0] / zc, a1 = K[1] / zc, a2 = -(pu / zc);
+    double b1 = K[4] / zc, b2 = -(pv / zc);
+    double Ju[6], Jv[6];
+    Ju[0] = yc * a2 - zc * a1; Ju[1] = zc * a0 - xc * a2; Ju[2] = xc * a1 - yc * a0;
+    Ju[3] = a0; Ju[4] = a1; Ju[5] = a2;
+    Jv[0] = yc * b2 - zc * b1; Jv[1] = -(xc * b2); Jv[2] = xc * b1;
+    Jv[3] = 0.0; Jv[4] = b1; Jv[5] = b2;
+    int q = 0;
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) {
+        VO_UNROLL
+        for (int j = i; j < 6; ++j) {
+            acc[q] = acc[q] + (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+            ++q;
+        }
+    }
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + (Ju[i] * ru + Jv[i] * rv);
+    acc[27] = acc[27] + (ru * ru + rv * rv);
+    return 1;
+}
+
+/* (H + lambda diag(H)) d = -g by a 6x6 Cholesky in a fixed order; H is the row-major upper triangle.
+ * Returns 0 ("no step") at a pivot that is not > 0. */
+VO_HD int vo_refine_solve(const double* H, const double* g, double lambda, double* d)
+{
+    double A[6][6], L[6][6], y[6];
+    int q = 0;
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) {
+        VO_UNROLL
+        for (int j = i; j < 6; ++j) {
+            A[j][i] = H[q];                       /* the lower triangle is what the factor reads */
+            ++q;
+        }
+    }
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] + lambda * A[i][i];
+    int ok = 1;
+    VO_UNROLL
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j][j];
+        VO_UNROLL
+        for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+        if (!(s > 0.0)) ok = 0;
+        double dj = sqrt(s);
+        L[j][j] = dj;
+        VO_UNROLL
+        for (int i = j + 1; i < 6; ++i) {
+            double r = A[i][j];
+            VO_UNROLL
+            for (int k = 0; k < j; ++k) r = r - L[i][k] * L[j][k];
+            L[i][j] = r / dj;
+        }
+    }
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) {
+        double s = -g[i];
+        VO_UNROLL
+        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    VO_UNROLL
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+        VO_UNROLL
+        for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * d[k];
+        d[i] = s / L[i][i];
+    }
+    return ok;
+}
+
+/* Retraction of the step d = (w, v): q = (1, w / 2) / sqrt(1 + |w|^2 / 4), dR from the unit quaternion
+ * by the polynomial formula, R' = dR R, t' = dR t + v. */
+VO_HD void vo_refine_retract(const double* R, const double* t, const double* d, double* Rn, double* tn)
+{
+    double hx = 0.5 * d[0], hy = 0.5 * d[1], hz = 0.5 * d[2];
+    double n = sqrt(1.0 + (hx * hx + hy * hy + hz * hz));
+    double w = 1.0 / n, x = hx / n, y = hy / n, z = hz / n;
+    double D[9];
+    D[0] = 1.0 - 2.0 * (y * y + z * z); D[1] = 2.0 * (x * y - w * z); D[2] = 2.0 * (x * z + w * y);
+    D[3] = 2.0 * (x * y + w * z); D[4] = 1.0 - 2.0 * (x * x + z * z); D[5] = 2.0 * (y * z - w * x);
+    D[6] = 2.0 * (x * z - w * y); D[7] = 2.0 * (y * z + w * x); D[8] = 1.0 - 2.0 * (x * x + y * y);
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        VO_UNROLL
+        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = D[3 * i] * R[j] + D[3 * i + 1] * R[3 + j] + D[3 * i + 2] * R[6 + j];
+        tn[i] = (D[3 * i] * t[0] + D[3 * i + 1] * t[1] + D[3 * i + 2] * t[2]) + d[3 + i];
+    }
+}
+
+/* The Levenberg-Marquardt loop, one pass over the points per trial, as a state machine around the
+ * caller's pass (the kernel's wave-wide one, the reference's loop over 64 partials):
+ *
+ *     vo_refine_begin(&st, R, t, lambda0);
+ *     sums, n_used, behind <- pass at (st.R, st.t)
+ *     vo_refine_first(&st, sums, n_used);
+ *     while (vo_refine_propose(&st, max_iterations)) {
+ *         sums, behind <- pass at (st.Rc, st.tc)
+ *         vo_refine_update(&st, sums, behind, relative_tolerance, absolute_tolerance);
+ *     }
+ *
+ * A pass is the 28 sums of vo_refine_point over the points, summed in 64 partials (partial l: the
+ * points k = l mod 64 in ascending k, from +0) and then the tree p[i] = p[i] + p[i + off] for
+ * off = 32 .. 1, i < off; the result is p[0].
+ * first: n_used < 3 ends with TOO_FEW, a non-finite sum with DEGENERATE; both keep the input pose.
+ * propose: MAX_ITER once passes >= max_iterations; otherwise solve at lambda, lambda *= 10 on "no
+ * step", DAMPING once lambda > lambda_max; the candidate is (Rc, tc).
+ * update: accept iff !behind && c' < c (a NaN c' fails).  On accept take the candidate and its H, g,
+ * lambda = max(lambda / 10, lambda_min), CONVERGED when c - c' <= relative_tolerance * c or
+ * c' <= absolute_tolerance * n_used; otherwise lambda *= 10.
+ * (R, t) is always the last accepted pose, c its cost: cost_final <= cost_initial. */
+typedef struct {
+    double R[9], t[3];              /* the last accepted pose */
+    double Rc[9], tc[3];            /* the candidate */
+    double H[21], g[6], c;          /* sums at (R, t) */
+    double c0, lambda;
+    int status, n_used, passes, accepted, done;
+} vo_refine_state;
+
+VO_HD void vo_refine_begin(vo_refine_state* s, const double* R, const double* t, double lambda0)
+{
+    VO_UNROLL
+    for (int i = 0; i < 9; ++i) { s->R[i] = R[i]; s->Rc[i] = R[i]; }
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) { s->t[i] = t[i]; s->tc[i] = t[i]; }
+    s->lambda = lambda0;
+    s->status = VO_REFINE_MAX_ITER; s->n_used = 0; s->passes = 0; s->accepted = 0; s->done = 0;
+    s->c = 0.0; s->c0 = 0.0;
+}
+
+VO_HD void vo_refine_first(vo_refine_state* s, const double* sums, int n_used)
+{
+    s->n_used = n_used;
+    s->passes = 1;
+    s->c = sums[27];
+    s->c0 = sums[27];
+    int finite = 1;
+    VO_UNROLL
+    for (int i = 0; i < VO_REFINE_NSUM; ++i) if (!(sums[i] - sums[i] == 0.0)) finite = 0;
+    if (n_used < 3) { s->status = VO_REFINE_TOO_FEW; s->done = 1; }
+    else if (!finite) { s->status = VO_REFINE_DEGENERATE; s->done = 1; }
+    VO_UNROLL
+    for (int i = 0; i < 21; ++i) s->H[i] = sums[i];
+    VO_UNROLL
+    for (int i = 0; i < 6; ++i) s->g[i] = sums[21 + i];
+}
+
+VO_HD int vo_refine_propose(vo_refine_state* s, int max_iterations)
+{
+    if (s->done) return 0;
+    if (s->passes >= max_iterations) { s->status = VO_REFINE_MAX_ITER; s->done = 1; return 0; }
+    for (;;) {
+        if (s->lambda > VO_REFINE_LAMBDA_MAX) { s->status = VO_REFINE_DAMPING; s->done = 1; return 0; }
+        double d[6];
+        if (vo_refine_solve(s->H, s->g, s->lambda, d)) {
+            vo_refine_retract(s->R, s->t, d, s->Rc, s->tc);
+            return 1;
+        }
+        s->lambda = s->lambda * 10.0;
+    }
+}
+
+VO_HD void vo_refine_update(vo_refine_state* s, const double* sums, int behind, double relative_tolerance,
+                            double absolute_tolerance)
+{
+    s->passes = s->passes + 1;
+    double cn = sums[27];
+    if (!behind && cn < s->c) {
+        double drop = s->c - cn;
+        int conv = (drop <= relative_tolerance * s->c) || (cn <= absolute_tolerance * (double)s->n_used);
+        VO_UNROLL
+        for (int i = 0; i < 9; ++i) s->R[i] = s->Rc[i];
+        VO_UNROLL
+        for (int i = 0; i < 3; ++i) s->t[i] = s->tc[i];
+        VO_UNROLL
+        for (int i = 0; i < 21; ++i) s->H[i] = sums[i];
+        VO_UNROLL
+        for (int i = 0; i < 6; ++i) s->g[i] = sums[21 + i];
+        s->c = cn;
+        s->accepted = s->accepted + 1;
+        double l = s->lambda / 10.0;
+        s->lambda = l > VO_REFINE_LAMBDA_MIN ? l : VO_REFINE_LAMBDA_MIN;
+        if (conv) { s->status = VO_REFINE_CONVERGED; s->done = 1; }
+    } else {
+        s->lambda = s->lambda * 10.0;
+    }
+}
+
 #endif /* VO_SPEC_H */

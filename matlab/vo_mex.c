@@ -3,7 +3,8 @@
  *
  * VO.m calls Computer Vision Toolbox functions; MATLAB resolves a name to the first match on
  * its path, so the `.m` files next to this gateway (undistortImage.m, detectSIFTFeatures.m,
- * extractFeatures.m, matchFeatures.m, triangulate.m, estworldpose.m, CreateLandmarksFromFeatures.m) shadow the
+ * extractFeatures.m, matchFeatures.m, triangulate.m, estworldpose.m, bundleAdjustmentMotion.m,
+ * CreateLandmarksFromFeatures.m) shadow the
  * toolbox and the reference's own CreateLandmarksFromFeatures.m without editing VO.m.  Each
  * calls this one gateway with a command string:
  *
@@ -34,6 +35,9 @@
  *        distance in pixels, N x 1 logical "in front of both cameras")
  *   [A, inliers, status] = vo_mex('estworldpose', imagePoints, worldPoints, K, opts)
  *        estworldpose (P3P + MSAC)                                       VO.m:123-127
+ *   [refinedA, reprojectionErrors] = vo_mex('refinepose', xyzPoints, imagePoints, A, K, opts)
+ *        bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose, intrinsics) right after
+ *        estworldpose (VO.m:123-130): vo_refine_pose; M x 1 double pixel distances at the refined pose
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
  *        CreateLandmarksFromFeatures.m:2-18 (the rows before the :20 append)
  *   [rel_A, A, status, nLandmarks] = vo_mex('step', Il, Ir, P1, P2)
@@ -601,6 +605,68 @@ static void cmd_estworldpose(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
     mxFree(inl);
 }
 
+/* vo_refine_pose through a weak reference: with a libvo that lacks it 'refinepose' raises
+ * vo:bundleAdjustmentMotion:unavailable and every other command runs as before */
+extern __typeof__(vo_refine_pose) vo_refine_pose __attribute__((weak));
+extern __typeof__(vo_default_refine_params) vo_default_refine_params __attribute__((weak));
+
+/* sqrt(du^2 + dv^2) as the hardware instruction (no errno path: the gateway links no libm of its own) */
+#if defined(__GNUC__) && !defined(__clang__)
+__attribute__((optimize("no-math-errno")))
+#endif
+static double pixel_norm(double du, double dv) { return __builtin_sqrt(du * du + dv * dv); }
+
+/* [refinedPose, reprojectionErrors] = vo_mex('refinepose', xyzPoints, imagePoints, A, K, opts)
+ * bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose, intrinsics) after estworldpose
+ * (VO.m:123-130): xyzPoints M x 3 and imagePoints M x 2 double, A the 4 x 4 absolutePose.A, K 3 x 3;
+ * opts (optional) = [MaxIterations AbsoluteTolerance RelativeTolerance] double.  reprojectionErrors:
+ * M x 1 double, each point's pixel distance at the refined pose, computed here from the outputs. */
+static void cmd_refinepose(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs != 5 && nrhs != 6) need_args(nrhs, 5, "refinepose");
+    if (nlhs > 2) mexErrMsgIdAndTxt("vo:badArgument", "bundleAdjustmentMotion returns at most [refinedPose, reprojectionErrors]");
+    if (!vo_refine_pose || !vo_default_refine_params)
+        mexErrMsgIdAndTxt("vo:bundleAdjustmentMotion:unavailable", "this libvo has no vo_refine_pose: keep estworldpose's pose, "
+                          "or link a newer libvo");
+    const int n = (int)mxGetM(prhs[1]);
+    double* wld = points_f64(prhs[1], 3, n, "xyzPoints");
+    double* img = points_f64(prhs[2], 2, n, "imagePoints");
+    double A[16], K[9], T[16];
+    to_row_major(prhs[3], A, 4, 4, "absolutePose.A");
+    to_row_major(prhs[4], K, 3, 3, "intrinsics.K");
+    vo_refine_params rp;
+    vo_default_refine_params(&rp);
+    if (nrhs == 6) {
+        need_real(prhs[5], mxDOUBLE_CLASS, 1, 3, "opts");
+        const double* o = mxGetDoubles(prhs[5]);
+        rp.max_iterations = (o[0] >= 1.0 && o[0] <= 100.0 && o[0] == (double)(int32_t)o[0]) ? (int32_t)o[0] : 0;   /* 0: refused by libvo */
+        rp.absolute_tolerance = o[1];
+        rp.relative_tolerance = o[2];
+    }
+    need_ctx(0, 0);
+    const int rc = vo_refine_pose(g_ctx, img, wld, n, NULL, K, A, &rp, T, NULL);
+    if (rc != VO_OK) { mxFree(wld); mxFree(img); check(rc); }
+    plhs[0] = mat4_to_mx(T);
+    if (nlhs > 1) {
+        plhs[1] = mxCreateDoubleMatrix(n, 1, mxREAL);
+        double* e = n ? mxGetDoubles(plhs[1]) : NULL;
+        double R[9], t[3];
+        for (int i = 0; i < 3; ++i) { R[3 * i] = T[i]; R[3 * i + 1] = T[4 + i]; R[3 * i + 2] = T[8 + i]; }
+        for (int i = 0; i < 3; ++i) t[i] = -(R[3 * i] * T[3] + R[3 * i + 1] * T[7] + R[3 * i + 2] * T[11]);
+        for (int k = 0; k < n; ++k) {
+            const double* X = wld + 3 * (size_t)k;
+            const double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+            const double yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+            const double zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+            const double du = (K[0] * (xc / zc) + K[1] * (yc / zc) + K[2]) - img[2 * (size_t)k];
+            const double dv = (K[4] * (yc / zc) + K[5]) - img[2 * (size_t)k + 1];
+            e[k] = pixel_norm(du, dv);
+        }
+    }
+    mxFree(wld);
+    mxFree(img);
+}
+
 /* CreateLandmarksFromFeatures(features_l, features_r, P1, P2, pose, ~) rows (:2-18): VO.m:145-158
  * has already filtered the points, so libvo's own filter runs against no old points (K = 0). */
 static void cmd_landmarks(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
@@ -674,6 +740,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "match")) cmd_match(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "triangulate")) cmd_triangulate(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "refinepose")) cmd_refinepose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks")) cmd_landmarks(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step")) cmd_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks_all")) cmd_landmarks_all(nlhs, plhs, nrhs, prhs);

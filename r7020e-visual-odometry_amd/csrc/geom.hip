@@ -12,7 +12,10 @@
 //       (lane-strided partial MSAC sums + fixed shuffle tree), then the
 //       sequential adaptive-termination replay of the chunk -- until the replay
 //       stops; msac_final: inlier mask + camera pose.
-//   landmarks (VO.m:145-160, CreateLandmarksFromFeatures.m)  k_stereo_pos,
+//   bundleAdjustmentMotion (after VO.m:123-127, optional)  k_refine_pose: one wave per frame runs
+//       the Levenberg-Marquardt loop of vo_spec.h's vo_refine_* over the MSAC inliers and replaces
+//       the frame's pose.
+//   landmarks(VO.m:145-160, CreateLandmarksFromFeatures.m)  k_stereo_pos,
 //       k_lm_filter (any-x-or-y equality test, quirk Q3) + block compaction,
 //       k_lm_tri (odd rows, z gates).  (One fused block per frame measured
 //       3.5x slower: 0.27 vs 0.075 ms per batch for positions + filter.)  The world transform needs the chained pose and runs
@@ -54,10 +57,16 @@ hipError_t geom_alloc(GeomBuffers& g, int max_frames, int kp_cap, int n_hyp)
     return hipMemset(g.list_n, 0, sizeof(int) * 4 * F);
 }
 
+hipError_t geom_alloc_refine(GeomBuffers& g)
+{
+    if (g.refine) return hipSuccess;
+    return hipMalloc((void**)&g.refine, sizeof(vo_refine_stats) * (size_t)g.max_frames);
+}
+
 void geom_free(GeomBuffers& g)
 {
     void* bufs[] = {g.lists, g.list_n, g.step_i, g.step_j, g.step_n, g.world, g.imgpt, g.oldpos, g.inliers, g.hyp,
-                    g.fg, g.spos, g.s_n, g.lm_new, g.lm_M, g.lm_X, g.lm_keep, g.lm_rows};
+                    g.fg, g.spos, g.s_n, g.lm_new, g.lm_M, g.lm_X, g.lm_keep, g.lm_rows, g.refine};
     for (void* p : bufs) (void)hipFree(p);   // teardown: nothing to report to
     g = GeomBuffers();
 }
@@ -655,6 +664,117 @@ __global__ __launch_bounds__(VO_MSAC_T) void k_msac(MsacArgs a)
 }
 
 // ---------------------------------------------------------------------------
+// bundleAdjustmentMotion after estworldpose (VO.m:123-130; vo_spec.h vo_refine_*)
+// ---------------------------------------------------------------------------
+struct RefineArgs {
+    const double* img; const double* world; const uint8_t* use; const int* n; int n_stride;   // n[f * n_stride]
+    FrameGeom* fg; vo_refine_stats* stats;
+    int kp_cap, need_ok;
+    vo_refine_params p;
+    double K[9];
+};
+
+// One pass of the wave over the frame's points: lane l sums the points k = l (mod 64) in ascending
+// k, then the xor butterfly -- the fixed tree of msac_score_slot; every level adds the same two
+// values in both partner lanes, so all 64 lanes end with the bits of the tree's p[0] and every
+// decision taken on the sums is wave-uniform.
+__device__ __forceinline__ void refine_pass(const double* K, const double* img, const double* world, const uint8_t* use, int n,
+                                            int lane, const double* R, const double* t, const double* z0, double* sums,
+                                            int& n_used, int& behind)
+{
+#pragma unroll
+    for (int q = 0; q < VO_REFINE_NSUM; ++q) sums[q] = 0.0;
+    int cnt = 0, bh = 0;
+    for (int k = lane; k < n; k += VO_REFINE_LANES)
+        cnt += vo_refine_point(R, t, z0, K, world + 3 * k, img + 2 * k, use[k], sums, &bh);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < VO_REFINE_NSUM; ++q) sums[q] = sums[q] + __shfl_xor(sums[q], off);
+        cnt += __shfl_xor(cnt, off);
+        bh |= __shfl_xor(bh, off);
+    }
+    n_used = cnt;
+    behind = bh;
+}
+
+// Wave-uniform doubles moved, not computed (the bits stay): into scalar registers, and parked
+// across a pass as lane q of one register pair.  The pass then holds its 28 accumulators and a
+// point's temporaries in vector registers; the pose it runs at lives in scalar registers and the
+// accepted pose with its H, g (39 doubles, dead weight during a pass) in two vector registers.
+__device__ __forceinline__ double uniform_f64(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+__device__ __forceinline__ double unpark_f64(double pk, int q)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(pk), q), __builtin_amdgcn_readlane(__double2loint(pk), q));
+}
+
+// One wave per frame runs the whole Levenberg-Marquardt loop: no LDS, no barrier, no atomics.  The
+// kernel is latency-bound like k_msac (a frame's points, 41 bytes each, stay in cache after the
+// first pass).  Starts from fg[f].T and overwrites it when a step was accepted.
+__global__ __launch_bounds__(64) void k_refine_pose(RefineArgs a)
+{
+    const int f = blockIdx.x, lane = threadIdx.x;
+    FrameGeom* g = a.fg + f;
+    vo_refine_stats* so = a.stats + f;
+    if (a.need_ok && g->status != VO_OK) {                  // MSAC failed, or frame 1: not refined
+        if (lane == 0) {
+            so->status = VO_REFINE_TOO_FEW; so->n_used = 0; so->passes = 0; so->accepted = 0;
+            so->cost_initial = 0.0; so->cost_final = 0.0;
+        }
+        return;
+    }
+    int n = a.n[(size_t)f * a.n_stride];
+    n = n < 0 ? 0 : (n > a.kp_cap ? a.kp_cap : n);
+    const double* img = a.img + (size_t)f * a.kp_cap * 2;
+    const double* world = a.world + (size_t)f * a.kp_cap * 3;
+    const uint8_t* use = a.use + (size_t)f * a.kp_cap;
+    double T[16], R[9], t[3], z0[4], sums[VO_REFINE_NSUM];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) T[q] = g->T[q];
+    vo_refine_from_T(T, R, t);
+    z0[0] = uniform_f64(R[6]); z0[1] = uniform_f64(R[7]); z0[2] = uniform_f64(R[8]); z0[3] = uniform_f64(t[2]);
+    vo_refine_state st;
+    vo_refine_begin(&st, R, t, a.p.lambda0);
+    int n_used, behind;
+    refine_pass(a.K, img, world, use, n, lane, st.R, st.t, z0, sums, n_used, behind);
+    vo_refine_first(&st, sums, n_used);
+    while (vo_refine_propose(&st, a.p.max_iterations)) {
+        double pk = 0.0, Rc[9], tc[3];
+#pragma unroll
+        for (int q = 0; q < 21; ++q) pk = lane == q ? st.H[q] : pk;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) pk = lane == 21 + q ? st.g[q] : pk;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) { pk = lane == 27 + q ? st.R[q] : pk; Rc[q] = uniform_f64(st.Rc[q]); }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { pk = lane == 36 + q ? st.t[q] : pk; tc[q] = uniform_f64(st.tc[q]); }
+        int m;
+        refine_pass(a.K, img, world, use, n, lane, Rc, tc, z0, sums, m, behind);
+#pragma unroll
+        for (int q = 0; q < 21; ++q) st.H[q] = unpark_f64(pk, q);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) st.g[q] = unpark_f64(pk, 21 + q);
+#pragma unroll
+        for (int q = 0; q < 9; ++q) { st.R[q] = unpark_f64(pk, 27 + q); st.Rc[q] = Rc[q]; }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { st.t[q] = unpark_f64(pk, 36 + q); st.tc[q] = tc[q]; }
+        vo_refine_update(&st, sums, behind, a.p.relative_tolerance, a.p.absolute_tolerance);
+    }
+    if (lane == 0) {
+        if (st.accepted > 0) {
+            vo_refine_to_T(st.R, st.t, T);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) g->T[q] = T[q];
+        }
+        so->status = st.status; so->n_used = st.n_used; so->passes = st.passes; so->accepted = st.accepted;
+        so->cost_initial = st.c0; so->cost_final = st.c;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // landmarks
 // ---------------------------------------------------------------------------
 // stereo subset positions of frame f (VO.m:141-142): spos[f][j] = (lx, ly, rx, ry)
@@ -846,6 +966,7 @@ void geom_enqueue(GeomBuffers& g, const MatchBuffers& mb, const MatchJob* d_trac
     VO_LAUNCH(k_gather_tri, dim3(16, B), dim3(64), 0, s, a.sb->kp, K, g.lists, g.list_n, g.oldpos, g.imgpt, g.world, M, cal);
     MsacArgs ma = msac_args(g, g.imgpt, g.world, g.list_n + 3, 4, a.calib.K, a.rp, (uint32_t)a.frame_index0);
     msac_enqueue(ma, B, s);
+    if (a.refine_on) refine_launch(g, g.imgpt, g.world, g.inliers, g.list_n + 3, 4, a.calib.K, a.refine, B, 1, s);
     VO_LAUNCH(k_stereo_pos, dim3(16, B), dim3(256), 0, s, a.sb->kp, K, a.pair_i, a.pair_j, a.pair_n, g.spos, g.s_n);
     VO_LAUNCH(k_lm_filter, dim3(B), dim3(1024), 0, s, g.spos, g.s_n, g.oldpos, g.list_n + 3, 4, K, g.lm_keep, g.lm_new,
               g.lm_M, g.lm_rows);
@@ -931,6 +1052,19 @@ void estworldpose_launch(GeomBuffers& g, const double* img, const double* world,
 {
     MsacArgs ma = msac_args(g, img, world, n, 0, K, rp, frame_key);
     msac_enqueue(ma, 1, s);
+}
+
+void refine_launch(GeomBuffers& g, const double* img, const double* world, const uint8_t* use, const int* n, int n_stride,
+                   const double K[9], const vo_refine_params& p, int frames, int need_ok, hipStream_t s)
+{
+    if (frames <= 0) return;
+    RefineArgs a;
+    a.img = img; a.world = world; a.use = use; a.n = n; a.n_stride = n_stride;
+    a.fg = g.fg; a.stats = g.refine;
+    a.kp_cap = g.kp_cap; a.need_ok = need_ok;
+    a.p = p;
+    memcpy(a.K, K, sizeof(a.K));
+    VO_LAUNCH(k_refine_pose, dim3(frames), dim3(64), 0, s, a);
 }
 
 void landmarks_launch(GeomBuffers& g, const int* kn, const vo_calib& c, hipStream_t s)

@@ -97,6 +97,8 @@ struct vo_ctx {
         // the set's last SIFT call ran with vo_set_strongest on, so its n_det holds the detected
         // counts (otherwise n_kp does)
         bool sel_used = false;
+        // the set's last step batch ran with vo_set_pose_refinement on, so gb.refine holds its stats
+        bool refine_used = false;
     } set[2];
     int next_set = 0, last_set = 0;
     Pyramid py;
@@ -119,6 +121,9 @@ struct vo_ctx {
     // vo_set_strongest: SIFTPoints.selectStrongest(points, strongest) between detection and
     // description in every entry that detects (0 = off)
     int strongest = 0;
+    // vo_set_pose_refinement: bundleAdjustmentMotion after MSAC in every entry that runs the loop body
+    bool refine_on = false;
+    vo_refine_params refine = {};
     // the last SIFT call was vo_describe / vo_describe_batch: set 0 holds a scale space and the
     // caller's points, no detections, so the fetches of a detecting call's results are refused
     bool described = false;
@@ -207,6 +212,10 @@ void vo_default_match_opts(vo_match_opts* o) { o->match_threshold = 1.0f; o->max
 void vo_default_ransac_params(vo_ransac_params* p)
 {
     p->max_num_trials = 1000; p->confidence = 99.0; p->max_reprojection_error = 1.0; p->seed = 0x5EED;
+}
+void vo_default_refine_params(vo_refine_params* p)
+{
+    p->max_iterations = 20; p->relative_tolerance = 1e-9; p->absolute_tolerance = 0.0; p->lambda0 = 1e-3;
 }
 
 const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -1324,6 +1333,8 @@ static StepArgs step_args(vo_ctx* c, int B, int set = 0)
     a.frame_index0 = c->frame_index;
     a.calib = c->calib;
     a.rp = c->rp;
+    a.refine_on = c->refine_on ? 1 : 0;
+    a.refine = c->refine;
     return a;
 }
 
@@ -1398,6 +1409,7 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     int rc = enqueue_sift_stereo(c, set, d_l, d_r, B, true, false, fork);   // `stream` waits for this set's SIFT
     if (rc) return rc;
     StepArgs a = step_args(c, B, set);
+    S.refine_used = c->refine_on;
     geom_enqueue(S.gb, S.mb, S.d_jobs + job_track(c, 0, 0), a, c->mp, c->stream);
     vo_ctx::StepHost& H = c->sh[slot];
     HIPC(c, hipMemcpyAsync(H.fg, S.gb.fg, sizeof(FrameGeom) * B, hipMemcpyDeviceToHost, c->stream));
@@ -1958,6 +1970,102 @@ int vo_estworldpose(vo_ctx* c, const double* img, const double* world, int n, co
     if (n_inliers) *n_inliers = g.n_inliers;
     if (g.status == VO_ERR_NO_CONSENSUS) return fail(c, g.status, "estworldpose: no consensus (MSAC found no model with >= 4 inliers)");
     if (g.status != VO_OK) return fail(c, g.status, "estworldpose failed (%d)", g.status);
+    return VO_OK;
+}
+
+// -> nullptr when the block is inside the ranges of include/vo.h, else the offending field
+static const char* refine_params_refusal(const vo_refine_params& p)
+{
+    if (p.max_iterations < 1 || p.max_iterations > 100) return "max_iterations";
+    if (!(p.relative_tolerance >= 0.0 && p.relative_tolerance - p.relative_tolerance == 0.0)) return "relative_tolerance";
+    if (!(p.absolute_tolerance >= 0.0 && p.absolute_tolerance - p.absolute_tolerance == 0.0)) return "absolute_tolerance";
+    if (!(p.lambda0 >= VO_REFINE_LAMBDA_MIN && p.lambda0 <= VO_REFINE_LAMBDA_MAX)) return "lambda0";
+    return nullptr;
+}
+
+// index of the first non-finite value, or -1
+static long first_non_finite(const double* v, long n)
+{
+    for (long i = 0; i < n; ++i)
+        if (!(v[i] - v[i] == 0.0)) return i;
+    return -1;
+}
+
+int vo_refine_pose(vo_ctx* c, const double* img, const double* world, int n, const uint8_t* use, const double K9[9],
+                   const double T_in[16], const vo_refine_params* params, double T_out[16], vo_refine_stats* stats)
+{
+    if (!c || n < 0 || (n && (!img || !world)) || !K9 || !T_in || !T_out) return fail(c, VO_ERR_ARG, "vo_refine_pose: bad arguments");
+    const int cap = c->set[0].sb.kp_cap;
+    if (n > cap) return fail(c, VO_ERR_CAPACITY, "vo_refine_pose: %d points exceed max_keypoints", n);
+    vo_refine_params p;
+    if (params) p = *params; else vo_default_refine_params(&p);
+    if (const char* field = refine_params_refusal(p)) return fail(c, VO_ERR_ARG, "vo_refine_pose: parameter out of range: %s", field);
+    long bad;
+    if ((bad = first_non_finite(img, 2L * n)) >= 0)
+        return fail(c, VO_ERR_ARG, "vo_refine_pose: imagePoints(%ld, %ld) is not finite (point index %ld)", bad / 2 + 1, bad % 2 + 1, bad / 2);
+    if ((bad = first_non_finite(world, 3L * n)) >= 0)
+        return fail(c, VO_ERR_ARG, "vo_refine_pose: worldPoints(%ld, %ld) is not finite (point index %ld)", bad / 3 + 1, bad % 3 + 1, bad / 3);
+    if ((bad = first_non_finite(K9, 9)) >= 0) return fail(c, VO_ERR_ARG, "vo_refine_pose: K[%ld] is not finite", bad);
+    if ((bad = first_non_finite(T_in, 16)) >= 0) return fail(c, VO_ERR_ARG, "vo_refine_pose: T_in[%ld] is not finite", bad);
+    if (T_in[12] != 0.0 || T_in[13] != 0.0 || T_in[14] != 0.0 || T_in[15] != 1.0)
+        return fail(c, VO_ERR_ARG, "vo_refine_pose: the last row of T_in is not 0 0 0 1");
+    BEGIN_CALL(c);
+    if (n == 0) {                                       // nothing to launch: the pass over no points
+        memcpy(T_out, T_in, sizeof(double) * 16);
+        if (stats) *stats = vo_refine_stats{VO_REFINE_TOO_FEW, 0, 1, 0, 0.0, 0.0};
+        g_prof = nullptr;
+        return VO_OK;
+    }
+    GeomBuffers& gb = c->set[0].gb;
+    HIPC(c, geom_alloc_refine(gb));
+    c->have_features = false;
+    c->set[0].refine_used = false;                      // slot 0 of the set's stats is overwritten
+    std::vector<uint8_t> ones;
+    if (!use) { ones.assign((size_t)n, 1); use = ones.data(); }
+    HIPC(c, hipMemcpyAsync(gb.imgpt, img, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(gb.world, world, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(gb.inliers, use, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->d_fn, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync((char*)gb.fg + offsetof(FrameGeom, T), T_in, sizeof(double) * 16, hipMemcpyHostToDevice, c->stream));
+    refine_launch(gb, gb.imgpt, gb.world, gb.inliers, c->d_fn, 0, K9, p, 1, 0, c->stream);
+    FrameGeom g;
+    vo_refine_stats st;
+    HIPC(c, hipMemcpyAsync(&g, gb.fg, sizeof(g), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&st, gb.refine, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    int rc = finish(c);
+    if (rc) return rc;
+    memcpy(T_out, g.T, sizeof(g.T));
+    if (stats) *stats = st;
+    return VO_OK;
+}
+
+int vo_set_pose_refinement(vo_ctx* c, const vo_refine_params* p)
+{
+    if (!c) return VO_ERR_ARG;
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_set_pose_refinement: step batches pending (vo_step_collect first)");
+    if (!p) { c->refine_on = false; return VO_OK; }
+    if (const char* field = refine_params_refusal(*p))
+        return fail(c, VO_ERR_ARG, "vo_set_pose_refinement: parameter out of range: %s", field);
+    hipSetDevice(c->device);
+    for (int k = 0; k < 2; ++k) HIPC(c, geom_alloc_refine(c->set[k].gb));
+    c->refine = *p;
+    c->refine_on = true;
+    return VO_OK;
+}
+
+int vo_fetch_pose_refinement(vo_ctx* c, int frame, vo_refine_stats* out)
+{
+    if (!c || !out) return fail(c, VO_ERR_ARG, "vo_fetch_pose_refinement: bad arguments");
+    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
+        return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: frame %d not in the last collected batch", frame);
+    for (const vo_ctx::Pending& q : c->pending)
+        if (q.set == c->last_step_set)
+            return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: the collected batch's buffer set is reused by a pending batch");
+    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    if (!S.refine_used || !S.gb.refine)
+        return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: the batch ran without pose refinement (vo_set_pose_refinement)");
+    hipSetDevice(c->device);
+    HIPC(c, hipMemcpy(out, S.gb.refine + frame, sizeof(*out), hipMemcpyDeviceToHost));
     return VO_OK;
 }
 

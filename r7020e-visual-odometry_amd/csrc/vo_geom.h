@@ -50,11 +50,15 @@ struct GeomBuffers {
     float* lm_X = nullptr;       // [max_frames][kp_cap][3] camera-frame points of odd rows
     uint8_t* lm_keep = nullptr;  // [max_frames][kp_cap]
     int* lm_rows = nullptr;      // [max_frames]
+    // pose refinement (vo_set_pose_refinement / vo_refine_pose): per-frame stats, allocated by
+    // geom_alloc_refine at the first call that needs them
+    vo_refine_stats* refine = nullptr;   // [max_frames]
     // the batch's landmark rows packed in frame order (one D2H copy per batch): row r of frame f
     // at sum_{g<f} min(lm_rows[g], kp_cap) + r
 };
 
 hipError_t geom_alloc(GeomBuffers& g, int max_frames, int kp_cap, int n_hyp);
+hipError_t geom_alloc_refine(GeomBuffers& g);     // g.refine, once
 void geom_free(GeomBuffers& g);
 
 // Fill the 4 x max_frames tracking match jobs starting at jobs[first].
@@ -72,10 +76,12 @@ struct StepArgs {
     long frame_index0;             // global index of frame 0 (Philox key)
     vo_calib calib;
     vo_ransac_params rp;
+    int refine_on;                 // bundleAdjustmentMotion after MSAC (vo_set_pose_refinement)
+    vo_refine_params refine;
 };
 
-// Enqueue tracking (4 matches + compositions), triangulation, MSAC and the
-// landmark kernels for frames [0, B).  match jobs at d_jobs + first.
+// Enqueue tracking (4 matches + compositions), triangulation, MSAC, the pose refinement
+// (a.refine_on) and the landmark kernels for frames [0, B).  match jobs at d_jobs + first.
 void geom_enqueue(GeomBuffers& g, const MatchBuffers& mb, const MatchJob* d_track_jobs, const StepArgs& a,
                   const vo_match_params& mp, hipStream_t s);
 // tracking only (4 matches + compositions); lists/list_n valid afterwards.
@@ -104,6 +110,13 @@ void tri_quality_launch(const float* pos, const double* X, const int* n, int n_s
                         const vo_calib& c, float* err, uint8_t* valid, hipStream_t s);
 void estworldpose_launch(GeomBuffers& g, const double* img, const double* world, const int* n, const double K[9],
                          const vo_ransac_params& rp, uint32_t frame_key, hipStream_t s);
+// bundleAdjustmentMotion (vo_spec.h vo_refine_*; k_refine_pose, one wave per frame) for `frames`
+// frames laid out as g.imgpt / g.world / g.inliers: frame f has n[f * n_stride] points (clamped to
+// kp_cap) at img + f * kp_cap * 2, world + f * kp_cap * 3 and use + f * kp_cap.  It starts from
+// g.fg[f].T and overwrites it when a step was accepted; g.refine[f] gets the stats.  need_ok: frames
+// whose g.fg[f].status is not VO_OK are left alone (stats: TOO_FEW, n_used 0, passes 0).
+void refine_launch(GeomBuffers& g, const double* img, const double* world, const uint8_t* use, const int* n, int n_stride,
+                   const double K[9], const vo_refine_params& p, int frames, int need_ok, hipStream_t s);
 // landmark filter + CreateLandmarksFromFeatures on g.spos/g.s_n (frame 0) vs
 // g.oldpos with *kn old rows.
 void landmarks_launch(GeomBuffers& g, const int* kn, const vo_calib& c, hipStream_t s);

@@ -280,6 +280,16 @@ def set_sequence_strongest(ctx, strongest) -> None:
         ctx.set_strongest(int(strongest))
 
 
+def set_sequence_refinement(ctx, refine) -> None:
+    """bundleAdjustmentMotion after estworldpose on the driver's context (vo_set_pose_refinement):
+    `refine` is a vo.RefineParams, True (the defaults) or None / False, which leave the context as
+    it is.  The refinement is per frame, so a sharded run keeps equal to a single-process one."""
+    from . import vo
+    if refine is None or refine is False:
+        return
+    ctx.set_pose_refinement(vo.default_refine_params() if refine is True else refine)
+
+
 def _pipelined(ctx, batches, dev, on_collect=None, depth: int | None = None) -> list:
     """Drive the loop body through vo_step_submit_dev / vo_step_collect: while batch n's
     kernels run, the host decodes and uploads batch n+1 (threaded PNG decode, pinned H2D),
@@ -322,11 +332,12 @@ def _pipelined(ctx, batches, dev, on_collect=None, depth: int | None = None) -> 
 
 
 def run(seq: KittiSequence, batch: int = 16, stop: int | None = None, device: int | None = None, ctx=None,
-        viz_dir: str | os.PathLike | None = None, viz_every: int = 100, strongest: int | None = None):
+        viz_dir: str | os.PathLike | None = None, viz_every: int = 100, strongest: int | None = None, refine=None):
     """The VO.m loop over a KITTI sequence through libvo: frames in batches of `batch`
     (pipelined vo_step_submit_dev / vo_step_collect, tracking carried across batches), H2D
     from pinned host buffers.  `strongest`=N keeps the N strongest keypoints of every image
-    (selectStrongest, the knob VO.m:140, 206 name; `set_sequence_strongest`).  With `viz_dir`, every `viz_every`-th frame writes the reference's
+    (selectStrongest, the knob VO.m:140, 206 name; `set_sequence_strongest`).  `refine` (True, or a
+    vo.RefineParams) refines every relative pose over its MSAC inliers (`set_sequence_refinement`).  With `viz_dir`, every `viz_every`-th frame writes the reference's
     figures (`viz.snapshot`: img/<i>/view.png, map.svg, error.svg, 3d_map.svg; the landmark map
     in them includes the whole batch of frame i).
     Returns (poses [n, 4, 4] with frame 0 = identity, per-frame vo_step_out records,
@@ -339,6 +350,7 @@ def run(seq: KittiSequence, batch: int = 16, stop: int | None = None, device: in
         ctx = vo.Context(seq.rows, seq.cols, batch, device=device, calib=vo.calib_from(seq.P1, seq.P2))
     set_sequence_distortion(ctx, seq)
     set_sequence_strongest(ctx, strongest)
+    set_sequence_refinement(ctx, refine)
     hook = None
     if viz_dir is not None:
         from . import viz
@@ -373,7 +385,7 @@ def _local_device() -> int:
 
 
 def run_shard(seq, rank: int, world: int, batch: int = 16, device: int | None = None,
-              stop: int | None = None, ctx=None, rows_to_host: bool = True, strongest: int | None = None):
+              stop: int | None = None, ctx=None, rows_to_host: bool = True, strongest: int | None = None, refine=None):
     """One rank's part of a frame-sharded run (`sharding.py`): the block
     [start, end) of frames plus a one-frame halo, MSAC keyed by the global frame index,
     landmark rows kept in the camera frame.  `seq` is a KittiSequence (PNG frames) or a
@@ -381,7 +393,7 @@ def run_shard(seq, rank: int, world: int, batch: int = 16, device: int | None = 
     frames [halo, end)).  Returns (outs: the block's STEP_DTYPE records [end - start],
     X [L, 3] float32, keep [L] bool: the block's camera-frame landmark rows).  With
     rows_to_host=False (and a caller-owned `ctx`) the rows stay in the context's device store
-    for `finish_shard` and X, keep are None.  `strongest`: as for `run`."""
+    for `finish_shard` and X, keep are None.  `strongest`, `refine`: as for `run`."""
     import torch
     from . import sharding, vo
     if not rows_to_host and ctx is None:        # checked before any context or frame work
@@ -399,6 +411,7 @@ def run_shard(seq, rank: int, world: int, batch: int = 16, device: int | None = 
     ctx.reset()
     set_sequence_distortion(ctx, seq)
     set_sequence_strongest(ctx, strongest)
+    set_sequence_refinement(ctx, refine)
     ctx.set_landmark_frame(True)
     ctx.set_frame_index(h)
     src = device_batches(seq[0], seq[1], batch, h, e) if on_device else seq.batches(batch, h, e)
@@ -487,14 +500,14 @@ def finish_shard(ctx, outs, n: int, rank: int, world: int, device: int, group=No
 
 
 def run_distributed(seq, batch: int = 16, device: int | None = None, stop: int | None = None,
-                    group=None, strongest: int | None = None):
+                    group=None, strongest: int | None = None, refine=None):
     """Frame-sharded run over a torch.distributed group (one process per GPU; RCCL over
     xGMI with the nccl backend): every rank runs its block (`run_shard`, landmark rows kept on
     the device), then `finish_shard`: one all-gather of the per-frame records, the world-pose
     chain on every rank (host product of `VO.m:130`), each rank's own rows moved to the world on
     its device (`CreateLandmarksFromFeatures.m:17`) and gathered to rank 0.  Returns (world
     poses [n, 4, 4], gathered per-frame records, landmarks float32 [L, 3] on rank 0 / None on the
-    other ranks), equal bit for bit to a single-process run.  `strongest`: as for `run`, set on
+    other ranks), equal bit for bit to a single-process run.  `strongest`, `refine`: as for `run`, set on
     every rank's context."""
     import torch
     import torch.distributed as dist
@@ -510,7 +523,7 @@ def run_distributed(seq, batch: int = 16, device: int | None = None, stop: int |
     P1, P2 = seq_calib(seq)
     ctx = vo.Context(rows, cols, batch, device=device, calib=vo.calib_from(P1, P2))
     try:
-        outs, _, _ = run_shard(seq, rank, world, batch, device, n, ctx=ctx, rows_to_host=False, strongest=strongest)
+        outs, _, _ = run_shard(seq, rank, world, batch, device, n, ctx=ctx, rows_to_host=False, strongest=strongest, refine=refine)
         dev = torch.device("cuda", device) if dist.get_backend(group) == "nccl" else None
         return finish_shard(ctx, outs, n, rank, world, device, group=group, collective_device=dev)
     finally:

@@ -11,7 +11,8 @@ running on the MI355X through libvo.so:
     find_remaining_points                  VO.m:280-334
     triangulate                            VO.m:113-116
     estworldpose                           VO.m:123-127
-    CreateLandmarksFromFeatures            CreateLandmarksFromFeatures.m:1-21
+    bundleAdjustmentMotion                 after VO.m:123-127 (refine_pose, set_pose_refinement)
+    CreateLandmarksFromFeatures           CreateLandmarksFromFeatures.m:1-21
     VisualOdometry.step                    the VO.m loop body (VO.m:70-161)
 
 Coordinates are MATLAB 1-based.  Index pairs are 1-based uint32 (P x 2).
@@ -64,6 +65,18 @@ class RansacParams(C.Structure):
                 ("max_reprojection_error", C.c_double), ("seed", C.c_uint32)]
 
 
+class RefineParams(C.Structure):
+    """vo_refine_params: bundleAdjustmentMotion's MaxIterations, RelativeTolerance, AbsoluteTolerance
+    (px^2 per used point) and the first Levenberg-Marquardt damping."""
+    _fields_ = [("max_iterations", C.c_int32), ("relative_tolerance", C.c_double),
+                ("absolute_tolerance", C.c_double), ("lambda0", C.c_double)]
+
+
+class RefineStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("passes", C.c_int32), ("accepted", C.c_int32),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double)]
+
+
 class Calib(C.Structure):
     _fields_ = [("P1", C.c_double * 12), ("P2", C.c_double * 12), ("K", C.c_double * 9)]
 
@@ -95,6 +108,10 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 STEP_DTYPE = np.dtype([("status", "<i4"), ("n_left", "<i4"), ("n_right", "<i4"), ("n_stereo", "<i4"),
                        ("n_tracked", "<i4"), ("n_inliers", "<i4"), ("n_landmarks", "<i4"), ("flags", "<i4"),
                        ("rel_pose", "<f8", (4, 4)), ("pose", "<f8", (4, 4))])
+REFINE_STATS_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("passes", "<i4"), ("accepted", "<i4"),
+                               ("cost_initial", "<f8"), ("cost_final", "<f8")])
+# vo_refine_stats.status
+VO_REFINE_CONVERGED, VO_REFINE_MAX_ITER, VO_REFINE_DAMPING, VO_REFINE_DEGENERATE, VO_REFINE_TOO_FEW = 0, 1, 2, -1, -3
 
 # exported symbols (tests check the library exports every one)
 EXPORTS = [
@@ -111,6 +128,7 @@ EXPORTS = [
     "vo_set_strongest", "vo_fetch_detected_count",
     "vo_check_points", "vo_describe", "vo_describe_batch",
     "vo_triangulate_ex", "vo_fetch_track_quality",
+    "vo_default_refine_params", "vo_refine_pose", "vo_set_pose_refinement", "vo_fetch_pose_refinement",
 ]
 
 _libs: dict = {}
@@ -177,6 +195,13 @@ def load_library(path: str | os.PathLike | None = None):
     L.vo_fetch_track_quality.argtypes = [vp, C.c_int, P(C.c_float), P(C.c_float), P(C.c_uint8), C.c_int, P(C.c_int)]
     L.vo_estworldpose.argtypes = [vp, P(C.c_double), P(C.c_double), C.c_int, P(C.c_double), P(RansacParams),
                                   C.c_uint32, P(C.c_double), P(C.c_uint8), P(C.c_int)]
+    if hasattr(L, "vo_refine_pose"):     # (absent from an older library timed beside this one: tools/refine_times.py)
+        L.vo_default_refine_params.argtypes = [P(RefineParams)]
+        L.vo_default_refine_params.restype = None
+        L.vo_refine_pose.argtypes = [vp, P(C.c_double), P(C.c_double), C.c_int, P(C.c_uint8), P(C.c_double), P(C.c_double),
+                                     P(RefineParams), P(C.c_double), P(RefineStats)]
+        L.vo_set_pose_refinement.argtypes = [vp, P(RefineParams)]
+        L.vo_fetch_pose_refinement.argtypes = [vp, C.c_int, P(RefineStats)]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
                                P(C.c_double), P(C.c_double), C.c_int, P(C.c_int)]
     L.vo_step.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(StepOut)]
@@ -232,6 +257,25 @@ def default_ransac_params() -> RansacParams:
     p = RansacParams()
     load_library().vo_default_ransac_params(C.byref(p))
     return p
+
+
+def default_refine_params(**overrides) -> RefineParams:
+    """vo_default_refine_params (20 passes, relative tolerance 1e-9, absolute 0, lambda0 1e-3), with
+    any field overridden by keyword."""
+    p = RefineParams()
+    load_library().vo_default_refine_params(C.byref(p))
+    for k, v in overrides.items():
+        if k not in dict(RefineParams._fields_):
+            raise VOError(VO_ERR_ARG, f"default_refine_params: no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _refine_stats(s: RefineStats) -> np.ndarray:
+    out = np.zeros((), REFINE_STATS_DTYPE)
+    for name, _ in RefineStats._fields_:
+        out[name] = getattr(s, name)
+    return out
 
 
 def calib_from(P1, P2, K=None) -> Calib:
@@ -628,6 +672,41 @@ class Context:
         else:
             self._check(rc, allow=(VO_ERR_TOO_FEW_POINTS, VO_ERR_NO_CONSENSUS))
         return rc, T.reshape(4, 4), inl[: img.shape[0]].astype(bool), nin.value
+
+    # ---- bundleAdjustmentMotion ----
+    def refine_pose(self, imagePoints, worldPoints, T, K, use=None, params: RefineParams | None = None):
+        """refinedPose = bundleAdjustmentMotion(worldPoints, imagePoints, T, intrinsics) on the points
+        with use != 0 (None: all), e.g. estworldpose's pose and inlier mask (vo_refine_pose).
+        -> (T 4x4, stats record of REFINE_STATS_DTYPE: status VO_REFINE_*, n_used, passes, accepted,
+        cost_initial, cost_final in px^2)."""
+        img = np.ascontiguousarray(imagePoints, np.float64).reshape(-1, 2)
+        world = np.ascontiguousarray(worldPoints, np.float64).reshape(-1, 3)
+        if img.shape[0] != world.shape[0]:
+            raise VOError(VO_ERR_ARG, "refine_pose: imagePoints and worldPoints differ in length")
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        u = None
+        if use is not None:
+            u = np.ascontiguousarray(np.asarray(use) != 0, np.uint8).reshape(-1)
+            if u.shape[0] != img.shape[0]:
+                raise VOError(VO_ERR_ARG, "refine_pose: use and imagePoints differ in length")
+        out = np.zeros(16)
+        st = RefineStats()
+        self._check(self.lib.vo_refine_pose(self.h, _p(img, C.c_double), _p(world, C.c_double), img.shape[0],
+                                            _p(u, C.c_uint8) if u is not None else None, _p(K, C.c_double), _p(T, C.c_double),
+                                            C.byref(params) if params is not None else None, _p(out, C.c_double), C.byref(st)))
+        return out.reshape(4, 4), _refine_stats(st)
+
+    def set_pose_refinement(self, params: RefineParams | None) -> None:
+        """bundleAdjustmentMotion after estworldpose in every entry that runs the loop body
+        (vo_set_pose_refinement): rel_pose / pose are then the refined ones.  None turns it off."""
+        self._check(self.lib.vo_set_pose_refinement(self.h, C.byref(params) if params is not None else None))
+
+    def fetch_pose_refinement(self, frame: int) -> np.ndarray:
+        """The refinement's stats record of `frame` of the last collected batch (vo_fetch_pose_refinement)."""
+        st = RefineStats()
+        self._check(self.lib.vo_fetch_pose_refinement(self.h, frame, C.byref(st)))
+        return _refine_stats(st)
 
     # ---- new-landmark filter + CreateLandmarksFromFeatures ----
     def landmarks(self, l_pos, r_pos, old_l, old_r, pose) -> np.ndarray:
