@@ -37,6 +37,25 @@ int oracle_sift_params_ok(const vo_sift_params* p);
 int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
                 vo_keypoint* kps, uint8_t* desc, int capacity);
 
+/* What became of each extremum candidate of oracle_sift, in its scan order (octave, layer, row,
+ * col).  A candidate is a DoG centre with |val| > the extremum threshold that is an extremum of its
+ * 3x3x3 block within the DoG levels 1..L -- what vo_fetch_candidate_counts counts (include/vo.h).
+ * trace[i][8] = (octave, layer, r, c, outcome, refined r, refined c, refined layer): octave is the
+ * pyramid's index (0 = the first, upsampled or not); the refined location is the integer sample the
+ * outcome was decided at (after a move that left the domain: where it moved to).  Writes at most
+ * `capacity` records; *n_cand is the uncapped count, *n_acc the accepted ones.  Returns *n_cand,
+ * -1 for a parameter block the oracle refuses. */
+#define ORACLE_SIFT_ACCEPTED       0
+#define ORACLE_SIFT_LEFT_DOMAIN    1   /* a Newton move left the border-5 box or the layers 1..L */
+#define ORACLE_SIFT_NO_CONVERGENCE 2   /* 5 steps without every |offset| < 0.5 */
+#define ORACLE_SIFT_CONTRAST       3
+#define ORACLE_SIFT_EDGE           4
+#define ORACLE_SIFT_OVERFLOW       5   /* an offset beyond INT_MAX / 3 (a singular Hessian steps by 0 instead) */
+#define ORACLE_SIFT_OUTER          6   /* not an extremum against DoG level 0 (layer 1) or L + 1 (layer L) */
+#define ORACLE_SIFT_TRACE_FIELDS   8
+int oracle_sift_trace(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
+                      int32_t* trace, int capacity, int* n_cand, int* n_acc);
+
 /* Intermediate access for KATs: Gaussian blur of a float image with the
  * spec kernel for sigma (reflect-101), and the spec kernel itself. */
 int oracle_gauss_kernel(double sigma, float* k, int cap);  /* returns radius; k[0..radius] */

@@ -96,6 +96,9 @@ def lib(cv: bool = False):
         P = C.POINTER
         L.oracle_sift.argtypes = [P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(SiftParams), P(Keypoint), P(C.c_uint8), C.c_int]
         L.oracle_sift.restype = C.c_int
+        L.oracle_sift_trace.argtypes = [P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(SiftParams), P(C.c_int32), C.c_int,
+                                        P(C.c_int), P(C.c_int)]
+        L.oracle_sift_trace.restype = C.c_int
         L.oracle_gauss_kernel.argtypes = [C.c_double, P(C.c_float), C.c_int]
         L.oracle_gauss_kernel.restype = C.c_int
         L.oracle_blur.argtypes = [P(C.c_float), P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int]
@@ -159,6 +162,26 @@ def sift(img: np.ndarray, params: SiftParams | None = None, cv: bool = False):
                           kps.ctypes.data_as(C.POINTER(Keypoint)), _p(desc, C.c_uint8), cap)
     n = min(_check_params(n, p, "sift"), cap)
     return kps[:n].copy(), desc[:n].copy()
+
+
+# oracle_sift_trace's outcome codes (oracle.h ORACLE_SIFT_*)
+SIFT_OUTCOMES = ("accepted", "left_domain", "no_convergence", "contrast", "edge", "overflow", "outer")
+TRACE_DTYPE = np.dtype([("octave", "<i4"), ("layer", "<i4"), ("r", "<i4"), ("c", "<i4"), ("outcome", "<i4"),
+                        ("rr", "<i4"), ("rc", "<i4"), ("rlayer", "<i4")])
+
+
+def sift_trace(img: np.ndarray, params: SiftParams | None = None):
+    """What became of every extremum candidate of oracle.sift, in scan order (oracle_sift_trace):
+    -> (records [n_cand] of TRACE_DTYPE, n_cand, n_acc).  octave is the pyramid's index; rr, rc,
+    rlayer the integer sample the outcome was decided at."""
+    img = np.ascontiguousarray(img, np.uint8)
+    p = params or sift_params()
+    nc, na = C.c_int(0), C.c_int(0)
+    args = (_p(img, C.c_uint8), img.shape[0], img.shape[1], img.shape[1], C.byref(p))
+    _check_params(lib().oracle_sift_trace(*args, None, 0, C.byref(nc), C.byref(na)), p, "sift_trace")
+    rec = np.zeros(max(nc.value, 1), TRACE_DTYPE)
+    lib().oracle_sift_trace(*args, rec.ctypes.data_as(C.POINTER(C.c_int32)), nc.value, C.byref(nc), C.byref(na))
+    return rec[: nc.value].copy(), nc.value, na.value
 
 
 def gauss_kernel(sigma: float) -> np.ndarray:

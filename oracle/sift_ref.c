@@ -228,8 +228,12 @@ static int solve3(const float H[9], const float b[3], float X[3])
     return 1;
 }
 
+/* Returns an ORACLE_SIFT_* outcome code (oracle.h).  out->r, c, layer are the integer location the
+ * decision was taken at (after a move that left the domain: the location it moved to); the other
+ * fields are written for ORACLE_SIFT_ACCEPTED only. */
 static int refine(const pyramid_t* py, int o, int layer, int r, int c, const vo_sift_params* p, refined_t* out)
 {
+#define REFINE_RETURN(code) do { out->r = r; out->c = c; out->layer = layer; return (code); } while (0)
     const float img_scale = 1.0f / 255.0f;
     const float ds = img_scale * 0.5f, ss = img_scale, cs = img_scale * 0.25f;
     const octave_t* oc = &py->oct[o];
@@ -256,12 +260,12 @@ static int refine(const pyramid_t* py, int o, int layer, int r, int c, const vo_
         xi = -X[2]; xr = -X[1]; xc = -X[0];
         if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) break;
         const float big = (float)(0x7fffffff / 3);
-        if (fabsf(xi) > big || fabsf(xr) > big || fabsf(xc) > big) return 0;
+        if (fabsf(xi) > big || fabsf(xr) > big || fabsf(xc) > big) REFINE_RETURN(ORACLE_SIFT_OVERFLOW);
         c += vo_round(xc); r += vo_round(xr); layer += vo_round(xi);
         if (layer < 1 || layer > L || c < VO_SIFT_BORDER || c >= cols - VO_SIFT_BORDER ||
-            r < VO_SIFT_BORDER || r >= rows - VO_SIFT_BORDER) return 0;
+            r < VO_SIFT_BORDER || r >= rows - VO_SIFT_BORDER) REFINE_RETURN(ORACLE_SIFT_LEFT_DOMAIN);
     }
-    if (it >= VO_SIFT_MAX_INTERP) return 0;
+    if (it >= VO_SIFT_MAX_INTERP) REFINE_RETURN(ORACLE_SIFT_NO_CONVERGENCE);
     {
         const float* im = oc->d[layer];
         const float* pv = oc->d[layer - 1];
@@ -271,14 +275,14 @@ static int refine(const pyramid_t* py, int o, int layer, int r, int c, const vo_
                        (AT(nx, cols, r, c) - AT(pv, cols, r, c)) * ds};
         float t = dD[0] * xc + dD[1] * xr + dD[2] * xi;
         float contr = AT(im, cols, r, c) * img_scale + t * 0.5f;
-        if (fabsf(contr) * (float)L < p->contrast_threshold) return 0;
+        if (fabsf(contr) * (float)L < p->contrast_threshold) REFINE_RETURN(ORACLE_SIFT_CONTRAST);
         float v2 = AT(im, cols, r, c) * 2.0f;
         float dxx = (AT(im, cols, r, c + 1) + AT(im, cols, r, c - 1) - v2) * ss;
         float dyy = (AT(im, cols, r + 1, c) + AT(im, cols, r - 1, c) - v2) * ss;
         float dxy = (AT(im, cols, r + 1, c + 1) - AT(im, cols, r + 1, c - 1) - AT(im, cols, r - 1, c + 1) + AT(im, cols, r - 1, c - 1)) * cs;
         float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
         float et = p->edge_threshold;
-        if (det <= 0 || tr * tr * et >= (et + 1) * (et + 1) * det) return 0;
+        if (det <= 0 || tr * tr * et >= (et + 1) * (et + 1) * det) REFINE_RETURN(ORACLE_SIFT_EDGE);
         out->xo = (float)c + xc;
         out->yo = (float)r + xr;
         out->xi = xi;
@@ -288,9 +292,9 @@ static int refine(const pyramid_t* py, int o, int layer, int r, int c, const vo_
         out->scl = p->sigma * vo_expf(((float)layer + xi) / (float)L * 0.693147181f);
 #endif
         out->response = fabsf(contr);
-        out->r = r; out->c = c; out->layer = layer;
     }
-    return 1;
+    REFINE_RETURN(ORACLE_SIFT_ACCEPTED);
+#undef REFINE_RETURN
 }
 
 /* ---------------- orientation histogram ---------------- */
@@ -520,16 +524,31 @@ static int cv_remove_duplicated_sorted(vo_keypoint* kps, uint8_t* desc, int n)
 #endif
 
 /* ---------------- detect + describe ---------------- */
-int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
-                vo_keypoint* kps, uint8_t* desc, int capacity)
+/* val against the 3x3 block of one DoG level around (r, c): >= all nine for val > 0, <= otherwise */
+static int ext_level(const float* lvl, int C, int r, int c, float val)
 {
-    if (!oracle_sift_params_ok(p)) return -1;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            float q = AT(lvl, C, r + dy, c + dx);
+            if (!(val > 0 ? val >= q : val <= q)) return 0;
+        }
+    return 1;
+}
+
+/* The candidate loop of oracle_sift and oracle_sift_trace.  A candidate is a centre with |val| > thr
+ * that is an extremum of its 3x3x3 block within the DoG levels 1..L -- the count
+ * vo_fetch_candidate_counts reports (include/vo.h); one that fails against level 0 or L + 1 is
+ * ORACLE_SIFT_OUTER, the others go to refine().  With a trace nothing past refine() runs. */
+static int sift_scan(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
+                     vo_keypoint* kps, uint8_t* desc, int capacity,
+                     int32_t* trace, int trace_capacity, int* n_cand_out, int* n_acc_out)
+{
     pyramid_t py;
     build_pyramid(img, rows, cols, ld, p, &py);
     const int L = py.L;
     const float thr = (float)floor(0.5 * p->contrast_threshold / L * 255.0);
     const float up_scale = p->upsample ? 0.5f : 1.0f;
-    int count = 0;
+    int count = 0, n_cand = 0, n_acc = 0;
     for (int o = 0; o < py.n_oct; ++o) {
         const octave_t* oc = &py.oct[o];
         int R = oc->rows, C = oc->cols;
@@ -541,23 +560,26 @@ int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_pa
                 for (int c = VO_SIFT_BORDER; c < C - VO_SIFT_BORDER; ++c) {
                     float val = AT(cur, C, r, c);
                     if (!(fabsf(val) > thr)) continue;
-                    int ext = 1;
-                    if (val > 0) {
-                        for (int dy = -1; dy <= 1 && ext; ++dy)
-                            for (int dx = -1; dx <= 1; ++dx) {
-                                if (!(val >= AT(prv, C, r + dy, c + dx) && val >= AT(nxt, C, r + dy, c + dx) &&
-                                      val >= AT(cur, C, r + dy, c + dx))) { ext = 0; break; }
-                            }
+                    if (!ext_level(cur, C, r, c, val)) continue;
+                    if (i > 1 && !ext_level(prv, C, r, c, val)) continue;
+                    if (i < L && !ext_level(nxt, C, r, c, val)) continue;
+                    refined_t kp = {0};
+                    int code;
+                    int outer_ok = (i > 1 || ext_level(prv, C, r, c, val)) && (i < L || ext_level(nxt, C, r, c, val));
+                    if (!outer_ok) {
+                        code = ORACLE_SIFT_OUTER;
+                        kp.r = r; kp.c = c; kp.layer = i;
                     } else {
-                        for (int dy = -1; dy <= 1 && ext; ++dy)
-                            for (int dx = -1; dx <= 1; ++dx) {
-                                if (!(val <= AT(prv, C, r + dy, c + dx) && val <= AT(nxt, C, r + dy, c + dx) &&
-                                      val <= AT(cur, C, r + dy, c + dx))) { ext = 0; break; }
-                            }
+                        code = refine(&py, o, i, r, c, p, &kp);
                     }
-                    if (!ext) continue;
-                    refined_t kp;
-                    if (!refine(&py, o, i, r, c, p, &kp)) continue;
+                    if (trace && n_cand < trace_capacity) {
+                        int32_t* t = trace + (size_t)n_cand * ORACLE_SIFT_TRACE_FIELDS;
+                        t[0] = o; t[1] = i; t[2] = r; t[3] = c; t[4] = code; t[5] = kp.r; t[6] = kp.c; t[7] = kp.layer;
+                    }
+                    n_cand++;
+                    if (code != ORACLE_SIFT_ACCEPTED) continue;
+                    n_acc++;
+                    if (trace) continue;
                     float angles[VO_SIFT_MAX_PEAKS + 2];
                     const float* gimg = oc->g[kp.layer];
                     int np = orientations(gimg, R, C, kp.r, kp.c, kp.scl, angles);
@@ -585,8 +607,29 @@ int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_pa
         }
     }
     free_pyramid(&py);
+    if (n_cand_out) *n_cand_out = n_cand;
+    if (n_acc_out) *n_acc_out = n_acc;
+    return count;
+}
+
+int oracle_sift(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
+                vo_keypoint* kps, uint8_t* desc, int capacity)
+{
+    if (!oracle_sift_params_ok(p)) return -1;
+    int count = sift_scan(img, rows, cols, ld, p, kps, desc, capacity, NULL, 0, NULL, NULL);
 #ifdef VO_CV_LITERAL
     if (count <= capacity) count = cv_remove_duplicated_sorted(kps, desc, count);
 #endif
     return count;
+}
+
+int oracle_sift_trace(const uint8_t* img, int rows, int cols, int ld, const vo_sift_params* p,
+                      int32_t* trace, int capacity, int* n_cand, int* n_acc)
+{
+    if (!oracle_sift_params_ok(p)) return -1;
+    int nc = 0;
+    int32_t none[ORACLE_SIFT_TRACE_FIELDS];          /* trace == NULL: count only */
+    sift_scan(img, rows, cols, ld, p, NULL, NULL, 0, trace ? trace : none, trace ? capacity : 0, &nc, n_acc);
+    if (n_cand) *n_cand = nc;
+    return nc;
 }
