@@ -27,48 +27,25 @@
 
 namespace vo {
 
-hipError_t geom_alloc(GeomBuffers& g, int max_frames, int kp_cap, int n_hyp)
+hipError_t geom_alloc(DevPool& pool, GeomBuffers& g, int max_frames, int kp_cap, int n_hyp)
 {
     g.max_frames = max_frames; g.kp_cap = kp_cap; g.n_hyp = n_hyp;
     const size_t F = max_frames, K = kp_cap;
-    hipError_t e;
-#define GA(ptr, bytes) do { e = hipMalloc((void**)&(ptr), (bytes)); if (e != hipSuccess) return e; } while (0)
-    GA(g.lists, sizeof(int) * F * TL_COUNT * K);
-    GA(g.list_n, sizeof(int) * F * 4);
-    GA(g.step_i, sizeof(int) * 4 * F * K);
-    GA(g.step_j, sizeof(int) * 4 * F * K);
-    GA(g.step_n, sizeof(int) * 4 * F);
-    GA(g.world, sizeof(double) * F * K * 3);
-    GA(g.imgpt, sizeof(double) * F * K * 2);
-    GA(g.oldpos, sizeof(float) * F * K * 4);
-    GA(g.inliers, F * K);
-    GA(g.hyp, sizeof(MsacHyp) * F * n_hyp);
-    GA(g.fg, sizeof(FrameGeom) * F);
-    GA(g.spos, sizeof(float) * F * K * 4);
-    GA(g.s_n, sizeof(int) * F);
-    GA(g.lm_new, sizeof(int) * F * K);
-    GA(g.lm_M, sizeof(int) * F);
-    GA(g.lm_X, sizeof(float) * F * K * 3);
-    GA(g.lm_keep, F * K);
-    GA(g.lm_rows, sizeof(int) * F);
-#undef GA
-    e = hipMemset(g.step_n, 0, sizeof(int) * 4 * F);
-    if (e != hipSuccess) return e;
-    return hipMemset(g.list_n, 0, sizeof(int) * 4 * F);
+    hipError_t e = (hipError_t)pool.group({
+        DevPool::req(g.lists, F * TL_COUNT * K), DevPool::req(g.list_n, F * 4), DevPool::req(g.step_i, 4 * F * K),
+        DevPool::req(g.step_j, 4 * F * K), DevPool::req(g.step_n, 4 * F), DevPool::req(g.world, F * K * 3),
+        DevPool::req(g.imgpt, F * K * 2), DevPool::req(g.oldpos, F * K * 4), DevPool::req(g.inliers, F * K),
+        DevPool::req(g.hyp, F * n_hyp), DevPool::req(g.fg, F), DevPool::req(g.spos, F * K * 4), DevPool::req(g.s_n, F),
+        DevPool::req(g.lm_new, F * K), DevPool::req(g.lm_M, F), DevPool::req(g.lm_X, F * K * 3),
+        DevPool::req(g.lm_keep, F * K), DevPool::req(g.lm_rows, F)});
+    if (e == hipSuccess) e = hipMemset(g.step_n, 0, sizeof(int) * 4 * F);
+    if (e == hipSuccess) e = hipMemset(g.list_n, 0, sizeof(int) * 4 * F);
+    return e;
 }
 
-hipError_t geom_alloc_refine(GeomBuffers& g)
+hipError_t geom_alloc_refine(DevPool& pool, GeomBuffers& g)
 {
-    if (g.refine) return hipSuccess;
-    return hipMalloc((void**)&g.refine, sizeof(vo_refine_stats) * (size_t)g.max_frames);
-}
-
-void geom_free(GeomBuffers& g)
-{
-    void* bufs[] = {g.lists, g.list_n, g.step_i, g.step_j, g.step_n, g.world, g.imgpt, g.oldpos, g.inliers, g.hyp,
-                    g.fg, g.spos, g.s_n, g.lm_new, g.lm_M, g.lm_X, g.lm_keep, g.lm_rows, g.refine};
-    for (void* p : bufs) (void)hipFree(p);   // teardown: nothing to report to
-    g = GeomBuffers();
+    return g.refine ? hipSuccess : (hipError_t)pool.alloc(g.refine, (size_t)g.max_frames);
 }
 
 static inline int* glist(const GeomBuffers& g, int f, int l) { return g.lists + ((size_t)f * TL_COUNT + l) * g.kp_cap; }

@@ -43,7 +43,7 @@ __device__ __forceinline__ void top2c_merge(float& b, int& i, float& s, float b2
 // Pointers read from the job table are generic to the compiler, so loads through them became
 // flat loads, which count in both vmcnt and lgkmcnt and can only be waited for with vmcnt(0) /
 // lgkmcnt(0): every LDS wait of the tile loop also waited for the next tile's prefetch.  Every
-// job pointer addresses global memory (hipMalloc), so its loads and stores go through the
+// job pointer addresses global memory (device allocations), so its loads and stores go through the
 // global address space.
 template <class T>
 __device__ __forceinline__ T gld(const T* p)
@@ -436,43 +436,23 @@ __global__ void k_desc_meta(const uint8_t* __restrict__ desc, DescMeta* __restri
     }
 }
 
-hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap)
+hipError_t match_alloc(DevPool& pool, MatchBuffers& b, int max_jobs, int row_cap)
 {
     b.max_jobs = max_jobs;
     b.row_cap = row_cap;
     b.n_chunks = (row_cap + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
-    return hipMalloc((void**)&b.partial, sizeof(MatchTop2) * (size_t)max_jobs * b.n_chunks * row_cap);
+    return (hipError_t)pool.alloc(b.partial, (size_t)max_jobs * b.n_chunks * row_cap);
 }
 
-void match_free(MatchBuffers& b)
+hipError_t match_ex_alloc(DevPool& pool, MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back)
 {
-    hipFree(b.partial);
-    b = MatchBuffers();
-}
-
-hipError_t match_ex_alloc(MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back)
-{
-    MatchExBuffers n;
-    hipError_t e;
-    if ((e = hipMalloc((void**)&n.job_back, sizeof(MatchJob))) == hipSuccess &&
-        (e = hipMalloc((void**)&n.partial_back, sizeof(MatchTop2) * (size_t)b.n_chunks * b.row_cap)) == hipSuccess &&
-        (e = hipMalloc((void**)&n.metric, sizeof(float) * b.row_cap)) == hipSuccess &&
-        (e = hipMalloc((void**)&n.back, sizeof(int) * b.row_cap)) == hipSuccess &&
-        (e = hipMemcpy(n.job_back, &job_back, sizeof(MatchJob), hipMemcpyHostToDevice)) == hipSuccess) {
-        x = n;
-        return hipSuccess;
-    }
-    match_ex_free(n);
+    const size_t R = b.row_cap;
+    hipError_t e = (hipError_t)pool.group({DevPool::req(x.job_back, 1), DevPool::req(x.partial_back, b.n_chunks * R),
+                                           DevPool::req(x.metric, R), DevPool::req(x.back, R)});
+    if (e != hipSuccess) return e;
+    e = hipMemcpy(x.job_back, &job_back, sizeof(MatchJob), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { pool.release(x.job_back); pool.release(x.partial_back); pool.release(x.metric); pool.release(x.back); }
     return e;
-}
-
-void match_ex_free(MatchExBuffers& x)
-{
-    hipFree(x.job_back);
-    hipFree(x.partial_back);
-    hipFree(x.metric);
-    hipFree(x.back);
-    x = MatchExBuffers();
 }
 
 MatchBuffers match_view(const MatchBuffers& b, int k0)

@@ -119,52 +119,25 @@ SiftBuffers sift_view(const SiftBuffers& b, const Pyramid& py, int img0, int n)
     return v;
 }
 
-hipError_t sift_alloc(SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_cap)
+hipError_t sift_alloc(DevPool& pool, SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_cap)
 {
-    const int n = py.n_img;
-    b.n_img = n; b.kp_cap = kp_cap; b.cand_cap = cand_cap;
-    hipError_t e;
-#define VO_ALLOC(ptr, bytes) do { e = hipMalloc((void**)&(ptr), (bytes)); if (e != hipSuccess) return e; } while (0)
-    VO_ALLOC(b.arena, sizeof(float) * py.total);
-    VO_ALLOC(b.tmp, sizeof(float) * py.tmp_plane * n);
-    VO_ALLOC(b.mask, sizeof(unsigned long long) * (size_t)py.n_words * n + 8);
-    VO_ALLOC(b.woff, sizeof(uint32_t) * (size_t)py.n_seg * n + 8);
-    VO_ALLOC(b.cand, sizeof(uint32_t) * (size_t)cand_cap * n);
-    VO_ALLOC(b.n_cand, sizeof(int) * n);
-    VO_ALLOC(b.acc, sizeof(int) * (size_t)cand_cap * n);
-    VO_ALLOC(b.n_acc, sizeof(int) * n);
-    VO_ALLOC(b.cout, sizeof(CandOut) * (size_t)cand_cap * n);
-    VO_ALLOC(b.koff, sizeof(uint32_t) * (size_t)cand_cap * n);
-    VO_ALLOC(b.n_kp, sizeof(int) * n);
-    VO_ALLOC(b.n_det, sizeof(int) * n);
-    VO_ALLOC(b.kp, sizeof(vo_keypoint) * (size_t)kp_cap * n);
-    VO_ALLOC(b.kpi, sizeof(KpInt) * (size_t)kp_cap * n);
-    VO_ALLOC(b.desc, (size_t)VO_DESC_LEN * kp_cap * n);
-    VO_ALLOC(b.meta, sizeof(DescMeta) * (size_t)kp_cap * n);
-#undef VO_ALLOC
-    return hipSuccess;
+    const size_t n = py.n_img, C = (size_t)cand_cap * n, K = (size_t)kp_cap * n;
+    b.n_img = py.n_img; b.kp_cap = kp_cap; b.cand_cap = cand_cap;
+    return (hipError_t)pool.group({
+        DevPool::req(b.arena, py.total), DevPool::req(b.tmp, py.tmp_plane * n),
+        DevPool::req(b.mask, (size_t)py.n_words * n + 1), DevPool::req(b.woff, (size_t)py.n_seg * n + 2),
+        DevPool::req(b.cand, C), DevPool::req(b.n_cand, n), DevPool::req(b.acc, C), DevPool::req(b.n_acc, n),
+        DevPool::req(b.cout, C), DevPool::req(b.koff, C), DevPool::req(b.n_kp, n), DevPool::req(b.n_det, n),
+        DevPool::req(b.kp, K), DevPool::req(b.kpi, K), DevPool::req(b.desc, K * VO_DESC_LEN), DevPool::req(b.meta, K)});
 }
 
 // selectStrongest's comparison keys (k_sel_keys / k_sel_rank), allocated by the first
 // vo_set_strongest(n > 0): all or nothing
-hipError_t sift_alloc_select(SiftBuffers& b)
+hipError_t sift_alloc_select(DevPool& pool, SiftBuffers& b)
 {
-    if (b.skey && b.snpk) return hipSuccess;
-    unsigned long long* key = nullptr;
-    uint32_t* npk = nullptr;
-    hipError_t e = hipMalloc((void**)&key, sizeof(unsigned long long) * (size_t)b.cand_cap * b.n_img);
-    if (e == hipSuccess) e = hipMalloc((void**)&npk, sizeof(uint32_t) * (size_t)b.cand_cap * b.n_img);
-    if (e != hipSuccess) { hipFree(key); hipFree(npk); return e; }
-    b.skey = key; b.snpk = npk;
-    return hipSuccess;
-}
-
-void sift_free(SiftBuffers& b)
-{
-    hipFree(b.n_det); hipFree(b.skey); hipFree(b.snpk);
-    hipFree(b.arena); hipFree(b.tmp); hipFree(b.mask); hipFree(b.woff); hipFree(b.cand); hipFree(b.n_cand); hipFree(b.acc); hipFree(b.n_acc);
-    hipFree(b.cout); hipFree(b.koff); hipFree(b.n_kp); hipFree(b.kp); hipFree(b.kpi); hipFree(b.desc); hipFree(b.meta);
-    b = SiftBuffers();
+    if (b.skey) return hipSuccess;
+    const size_t C = (size_t)b.cand_cap * b.n_img;
+    return (hipError_t)pool.group({DevPool::req(b.skey, C), DevPool::req(b.snpk, C)});
 }
 
 // ---------------------------------------------------------------------------

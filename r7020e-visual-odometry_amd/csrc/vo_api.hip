@@ -14,7 +14,7 @@
 
 namespace vo {
 
-Profiler* g_prof = nullptr;
+thread_local Profiler* g_prof = nullptr;
 
 void Profiler::begin(const char* name, hipStream_t s)
 {
@@ -57,7 +57,29 @@ Profiler::~Profiler() { for (auto e : pool) hipEventDestroy(e); }
 
 using namespace vo;
 
+// the pool's way to the HIP runtime: every stream non-blocking, every event without timing
+static int hip_make(PoolKind kind, size_t bytes, void** out)
+{
+    switch (kind) {
+    case POOL_DEVICE: return hipMalloc(out, bytes);
+    case POOL_PINNED: return hipHostMalloc(out, bytes, 0);
+    case POOL_EVENT: return hipEventCreateWithFlags((hipEvent_t*)out, hipEventDisableTiming);
+    default: return hipStreamCreateWithFlags((hipStream_t*)out, hipStreamNonBlocking);
+    }
+}
+static void hip_drop(PoolKind kind, void* h)
+{
+    switch (kind) {
+    case POOL_DEVICE: (void)hipFree(h); break;
+    case POOL_PINNED: (void)hipHostFree(h); break;
+    case POOL_EVENT: (void)hipEventDestroy((hipEvent_t)h); break;
+    default: (void)hipStreamDestroy((hipStream_t)h);
+    }
+}
+
 struct vo_ctx {
+    // everything the context allocates, released when the context is deleted (the device selected)
+    DevPool pool{PoolBackend{hip_make, hip_drop}};
     int device = 0, rows = 0, cols = 0, max_batch = 0;
     vo_sift_params sp;
     vo_match_params mp;
@@ -227,51 +249,28 @@ static int job_stereo(const vo_ctx*, int f) { return f; }
 static int job_track(const vo_ctx* c, int step, int f) { return c->max_batch + step * c->max_batch + f; }
 static int job_count(const vo_ctx* c) { return 5 * c->max_batch; }
 
-static void destroy_streams(vo_ctx* c)
-{
-    for (int k = 0; k < vo_ctx::MAX_SUB; ++k) {
-        if (c->sub[k]) hipStreamDestroy(c->sub[k]);
-        if (c->ev_join[k]) hipEventDestroy(c->ev_join[k]);
-        if (c->ev_o0[k]) hipEventDestroy(c->ev_o0[k]);
-        if (c->ev_down[k]) hipEventDestroy(c->ev_down[k]);
-        if (c->ev_top[k]) hipEventDestroy(c->ev_top[k]);
-        c->sub[k] = nullptr; c->ev_join[k] = nullptr; c->ev_o0[k] = nullptr; c->ev_down[k] = nullptr; c->ev_top[k] = nullptr;
-    }
-    if (c->down) hipStreamDestroy(c->down);
-    c->down = nullptr;
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    c->ev_fork = nullptr;
-    for (int k = 0; k < VO_STEP_DEPTH; ++k) {
-        if (c->sh[k].ev) hipEventDestroy(c->sh[k].ev);
-        c->sh[k].ev = nullptr;
-    }
-    if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-    c->copy_stream = nullptr;
-}
-
-// Buffer set k: its buffers, its job table (job_stereo / job_track) and its two events.  On failure
-// *what names the step; set_free releases whatever was made.
-static hipError_t set_create(vo_ctx* c, int k, const char** what)
+// Buffer set k: its buffers, its job table (job_stereo / job_track) and its two events.  -> 0 or the
+// runtime's error code, *what naming the step (the pool keeps whatever was made).
+static int set_create(vo_ctx* c, int k, const char** what)
 {
     vo_ctx::BufferSet& S = c->set[k];
+    DevPool& pool = c->pool;
     const int M = c->max_batch, K = c->sp.max_keypoints, pair_slots = M + 1, n_jobs = job_count(c);
-    hipError_t e;
+    int e;
     *what = "event";
-    if ((e = hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming)) != hipSuccess) return e;
-    if ((e = hipEventCreateWithFlags(&S.ev_arena, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = pool.event(S.ev_done)) || (e = pool.event(S.ev_arena))) return e;
     *what = "sift buffers";
-    if ((e = sift_alloc(S.sb, c->py, K, 4 * K)) != hipSuccess) return e;
+    if ((e = sift_alloc(pool, S.sb, c->py, K, 4 * K))) return e;
     *what = "match buffers";
-    if ((e = match_alloc(S.mb, M, K)) != hipSuccess) return e;
+    if ((e = match_alloc(pool, S.mb, M, K))) return e;
     *what = "jobs";
-    if ((e = hipMalloc((void**)&S.d_jobs, sizeof(MatchJob) * n_jobs)) != hipSuccess) return e;
+    if ((e = pool.alloc(S.d_jobs, n_jobs))) return e;
     *what = "pairs";
-    if ((e = hipMalloc((void**)&S.pair_i, sizeof(int) * (size_t)pair_slots * K)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&S.pair_j, sizeof(int) * (size_t)pair_slots * K)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&S.pair_n, sizeof(int) * pair_slots)) != hipSuccess) return e;
-    if ((e = hipMemset(S.pair_n, 0, sizeof(int) * pair_slots)) != hipSuccess) return e;
+    if ((e = pool.group({DevPool::req(S.pair_i, (size_t)pair_slots * K), DevPool::req(S.pair_j, (size_t)pair_slots * K),
+                         DevPool::req(S.pair_n, pair_slots)}))) return e;
+    if ((e = hipMemset(S.pair_n, 0, sizeof(int) * pair_slots))) return e;
     *what = "geometry buffers";
-    if ((e = geom_alloc(S.gb, M, K, c->rp.max_num_trials)) != hipSuccess) return e;
+    if ((e = geom_alloc(pool, S.gb, M, K, c->rp.max_num_trials))) return e;
     std::vector<MatchJob> jobs(n_jobs);
     memset(jobs.data(), 0, sizeof(MatchJob) * n_jobs);
     const size_t dstride = (size_t)K * VO_DESC_LEN;
@@ -288,44 +287,72 @@ static hipError_t set_create(vo_ctx* c, int k, const char** what)
     return hipMemcpy(S.d_jobs, jobs.data(), sizeof(MatchJob) * n_jobs, hipMemcpyHostToDevice);
 }
 
-static void set_free(vo_ctx::BufferSet& S)
+// vo_create's streams, events and buffers.  -> 0 or the runtime's error code, `what` naming the step.
+static int create_resources(vo_ctx* c, std::string& what)
 {
-    sift_free(S.sb);
-    match_free(S.mb);
-    hipFree(S.d_jobs); hipFree(S.pair_i); hipFree(S.pair_j); hipFree(S.pair_n);
-    geom_free(S.gb);
-    if (S.ev_done) hipEventDestroy(S.ev_done);
-    if (S.ev_arena) hipEventDestroy(S.ev_arena);
-    S = vo_ctx::BufferSet();
-}
-
-static void destroy_buffers(vo_ctx* c)
-{
-    for (int k = 0; k < 2; ++k) set_free(c->set[k]);
-    for (int k = 0; k < VO_STEP_DEPTH; ++k) {
-        hipHostFree(c->sh[k].fg); hipHostFree(c->sh[k].nkp); hipHostFree(c->sh[k].ncand); hipHostFree(c->sh[k].np); hipHostFree(c->sh[k].rows);
-        hipHostFree(c->sh[k].ndet);
-        hipHostFree(c->sh[k].pX); hipHostFree(c->sh[k].pkeep);
-        hipFree(c->sh[k].d_pX); hipFree(c->sh[k].d_pkeep);
-        const hipEvent_t ev = c->sh[k].ev;               // owned by destroy_streams
-        c->sh[k] = vo_ctx::StepHost();
-        c->sh[k].ev = ev;
+    DevPool& pool = c->pool;
+    const int max_batch = c->max_batch, kp_cap = c->sp.max_keypoints;
+    int e;
+    what = "stream";
+    if ((e = pool.stream(c->stream))) return e;
+    for (int k = 0; k < vo_ctx::MAX_SUB; ++k) {
+        // every stream at the default priority: the forked SIFT streams must not rank below the
+        // geometry / copy streams of the pipelined loop body (at the lowest priority the full
+        // per-frame path dropped from 7.3 k to 5.4 k stereo frames/s), and the scale-space stream
+        // at the highest priority measured within noise.  No CU masks: with masks that bind
+        // (contiguous CU ranges), every split of the CUs between the two streams was 9-38 %
+        // slower -- both streams are bound per CU and need the whole chip (DESIGN.md 9b)
+        if ((e = pool.stream(c->sub[k]))) return e;
+        what = "event";
+        if ((e = pool.event(c->ev_join[k])) || (e = pool.event(c->ev_o0[k])) || (e = pool.event(c->ev_down[k])) ||
+            (e = pool.event(c->ev_top[k]))) return e;
+        what = "stream";
     }
-    for (void* p : c->lm_retired) hipFree(p);
-    c->lm_retired.clear();
-    hipFree(c->d_py); hipFree(c->d_job_single);
-    hipFree(c->d_rect);
-    c->d_rect = nullptr;
-    hipFree(c->d_tq_err); hipFree(c->d_tq_valid);
-    c->d_tq_err = nullptr; c->d_tq_valid = nullptr;
-    hipFree(c->d_img); hipFree(c->d_cm); hipFree(c->d_fd[0]); hipFree(c->d_fd[1]); hipFree(c->d_fm[0]); hipFree(c->d_fm[1]);
-    hipFree(c->d_ff[0]); hipFree(c->d_ff[1]); hipFree(c->d_bad);
-    hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
-    match_ex_free(c->mx);
-    hipFree(c->d_fn); hipFree(c->d_mi); hipFree(c->d_mj); hipFree(c->d_mn);
-    hipFree(c->d_lmX); hipFree(c->d_lmkeep); hipFree(c->d_lmw_pose); hipFree(c->d_lmw_off);
-    c->d_lmX = nullptr; c->d_lmkeep = nullptr; c->d_lmw_pose = nullptr; c->d_lmw_off = nullptr;
-    c->lm_cap = 0; c->lmw_cap = 0;
+    // (the down stream at the lowest / highest priority, forked after octave 0: 1-3 % slower than at
+    // the default, DESIGN.md §9j)
+    if ((e = pool.stream(c->down)) || (e = pool.stream(c->copy_stream))) return e;
+    what = "event";
+    if ((e = pool.event(c->ev_fork))) return e;
+    build_pyramid_geometry(c->py, c->rows, c->cols, 2 * max_batch + 2, c->sp);
+    what = "pyramid";
+    if ((e = pool.alloc(c->d_py, 1))) return e;
+    what = "pyramid copy";
+    if ((e = hipMemcpy(c->d_py, &c->py, sizeof(Pyramid), hipMemcpyHostToDevice))) return e;
+    for (int k = 0; k < 2; ++k) {
+        const char* step = "";
+        if ((e = set_create(c, k, &step))) { what = std::string(step) + (k ? " (set 1)" : ""); return e; }
+    }
+    what = "staging";
+    if ((e = pool.alloc(c->d_img, (size_t)2 * max_batch * c->rows * c->cols))) return e;
+    for (int k = 0; k < 2; ++k)
+        if ((e = pool.alloc(c->d_fd[k], (size_t)kp_cap * VO_DESC_LEN)) || (e = pool.alloc(c->d_fm[k], kp_cap)) ||
+            (e = pool.alloc(c->d_ff[k], (size_t)kp_cap * VO_DESC_LEN))) return e;
+    if ((e = pool.alloc(c->d_fn, 2)) || (e = pool.alloc(c->d_bad, 1)) || (e = pool.alloc(c->d_mi, kp_cap)) ||
+        (e = pool.alloc(c->d_mj, kp_cap)) || (e = pool.alloc(c->d_mn, 1))) return e;
+    {   // vo_match's job: the two staged descriptor sets (match_ex_buffers builds the exchanged one)
+        MatchJob J;
+        memset(&J, 0, sizeof(J));
+        J.d1 = c->d_fd[0]; J.m1 = c->d_fm[0]; J.idx1 = nullptr; J.n1 = c->d_fn;
+        J.d2 = c->d_fd[1]; J.m2 = c->d_fm[1]; J.idx2 = nullptr; J.n2 = c->d_fn + 1;
+        J.out_i = c->d_mi; J.out_j = c->d_mj; J.out_n = c->d_mn; J.cap = kp_cap;
+        what = "jobs";
+        if ((e = pool.alloc(c->d_job_single, 1))) return e;
+        what = "jobs copy";
+        if ((e = hipMemcpy(c->d_job_single, &J, sizeof(MatchJob), hipMemcpyHostToDevice))) return e;
+    }
+    const size_t F = max_batch, R = F * kp_cap;          // frames and landmark rows of a batch
+    for (int k = 0; k < VO_STEP_DEPTH; ++k) {
+        vo_ctx::StepHost& H = c->sh[k];
+        what = "event";
+        if ((e = pool.event(H.ev))) return e;
+        what = "packed rows";
+        if ((e = pool.alloc(H.d_pX, 3 * R)) || (e = pool.alloc(H.d_pkeep, R))) return e;
+        what = "pinned";
+        if ((e = pool.pinned(H.fg, F)) || (e = pool.pinned(H.nkp, 2 * F)) || (e = pool.pinned(H.ncand, 2 * F)) ||
+            (e = pool.pinned(H.ndet, 2 * F)) || (e = pool.pinned(H.np, F)) || (e = pool.pinned(H.rows, F)) ||
+            (e = pool.pinned(H.pX, 3 * R)) || (e = pool.pinned(H.pkeep, R))) return e;
+    }
+    return 0;
 }
 
 vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib* calib, const vo_sift_params* sift,
@@ -353,80 +380,13 @@ vo_ctx* vo_create(int device, int rows, int cols, int max_batch, const vo_calib*
     if (ransac) c->rp = *ransac; else vo_default_ransac_params(&c->rp);
     if (calib) { c->calib = *calib; c->has_calib = true; }
     memcpy(c->pose, I4, sizeof(I4));
-    auto bail = [&](const char* what, hipError_t e) -> vo_ctx* {
-        fail(nullptr, VO_ERR_HIP, "vo_create: %s: %s", what, hipGetErrorString(e));
-        destroy_buffers(c);
-        destroy_streams(c);
-        if (c->stream) hipStreamDestroy(c->stream);
+    std::string what;
+    const int e = create_resources(c, what);
+    if (e) {                                            // the context's pool frees what was made so far
+        fail(nullptr, VO_ERR_HIP, "vo_create: %s: %s", what.c_str(), hipGetErrorString((hipError_t)e));
         delete c;
         return nullptr;
-    };
-    // (every failure frees what was made so far)
-#define TRY(what, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return bail(what, e_); } while (0)
-    TRY("stream", hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int k = 0; k < vo_ctx::MAX_SUB; ++k) {
-        // every stream at the default priority: the forked SIFT streams must not rank below the
-        // geometry / copy streams of the pipelined loop body (at the lowest priority the full
-        // per-frame path dropped from 7.3 k to 5.4 k stereo frames/s), and the scale-space stream
-        // at the highest priority measured within noise.  No CU masks: with masks that bind
-        // (contiguous CU ranges), every split of the CUs between the two streams was 9-38 %
-        // slower -- both streams are bound per CU and need the whole chip (DESIGN.md 9b)
-        TRY("stream", hipStreamCreateWithFlags(&c->sub[k], hipStreamNonBlocking));
-        TRY("event", hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming));
-        TRY("event", hipEventCreateWithFlags(&c->ev_o0[k], hipEventDisableTiming));
-        TRY("event", hipEventCreateWithFlags(&c->ev_down[k], hipEventDisableTiming));
-        TRY("event", hipEventCreateWithFlags(&c->ev_top[k], hipEventDisableTiming));
     }
-    // (the down stream at the lowest / highest priority, forked after octave 0: 1-3 % slower than at
-    // the default, DESIGN.md §9j)
-    TRY("stream", hipStreamCreateWithFlags(&c->down, hipStreamNonBlocking));
-    TRY("event", hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    TRY("stream", hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    const int n_slots = 2 * max_batch + 2;
-    const int kp_cap = c->sp.max_keypoints;
-    build_pyramid_geometry(c->py, rows, cols, n_slots, c->sp);
-    TRY("pyramid", hipMalloc((void**)&c->d_py, sizeof(Pyramid)));
-    TRY("pyramid copy", hipMemcpy(c->d_py, &c->py, sizeof(Pyramid), hipMemcpyHostToDevice));
-    for (int k = 0; k < 2; ++k) {
-        const char* what = "";
-        const hipError_t e = set_create(c, k, &what);
-        if (e != hipSuccess) return bail((std::string(what) + (k ? " (set 1)" : "")).c_str(), e);
-    }
-    TRY("staging", hipMalloc((void**)&c->d_img, (size_t)2 * max_batch * rows * cols));
-    for (int k = 0; k < 2; ++k) {
-        TRY("staging", hipMalloc((void**)&c->d_fd[k], (size_t)kp_cap * VO_DESC_LEN));
-        TRY("staging", hipMalloc((void**)&c->d_fm[k], sizeof(DescMeta) * kp_cap));
-        TRY("staging", hipMalloc((void**)&c->d_ff[k], sizeof(float) * kp_cap * VO_DESC_LEN));
-    }
-    TRY("staging", hipMalloc((void**)&c->d_fn, sizeof(int) * 2));
-    TRY("staging", hipMalloc((void**)&c->d_bad, sizeof(int)));
-    TRY("staging", hipMalloc((void**)&c->d_mi, sizeof(int) * kp_cap));
-    TRY("staging", hipMalloc((void**)&c->d_mj, sizeof(int) * kp_cap));
-    TRY("staging", hipMalloc((void**)&c->d_mn, sizeof(int)));
-    {   // vo_match's job: the two staged descriptor sets (match_ex_buffers builds the exchanged one)
-        MatchJob J;
-        memset(&J, 0, sizeof(J));
-        J.d1 = c->d_fd[0]; J.m1 = c->d_fm[0]; J.idx1 = nullptr; J.n1 = c->d_fn;
-        J.d2 = c->d_fd[1]; J.m2 = c->d_fm[1]; J.idx2 = nullptr; J.n2 = c->d_fn + 1;
-        J.out_i = c->d_mi; J.out_j = c->d_mj; J.out_n = c->d_mn; J.cap = kp_cap;
-        TRY("jobs", hipMalloc((void**)&c->d_job_single, sizeof(MatchJob)));
-        TRY("jobs copy", hipMemcpy(c->d_job_single, &J, sizeof(MatchJob), hipMemcpyHostToDevice));
-    }
-    for (int k = 0; k < VO_STEP_DEPTH; ++k) {
-        vo_ctx::StepHost& H = c->sh[k];
-        TRY("event", hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
-        TRY("packed rows", hipMalloc((void**)&H.d_pX, sizeof(float) * 3 * max_batch * kp_cap));
-        TRY("packed rows", hipMalloc((void**)&H.d_pkeep, (size_t)max_batch * kp_cap));
-        TRY("pinned", hipHostMalloc((void**)&H.fg, sizeof(FrameGeom) * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.nkp, sizeof(int) * 2 * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.ncand, sizeof(int) * 2 * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.ndet, sizeof(int) * 2 * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.np, sizeof(int) * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.rows, sizeof(int) * max_batch, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.pX, sizeof(float) * 3 * max_batch * kp_cap, 0));
-        TRY("pinned", hipHostMalloc((void**)&H.pkeep, (size_t)max_batch * kp_cap, 0));
-    }
-#undef TRY
     return c;
 }
 
@@ -435,10 +395,8 @@ void vo_destroy(vo_ctx* c)
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    destroy_buffers(c);
-    destroy_streams(c);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    if (g_prof == &c->prof) g_prof = nullptr;
+    delete c;                                           // the pool: memory, then events, then streams
 }
 
 int vo_set_concurrency(vo_ctx* c, int n_streams)
@@ -464,13 +422,54 @@ int vo_set_profiling(vo_ctx* c, int enable)
     return VO_OK;
 }
 
-static int finish(vo_ctx* c);
+// the sticky error of the launches enqueued so far
+static int launch_status(vo_ctx* c)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? VO_OK : fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
+}
+
+// Synchronise the stream, collect profiling, translate errors.
+static int finish(vo_ctx* c)
+{
+    hipError_t e = hipStreamSynchronize(c->stream);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipStreamSynchronize(c->sub[k]);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->down);
+    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+    const int rc = launch_status(c);
+    if (rc) return rc;
+    if (c->prof.on) c->prof.collect();
+    return VO_OK;
+}
+
+// One entry's call on the context, constructed at its top: selects the device; refuses (status)
+// while step batches are pending unless the entry is the step pipeline's own (the others reuse
+// buffer set 0); points this thread's g_prof at the context's profiler while profiling is on, until
+// the entry returns by whatever path; and with quiesce, makes `stream` -- on which such calls run
+// over the context's own buffers -- wait for any batch still in flight on either buffer set (no
+// host synchronisation).
+struct CallScope {
+    int status = VO_OK;
+    explicit CallScope(vo_ctx* c, bool quiesce = true, bool step = false)
+    {
+        hipSetDevice(c->device);
+        if (!step && !c->pending.empty()) {
+            status = fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+            return;
+        }
+        g_prof = c->prof.on ? &c->prof : nullptr;
+        if (quiesce)
+            for (int k = 0; k < 2; ++k) hipStreamWaitEvent(c->stream, c->set[k].ev_done, 0);
+    }
+    ~CallScope() { g_prof = nullptr; }
+    CallScope(const CallScope&) = delete;
+};
+
 int vo_kernel_times(vo_ctx* c, const char** names, double* ms, int* calls, int capacity, int* n)
 {
     if (!c) return VO_ERR_ARG;
     hipSetDevice(c->device);
     if (c->prof.on) {                                  // asynchronous calls may still be in flight
-        g_prof = &c->prof;
         int rc = finish(c);
         if (rc) return rc;
     }
@@ -483,35 +482,6 @@ int vo_kernel_times(vo_ctx* c, const char** names, double* ms, int* calls, int c
     }
     return VO_OK;
 }
-
-// Synchronise the stream, collect profiling, translate errors.
-static int finish(vo_ctx* c)
-{
-    hipError_t e = hipStreamSynchronize(c->stream);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipStreamSynchronize(c->sub[k]);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->down);
-    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
-    if (c->prof.on) c->prof.collect();
-    g_prof = nullptr;
-    return VO_OK;
-}
-// quiesce: calls that run on `stream` over the context's own buffers first wait for any
-// batch still in flight on either buffer set (no host synchronisation)
-// Calls other than the step pipeline's own are refused while step batches are pending
-// (they reuse buffer set 0).
-static int begin_call(vo_ctx* c, bool quiesce = true, bool step = false)
-{
-    hipSetDevice(c->device);
-    if (!step && !c->pending.empty())
-        return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
-    g_prof = c->prof.on ? &c->prof : nullptr;
-    if (quiesce)
-        for (int k = 0; k < 2; ++k) hipStreamWaitEvent(c->stream, c->set[k].ev_done, 0);
-    return VO_OK;
-}
-#define BEGIN_CALL(...) do { int rc_ = begin_call(__VA_ARGS__); if (rc_) return rc_; } while (0)
 
 // MATLAB images are column-major: pixel (r, c) of image n at src[n * ld * cols + c * ld + r]
 // (ld >= rows).  32 x 32 LDS tile transpose into tightly packed row-major frames.
@@ -548,11 +518,8 @@ static int stage_images(vo_ctx* c, const uint8_t* img, int ld, int col_major, in
     // into its ld-byte slot (a padded view, ld > rows, must not be read past its end)
     const size_t need = (size_t)ld * ((size_t)cols * n - 1) + rows;
     if (need > c->cm_cap) {
-        HIPC(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_cm);
-        c->d_cm = nullptr;
-        c->cm_cap = 0;
-        HIPC(c, hipMalloc((void**)&c->d_cm, need));
+        HIPC(c, hipStreamSynchronize(c->stream));       // the old staging's last reader
+        HIPC(c, (hipError_t)c->pool.grow({DevPool::req(c->d_cm, need)}));
         c->cm_cap = need;
     }
     HIPC(c, hipMemcpyAsync(c->d_cm, img, need, hipMemcpyHostToDevice, c->stream));
@@ -566,7 +533,7 @@ int vo_sift_ex(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int co
     if (!c || !img || rows != c->rows || cols != c->cols || (col_major != 0 && col_major != 1) ||
         ld < (col_major ? rows : cols))
         return fail(c, VO_ERR_ARG, "vo_sift: bad arguments");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     int rc_stage = stage_images(c, img, ld, col_major, 1, c->d_img);
     if (rc_stage) return rc_stage;
     ImageSrc src{c->d_img, c->d_img, (size_t)rows * cols, cols, 0};
@@ -663,7 +630,7 @@ int vo_describe_batch(vo_ctx* c, const uint8_t* imgs, int ld, int col_major, int
             if (why) return fail(c, VO_ERR_ARG, "vo_describe: image %d point %d: %s", i, k, why);
         }
     if (total == 0) return VO_OK;                      // nothing to describe: nothing is launched
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     // tightly packed row-major images are one contiguous block: one copy (a 2-D copy of a pageable
     // buffer goes row by row -- 1.4 s for 512 images of 375 x 1242, profiles/describe_times.txt)
     if (!col_major && ld == c->cols) {
@@ -734,7 +701,7 @@ int vo_undistort(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int 
     bool trivial = false;
     if (!distortion_cam(d, &S.cam, &trivial))
         return fail(c, VO_ERR_ARG, "vo_undistort: intrinsics must be finite with fx, fy != 0, K[1][0] = 0 and a last row 0 0 1");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     // staging frame 0 = the image (row-major), frame 1 = the result
     const size_t fs = (size_t)rows * cols;
     int rc = stage_images(c, img, ld, col_major, 1, c->d_img);
@@ -765,13 +732,10 @@ int vo_undistort_batch_dev(vo_ctx* c, const uint8_t* d_in, int B, const vo_disto
     bool trivial = false;
     if (!distortion_cam(d, &S.cam, &trivial))
         return fail(c, VO_ERR_ARG, "vo_undistort_batch_dev: intrinsics must be finite with fx, fy != 0, K[1][0] = 0 and a last row 0 0 1");
-    BEGIN_CALL(c, false);
+    CallScope call(c, false); if (call.status) return call.status;
     S.in = d_in; S.out = d_out; S.copy = 0; S.pad = 0;
     undistort_launch(&S, 1, c->rows, c->cols, B, fs, fs, c->stream);
-    g_prof = nullptr;                                   // profiling events are collected by vo_kernel_times
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
-    return VO_OK;
+    return launch_status(c);                            // profiling events are collected by vo_kernel_times
 }
 
 int vo_set_distortion(vo_ctx* c, const vo_distortion* left, const vo_distortion* right)
@@ -791,7 +755,7 @@ int vo_set_distortion(vo_ctx* c, const vo_distortion* left, const vo_distortion*
     }
     if ((on[0] || on[1]) && !c->d_rect) {
         hipSetDevice(c->device);
-        HIPC(c, hipMalloc((void**)&c->d_rect, (size_t)2 * c->max_batch * c->rows * c->cols));
+        HIPC(c, (hipError_t)c->pool.alloc(c->d_rect, (size_t)2 * c->max_batch * c->rows * c->cols));
     }
     for (int k = 0; k < 2; ++k) {
         c->ud_on[k] = on[k];
@@ -819,9 +783,12 @@ int vo_fetch_rectified(vo_ctx* c, int image, uint8_t* out, int capacity)
 // The vo_fetch_* entries' shared start: wait for the last call's results, then pick the buffer set
 // that holds image slot `image`.  Image slots below 2 * max_batch (and the frames' pair slots with
 // them) are read from the last call's set (last_set: either set holds whole batches); the two carry
-// slots, 2 * max_batch and 2 * max_batch + 1, always from set 0.
-static int fetch_set(vo_ctx* c, int image, vo_ctx::BufferSet** S)
+// slots, 2 * max_batch and 2 * max_batch + 1, always from set 0.  detections: the entry `who` reads
+// what a detecting call left, which vo_describe does not leave.
+static int fetch_set(vo_ctx* c, int image, const char* who, bool detections, vo_ctx::BufferSet** S)
 {
+    if (detections && c->described)
+        return fail(c, VO_ERR_STATE, "%s: the last call described given points and detected nothing", who);
     hipSetDevice(c->device);
     HIPC(c, hipStreamSynchronize(c->stream));
     HIPC(c, hipEventSynchronize(c->set[c->last_set].ev_done));
@@ -849,7 +816,7 @@ int vo_set_strongest(vo_ctx* c, int n)
     if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "vo_set_strongest: step batches pending (vo_step_collect first)");
     if (n > 0) {
         hipSetDevice(c->device);
-        for (int k = 0; k < 2; ++k) HIPC(c, sift_alloc_select(c->set[k].sb));
+        for (int k = 0; k < 2; ++k) HIPC(c, sift_alloc_select(c->pool, c->set[k].sb));
     }
     c->strongest = n;
     return VO_OK;
@@ -858,9 +825,8 @@ int vo_set_strongest(vo_ctx* c, int n)
 int vo_fetch_detected_count(vo_ctx* c, int image, int* n_detected)
 {
     if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_detected_count: bad image");
-    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_detected_count: the last call described given points and detected nothing");
     vo_ctx::BufferSet* S = nullptr;
-    int rc = fetch_set(c, image, &S);
+    int rc = fetch_set(c, image, "vo_fetch_detected_count", true, &S);
     if (rc) return rc;
     int cnt = 0;
     HIPC(c, hipMemcpy(&cnt, (S->sel_used ? S->sb.n_det : S->sb.n_kp) + image, sizeof(int), hipMemcpyDeviceToHost));
@@ -868,106 +834,7 @@ int vo_fetch_detected_count(vo_ctx* c, int image, int* n_detected)
     return VO_OK;
 }
 
-// matchFeatures on the two staged descriptor sets d_fd[0] (n1 rows) / d_fd[1] (n2 rows)
-static int match_staged(vo_ctx* c, int n1, int n2, uint32_t* pairs, int capacity, int* n_pairs, const char* who)
-{
-    int nn[2] = {n1, n2};
-    HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
-    desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
-    desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
-    match_launch(c->set[0].mb, c->d_job_single, 1, c->mp, c->stream);
-    int P = 0;
-    HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    int rc = finish(c);
-    if (rc) return rc;
-    if (n_pairs) *n_pairs = P;
-    if ((rc = read_pairs(c, c->d_mi, c->d_mj, std::min(P, capacity), pairs))) return rc;
-    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
-    return VO_OK;
-}
-
-int vo_match(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, uint32_t* pairs, int capacity, int* n_pairs)
-{
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "vo_match: bad arguments");
-    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match: more rows than max_keypoints");
-    BEGIN_CALL(c);
-    if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
-    return match_staged(c, n1, n2, pairs, capacity, n_pairs, "vo_match");
-}
-
-// vo_match_f32 / vo_match_f32_ex: check the arguments, copy both matrices to the device as they
-// lie (d_ff) and pack them to u8 rows (d_fd); *bad = 1 if some value is not an integer in [0, 255]
-static int stage_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, int* bad,
-                     const char* who)
-{
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2) || (col_major != 0 && col_major != 1))
-        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
-    if ((n1 && ld1 < (col_major ? n1 : VO_DESC_LEN)) || (n2 && ld2 < (col_major ? n2 : VO_DESC_LEN)))
-        return fail(c, VO_ERR_ARG, "%s: leading dimension too small", who);
-    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
-    BEGIN_CALL(c);
-    HIPC(c, hipMemsetAsync(c->d_bad, 0, sizeof(int), c->stream));
-    const float* src[2] = {F1, F2};
-    const int n[2] = {n1, n2}, ld[2] = {ld1, ld2};
-    for (int s = 0; s < 2; ++s) {
-        if (!n[s]) continue;
-        // the matrix as it lies in host memory (MATLAB: n x 128 column-major, ld = n), one copy
-        const size_t elems = col_major ? (size_t)ld[s] * (VO_DESC_LEN - 1) + n[s] : (size_t)ld[s] * (n[s] - 1) + VO_DESC_LEN;
-        if (elems > (size_t)c->set[0].sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "%s: matrix exceeds staging", who);
-        HIPC(c, hipMemcpyAsync(c->d_ff[s], src[s], sizeof(float) * elems, hipMemcpyHostToDevice, c->stream));
-        pack_f32_desc_launch(c->d_ff[s], n[s], ld[s], col_major, c->d_fd[s], c->d_bad, c->stream);
-    }
-    HIPC(c, hipMemcpyAsync(bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
-}
-
-// the general-float path's buffers (normalised F1, transposed F2, per-row result)
-static int f32_buffers(vo_ctx* c, const char* who)
-{
-    if (c->d_fa && c->d_fbt && c->d_fres) return VO_OK;
-    // all three or none: a failed allocation leaves the context without any of them, so the
-    // next call allocates again instead of launching on a null buffer
-    const size_t fb = sizeof(float) * (size_t)c->set[0].sb.kp_cap * VO_DESC_LEN;
-    float* fa = nullptr; float* fbt = nullptr; int* fres = nullptr;
-    hipError_t e;
-    if ((e = hipMalloc((void**)&fa, fb)) != hipSuccess || (e = hipMalloc((void**)&fbt, fb)) != hipSuccess ||
-        (e = hipMalloc((void**)&fres, sizeof(int) * c->set[0].sb.kp_cap)) != hipSuccess) {
-        hipFree(fa); hipFree(fbt); hipFree(fres);
-        return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    hipFree(c->d_fa); hipFree(c->d_fbt); hipFree(c->d_fres);
-    c->d_fa = fa; c->d_fbt = fbt; c->d_fres = fres;
-    return VO_OK;
-}
-
-int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
-                 uint32_t* pairs, int capacity, int* n_pairs)
-{
-    int bad = 0;
-    int rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, "vo_match_f32");
-    if (rc) return rc;
-    // u8-valued rows (libvo / SIFT descriptors, what VO.m passes): the exact-integer spec of the
-    // hot path; any other single features: the float SSD spec (match_f32_launch)
-    if (!bad) return match_staged(c, n1, n2, pairs, capacity, n_pairs, "vo_match_f32");
-    if ((rc = f32_buffers(c, "vo_match_f32")) != VO_OK) return rc;
-    match_f32_launch(c->d_ff[0], n1, ld1, c->d_ff[1], n2, ld2, col_major, c->d_fa, c->d_fbt, c->d_fres, c->mp, c->stream);
-    std::vector<int> res((size_t)n1 + 1);
-    if (n1) HIPC(c, hipMemcpyAsync(res.data(), c->d_fres, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
-    rc = finish(c);
-    if (rc) return rc;
-    int P = 0;
-    for (int i = 0; i < n1; ++i) {
-        if (res[i] < 0) continue;
-        if (pairs && P < capacity) { pairs[2 * P] = (uint32_t)i + 1; pairs[2 * P + 1] = (uint32_t)res[i] + 1; }
-        ++P;
-    }
-    if (n_pairs) *n_pairs = P;
-    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "vo_match_f32: %d pairs exceed capacity %d", P, capacity);
-    return VO_OK;
-}
-
-// ---- matchFeatures with options: explicit thresholds, matchMetric, Unique -------------------
+// ---- matchFeatures; with options: explicit thresholds, matchMetric, Unique --------------------
 // opts == NULL: the context's parameters, unique 0
 static int match_opts_resolve(vo_ctx* c, const vo_match_opts* o, vo_match_params* p, int* unique, const char* who)
 {
@@ -986,6 +853,7 @@ static int match_opts_resolve(vo_ctx* c, const vo_match_opts* o, vo_match_params
     return VO_OK;
 }
 
+// what the entries with options need beyond vo_match's buffers, at the first such call
 static int match_ex_buffers(vo_ctx* c, const char* who)
 {
     if (c->mx.job_back) return VO_OK;
@@ -993,22 +861,25 @@ static int match_ex_buffers(vo_ctx* c, const char* who)
     memset(&J, 0, sizeof(J));
     J.d1 = c->d_fd[1]; J.m1 = c->d_fm[1]; J.n1 = c->d_fn + 1;
     J.d2 = c->d_fd[0]; J.m2 = c->d_fm[0]; J.n2 = c->d_fn;
-    const hipError_t e = match_ex_alloc(c->mx, c->set[0].mb, J);
+    const hipError_t e = match_ex_alloc(c->pool, c->mx, c->set[0].mb, J);
     if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return VO_OK;
 }
 
-// match_staged with options: d_fd[0] (n1 rows) / d_fd[1] (n2 rows) are staged; inside a call
-static int match_staged_ex(vo_ctx* c, int n1, int n2, const vo_match_params& p, int unique, uint32_t* pairs, float* metric,
-                           int capacity, int* n_pairs, const char* who)
+// matchFeatures on the two staged descriptor sets d_fd[0] (n1 rows) / d_fd[1] (n2 rows), inside a
+// call.  ex: the entry with options (parameters p, unique, the pairs' metric); else the context's
+// parameters through the hot path's match_launch.
+static int match_staged(vo_ctx* c, int n1, int n2, bool ex, const vo_match_params& p, int unique, uint32_t* pairs,
+                        float* metric, int capacity, int* n_pairs, const char* who)
 {
-    int rc = match_ex_buffers(c, who);
+    int rc = ex ? match_ex_buffers(c, who) : VO_OK;
     if (rc) return rc;
     int nn[2] = {n1, n2};
     HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
     desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
-    match_launch_ex(c->set[0].mb, c->d_job_single, c->mx, p, unique, c->stream);
+    if (ex) match_launch_ex(c->set[0].mb, c->d_job_single, c->mx, p, unique, c->stream);
+    else match_launch(c->set[0].mb, c->d_job_single, 1, c->mp, c->stream);
     int P = 0;
     HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     rc = finish(c);
@@ -1016,24 +887,99 @@ static int match_staged_ex(vo_ctx* c, int n1, int n2, const vo_match_params& p, 
     if (n_pairs) *n_pairs = P;
     const int m = std::min(P, capacity);
     if ((rc = read_pairs(c, c->d_mi, c->d_mj, m, pairs))) return rc;
-    if (m > 0 && metric) HIPC(c, hipMemcpy(metric, c->mx.metric, sizeof(float) * m, hipMemcpyDeviceToHost));
+    if (ex && m > 0 && metric) HIPC(c, hipMemcpy(metric, c->mx.metric, sizeof(float) * m, hipMemcpyDeviceToHost));
     if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
     return VO_OK;
+}
+
+// vo_match / vo_match_ex (ex: with opts and metric): check, upload both u8 sets, match
+static int match_u8(vo_ctx* c, const char* who, bool ex, const uint8_t* F1, int n1, const uint8_t* F2, int n2,
+                    const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs)
+{
+    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    vo_match_params p = c->mp;
+    int unique = 0;
+    int rc = ex ? match_opts_resolve(c, opts, &p, &unique, who) : VO_OK;
+    if (rc) return rc;
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
+    CallScope call(c); if (call.status) return call.status;
+    if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    return match_staged(c, n1, n2, ex, p, unique, pairs, metric, capacity, n_pairs, who);
+}
+
+int vo_match(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, uint32_t* pairs, int capacity, int* n_pairs)
+{
+    return match_u8(c, "vo_match", false, F1, n1, F2, n2, nullptr, pairs, nullptr, capacity, n_pairs);
 }
 
 int vo_match_ex(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, const vo_match_opts* opts, uint32_t* pairs,
                 float* metric, int capacity, int* n_pairs)
 {
-    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "vo_match_ex: bad arguments");
-    vo_match_params p;
-    int unique = 0;
-    int rc = match_opts_resolve(c, opts, &p, &unique, "vo_match_ex");
+    return match_u8(c, "vo_match_ex", true, F1, n1, F2, n2, opts, pairs, metric, capacity, n_pairs);
+}
+
+// vo_match_f32 / vo_match_f32_ex: check the arguments, copy both matrices to the device as they
+// lie (d_ff) and pack them to u8 rows (d_fd); *bad = 1 if some value is not an integer in [0, 255]
+static int stage_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, int* bad,
+                     const char* who)
+{
+    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2) || (col_major != 0 && col_major != 1))
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    if ((n1 && ld1 < (col_major ? n1 : VO_DESC_LEN)) || (n2 && ld2 < (col_major ? n2 : VO_DESC_LEN)))
+        return fail(c, VO_ERR_ARG, "%s: leading dimension too small", who);
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
+    CallScope call(c); if (call.status) return call.status;
+    HIPC(c, hipMemsetAsync(c->d_bad, 0, sizeof(int), c->stream));
+    const float* src[2] = {F1, F2};
+    const int n[2] = {n1, n2}, ld[2] = {ld1, ld2};
+    for (int s = 0; s < 2; ++s) {
+        if (!n[s]) continue;
+        // the matrix as it lies in host memory (MATLAB: n x 128 column-major, ld = n), one copy
+        const size_t elems = col_major ? (size_t)ld[s] * (VO_DESC_LEN - 1) + n[s] : (size_t)ld[s] * (n[s] - 1) + VO_DESC_LEN;
+        if (elems > (size_t)c->set[0].sb.kp_cap * VO_DESC_LEN) return fail(c, VO_ERR_CAPACITY, "%s: matrix exceeds staging", who);
+        HIPC(c, hipMemcpyAsync(c->d_ff[s], src[s], sizeof(float) * elems, hipMemcpyHostToDevice, c->stream));
+        pack_f32_desc_launch(c->d_ff[s], n[s], ld[s], col_major, c->d_fd[s], c->d_bad, c->stream);
+    }
+    HIPC(c, hipMemcpyAsync(bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+// the general-float path's buffers (normalised F1, transposed F2, per-row result): all three or
+// none, so after a failed allocation the next call allocates again instead of launching on null
+static int f32_buffers(vo_ctx* c, const char* who)
+{
+    if (c->d_fa) return VO_OK;
+    const size_t K = c->set[0].sb.kp_cap;
+    const int e = c->pool.group({DevPool::req(c->d_fa, K * VO_DESC_LEN), DevPool::req(c->d_fbt, K * VO_DESC_LEN),
+                                 DevPool::req(c->d_fres, K)});
+    return e ? fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString((hipError_t)e)) : VO_OK;
+}
+
+int vo_match_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                 uint32_t* pairs, int capacity, int* n_pairs)
+{
+    int bad = 0;
+    int rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, "vo_match_f32");
     if (rc) return rc;
-    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_match_ex: more rows than max_keypoints");
-    BEGIN_CALL(c);
-    if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
-    return match_staged_ex(c, n1, n2, p, unique, pairs, metric, capacity, n_pairs, "vo_match_ex");
+    // u8-valued rows (libvo / SIFT descriptors, what VO.m passes): the exact-integer spec of the
+    // hot path; any other single features: the float SSD spec (match_f32_launch)
+    if (!bad) return match_staged(c, n1, n2, false, c->mp, 0, pairs, nullptr, capacity, n_pairs, "vo_match_f32");
+    if ((rc = f32_buffers(c, "vo_match_f32")) != VO_OK) return rc;
+    match_f32_launch(c->d_ff[0], n1, ld1, c->d_ff[1], n2, ld2, col_major, c->d_fa, c->d_fbt, c->d_fres, c->mp, c->stream);
+    std::vector<int> res((size_t)n1 + 1);
+    if (n1) HIPC(c, hipMemcpyAsync(res.data(), c->d_fres, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
+    rc = finish(c);
+    if (rc) return rc;
+    int P = 0;
+    for (int i = 0; i < n1; ++i) {
+        if (res[i] < 0) continue;
+        if (pairs && P < capacity) { pairs[2 * P] = (uint32_t)i + 1; pairs[2 * P + 1] = (uint32_t)res[i] + 1; }
+        ++P;
+    }
+    if (n_pairs) *n_pairs = P;
+    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "vo_match_f32: %d pairs exceed capacity %d", P, capacity);
+    return VO_OK;
 }
 
 int vo_match_f32_ex(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
@@ -1047,11 +993,11 @@ int vo_match_f32_ex(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2
     int bad = 0;
     if ((rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, "vo_match_f32_ex")) != VO_OK) return rc;
     if (!bad) {
-        BEGIN_CALL(c);
-        return match_staged_ex(c, n1, n2, p, unique, pairs, metric, capacity, n_pairs, "vo_match_f32_ex");
+        CallScope call(c); if (call.status) return call.status;
+        return match_staged(c, n1, n2, true, p, unique, pairs, metric, capacity, n_pairs, "vo_match_f32_ex");
     }
     if ((rc = f32_buffers(c, "vo_match_f32_ex")) != VO_OK || (rc = match_ex_buffers(c, "vo_match_f32_ex")) != VO_OK) return rc;
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     match_f32_launch_ex(c->d_ff[0], n1, ld1, c->d_ff[1], n2, ld2, col_major, c->d_fa, c->d_fbt, c->d_fres, c->mx.metric,
                         c->mx.back, p, unique, c->stream);
     std::vector<int> res((size_t)n1 + 1), back((size_t)n2 + 1);
@@ -1110,7 +1056,7 @@ static int capacity_flags(const SiftBuffers& sb, const int* nkp, const int* ncan
 //           after ev_top and ev_join (both chains) the extremum test of octaves 1.., the feature
 //           stages and the stereo match.  ev_arena and ev_done are recorded here, so they cover
 //           both chains: the set's next call, the batch's slot event of the pipelined loop and
-//           begin_call's quiesce wait for them as before.
+//           CallScope's quiesce wait for them as before.
 // Forking after octave 0's level L instead (octaves 1.. beside octave 0's two widest blurs), with or
 // without octave 1's top levels back on sub[0], and the down stream at another priority all measured
 // 1-3 % slower than one chain: ev_o0 fires 9 ms later and the feature stream becomes the critical one
@@ -1206,19 +1152,14 @@ static int enqueue_sift_stereo(vo_ctx* c, int set, const uint8_t* d_l, const uin
 int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_rights, int B, vo_pair_stats* stats)
 {
     if (!c || !d_lefts || !d_rights || B < 1 || B > c->max_batch) return fail(c, VO_ERR_ARG, "vo_sift_match_batch_dev: bad arguments");
-    BEGIN_CALL(c, false);
+    CallScope call(c, false); if (call.status) return call.status;
     const int set = c->next_set;
     c->next_set ^= 1;
     const bool sync = stats != nullptr;      // profiling events are collected by vo_kernel_times
     int rc = enqueue_sift_stereo(c, set, d_lefts, d_rights, B, sync, true);
     if (rc) return rc;
     c->last_B = B;
-    if (!sync) {
-        g_prof = nullptr;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
-        return VO_OK;
-    }
+    if (!sync) return launch_status(c);
     const vo_ctx::BufferSet& S = c->set[set];
     std::vector<int> nk(2 * B), nc(2 * B), np(B);
     std::vector<int> nd;                     // detected counts: the flags' input (selection off: nk)
@@ -1243,9 +1184,8 @@ int vo_sift_match_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_
 int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, int capacity, int* n)
 {
     if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_keypoints: bad image");
-    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_keypoints: the last call described given points and detected nothing");
     vo_ctx::BufferSet* S = nullptr;
-    int rc = fetch_set(c, image, &S);
+    int rc = fetch_set(c, image, "vo_fetch_keypoints", true, &S);
     if (rc) return rc;
     const SiftBuffers& B = S->sb;
     int cnt = 0;
@@ -1262,9 +1202,8 @@ int vo_fetch_keypoints(vo_ctx* c, int image, vo_keypoint* kps, uint8_t* desc, in
 int vo_fetch_candidate_counts(vo_ctx* c, int image, int* n_cand, int* n_accepted)
 {
     if (!c || image < 0 || image >= c->set[0].sb.n_img) return fail(c, VO_ERR_ARG, "vo_fetch_candidate_counts: bad image");
-    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_candidate_counts: the last call described given points and detected nothing");
     vo_ctx::BufferSet* S = nullptr;
-    int rc = fetch_set(c, image, &S);
+    int rc = fetch_set(c, image, "vo_fetch_candidate_counts", true, &S);
     if (rc) return rc;
     const SiftBuffers& B = S->sb;
     int v[2] = {0, 0};
@@ -1281,7 +1220,7 @@ int vo_fetch_gaussian(vo_ctx* c, int image, int octave, int level, float* out, i
         level >= c->py.L + 3)
         return fail(c, VO_ERR_ARG, "vo_fetch_gaussian: bad image/octave/level");
     vo_ctx::BufferSet* S = nullptr;
-    int rc = fetch_set(c, image, &S);
+    int rc = fetch_set(c, image, "vo_fetch_gaussian", false, &S);
     if (rc) return rc;
     const SiftBuffers& B = S->sb;
     const OctGeom& g = c->py.oct[octave];
@@ -1298,9 +1237,8 @@ int vo_fetch_gaussian(vo_ctx* c, int image, int octave, int level, float* out, i
 int vo_fetch_stereo_pairs(vo_ctx* c, int frame, uint32_t* pairs, int capacity, int* n)
 {
     if (!c || frame < 0 || frame >= c->max_batch) return fail(c, VO_ERR_ARG, "vo_fetch_stereo_pairs: bad frame");
-    if (c->described) return fail(c, VO_ERR_STATE, "vo_fetch_stereo_pairs: the last call described given points and detected nothing");
     vo_ctx::BufferSet* S = nullptr;
-    int rc = fetch_set(c, 2 * frame, &S);                  // the frame's images and its pair slot: one set
+    int rc = fetch_set(c, 2 * frame, "vo_fetch_stereo_pairs", true, &S);   // the frame's images and its pair slot: one set
     if (rc) return rc;
     int P = 0;
     HIPC(c, hipMemcpy(&P, S->pair_n + frame, sizeof(int), hipMemcpyDeviceToHost));
@@ -1422,8 +1360,7 @@ static int submit_batch(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B
     lm_pack_launch(S.gb, B, H.d_pX, H.d_pkeep, c->stream);
     if ((rc = enqueue_carry(c, set, B - 1, set ^ 1))) return rc;
     HIPC(c, hipEventRecord(H.ev, c->stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
+    if ((rc = launch_status(c))) return rc;
     c->pending.push_back({set, slot, B, c->have_features, c->strongest > 0});
     c->next_step_set ^= 1;
     c->next_slot = (slot + 1) % VO_STEP_DEPTH;
@@ -1440,7 +1377,6 @@ static int collect_batch(vo_ctx* c, vo_step_out* outs, int capacity, int* n_out)
     const int K = c->set[0].sb.kp_cap, B = P.B;
     const vo_ctx::StepHost& H = c->sh[P.slot];
     if (c->prof.on) {                                  // profiling: events of every stream are collected
-        g_prof = &c->prof;
         int rc = finish(c);
         if (rc) return rc;
     } else {
@@ -1460,28 +1396,26 @@ static int collect_batch(vo_ctx* c, vo_step_out* outs, int capacity, int* n_out)
         const size_t first = (P.first_tracked ? 0 : roff[1]), add = total - first;
         if (add > 0) {
             if (c->lm_n + add > c->lm_cap) {
-                size_t cap = std::max<size_t>({c->lm_n + add, 2 * c->lm_cap, (size_t)1 << 16});
-                float* nX = nullptr; uint8_t* nk = nullptr;
-                if (hipMalloc((void**)&nX, sizeof(float) * 3 * cap) != hipSuccess ||
-                    hipMalloc((void**)&nk, cap) != hipSuccess) {
-                    hipFree(nX);
-                    return fail(c, VO_ERR_HIP, "vo_step_collect: landmark store of %zu rows", cap);
-                }
                 // the store at least doubles; the old one is copied on `stream` (in order with the
                 // appends) and retired until reset / destroy, so growth never waits for the pipeline
+                const size_t cap = std::max<size_t>({c->lm_n + add, 2 * c->lm_cap, (size_t)1 << 16}), n_retired = c->lm_retired.size();
+                float* oX = c->d_lmX;
+                uint8_t* ok = c->d_lmkeep;
+                if (c->pool.grow({DevPool::req(c->d_lmX, 3 * cap), DevPool::req(c->d_lmkeep, cap)}, &c->lm_retired))
+                    return fail(c, VO_ERR_HIP, "vo_step_collect: landmark store of %zu rows", cap);
                 hipError_t ge = hipSuccess;
                 if (c->lm_n > 0) {
-                    ge = hipMemcpyAsync(nX, c->d_lmX, sizeof(float) * 3 * c->lm_n, hipMemcpyDeviceToDevice, c->stream);
-                    if (ge == hipSuccess) ge = hipMemcpyAsync(nk, c->d_lmkeep, c->lm_n, hipMemcpyDeviceToDevice, c->stream);
+                    ge = hipMemcpyAsync(c->d_lmX, oX, sizeof(float) * 3 * c->lm_n, hipMemcpyDeviceToDevice, c->stream);
+                    if (ge == hipSuccess) ge = hipMemcpyAsync(c->d_lmkeep, ok, c->lm_n, hipMemcpyDeviceToDevice, c->stream);
                 }
                 if (ge != hipSuccess) {
                     (void)hipStreamSynchronize(c->stream);   // the copies may be queued: let them drain
-                    hipFree(nX); hipFree(nk);
+                    c->pool.release(c->d_lmX); c->pool.release(c->d_lmkeep);
+                    c->d_lmX = oX; c->d_lmkeep = ok;         // back to the old store, no longer retired
+                    c->lm_retired.resize(n_retired);
                     return fail(c, VO_ERR_HIP, "vo_step_collect: landmark store growth: %s", hipGetErrorString(ge));
                 }
-                if (c->d_lmX) c->lm_retired.push_back(c->d_lmX);
-                if (c->d_lmkeep) c->lm_retired.push_back(c->d_lmkeep);
-                c->d_lmX = nX; c->d_lmkeep = nk; c->lm_cap = cap;
+                c->lm_cap = cap;
             }
             HIPC(c, hipMemcpyAsync(c->d_lmX + 3 * c->lm_n, H.d_pX + 3 * first, sizeof(float) * 3 * add,
                                    hipMemcpyDeviceToDevice, c->stream));
@@ -1546,10 +1480,8 @@ extern "C" {
 int vo_step_batch_dev(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B, vo_step_out* outs)
 {
     if (!c || !d_l || !d_r || !outs || B < 1 || B > c->max_batch) return fail(c, VO_ERR_ARG, "vo_step_batch_dev: bad arguments");
-    BEGIN_CALL(c);
-    int rc = run_batch(c, d_l, d_r, B, outs);
-    g_prof = nullptr;
-    return rc;
+    CallScope call(c); if (call.status) return call.status;
+    return run_batch(c, d_l, d_r, B, outs);
 }
 
 int vo_step_batch_ex(vo_ctx* c, const uint8_t* lefts, const uint8_t* rights, int ld, int col_major, int B, vo_step_out* outs)
@@ -1557,15 +1489,13 @@ int vo_step_batch_ex(vo_ctx* c, const uint8_t* lefts, const uint8_t* rights, int
     if (!c || !lefts || !rights || !outs || B < 1 || B > c->max_batch || (col_major != 0 && col_major != 1) ||
         ld < (col_major ? c->rows : c->cols))
         return fail(c, VO_ERR_ARG, "vo_step_batch: bad arguments");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     const size_t fs = (size_t)c->rows * c->cols;
     uint8_t* dl = c->d_img;
     uint8_t* dr = c->d_img + fs * B;
     int rc = stage_images(c, lefts, ld, col_major, B, dl);
     if (!rc) rc = stage_images(c, rights, ld, col_major, B, dr);
-    if (!rc) rc = run_batch(c, dl, dr, B, outs);
-    g_prof = nullptr;
-    return rc;
+    return rc ? rc : run_batch(c, dl, dr, B, outs);
 }
 
 int vo_step_batch(vo_ctx* c, const uint8_t* lefts, const uint8_t* rights, int ld, int B, vo_step_out* outs)
@@ -1581,36 +1511,43 @@ int vo_step(vo_ctx* c, const uint8_t* left, const uint8_t* right, int ld, vo_ste
 int vo_step_submit_dev(vo_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int B)
 {
     if (!c || !d_l || !d_r || B < 1 || B > c->max_batch) return fail(c, VO_ERR_ARG, "vo_step_submit_dev: bad arguments");
-    BEGIN_CALL(c, false, true);
+    CallScope call(c, false, true); if (call.status) return call.status;
     // the first batch of a pipeline is ordered after earlier work on `stream`; later ones
     // overlap the previous batch's geometry (their inputs must be ready at the call)
-    int rc = submit_batch(c, d_l, d_r, B, c->pending.empty());
-    if (!c->prof.on) g_prof = nullptr;
-    return rc;
+    return submit_batch(c, d_l, d_r, B, c->pending.empty());
 }
 
 int vo_step_collect(vo_ctx* c, vo_step_out* outs, int capacity, int* n)
 {
     if (!c || !outs) return fail(c, VO_ERR_ARG, "vo_step_collect: bad arguments");
     hipSetDevice(c->device);
-    int rc = collect_batch(c, outs, capacity, n);
-    g_prof = nullptr;
-    return rc;
+    return collect_batch(c, outs, capacity, n);
 }
 
 int vo_steps_pending(const vo_ctx* c) { return c ? (int)c->pending.size() : 0; }
+
+// The start of the entries that read the last collected step batch: frame in that batch, and its
+// buffer set not reused by a pending one.  Selects the device.
+static int collected_set(vo_ctx* c, int frame, const char* who, const vo_ctx::BufferSet** S)
+{
+    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
+        return fail(c, VO_ERR_STATE, "%s: frame %d not in the last collected batch", who, frame);
+    for (const vo_ctx::Pending& q : c->pending)
+        if (q.set == c->last_step_set)
+            return fail(c, VO_ERR_STATE, "%s: the collected batch's buffer set is reused by a pending batch", who);
+    hipSetDevice(c->device);
+    *S = &c->set[c->last_step_set];
+    return VO_OK;
+}
 
 int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* world, float* det, int capacity,
                     int* n_tracked, int* n_det)
 {
     if (!c || capacity < 0) return fail(c, VO_ERR_ARG, "vo_fetch_tracks: bad arguments");
-    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
-        return fail(c, VO_ERR_STATE, "vo_fetch_tracks: frame %d not in the last collected batch", frame);
-    for (const vo_ctx::Pending& q : c->pending)
-        if (q.set == c->last_step_set)
-            return fail(c, VO_ERR_STATE, "vo_fetch_tracks: the collected batch's buffer set is reused by a pending batch");
-    hipSetDevice(c->device);
-    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    const vo_ctx::BufferSet* Sp = nullptr;
+    int rc = collected_set(c, frame, "vo_fetch_tracks", &Sp);
+    if (rc) return rc;
+    const vo_ctx::BufferSet& S = *Sp;
     const int K = c->set[0].sb.kp_cap;
     int n = 0, nd = 0;
     HIPC(c, hipMemcpy(&n, S.gb.list_n + 4 * frame + 3, sizeof(int), hipMemcpyDeviceToHost));
@@ -1642,22 +1579,18 @@ int vo_fetch_tracks(vo_ctx* c, int frame, float* old_l, float* cur_l, double* wo
 // the quality buffers of vo_triangulate_ex / vo_fetch_track_quality, at the first call that needs them
 static int tri_quality_buffers(vo_ctx* c)
 {
-    const int K = c->set[0].sb.kp_cap;
-    if (!c->d_tq_err) HIPC(c, hipMalloc((void**)&c->d_tq_err, sizeof(float) * K));
-    if (!c->d_tq_valid) HIPC(c, hipMalloc((void**)&c->d_tq_valid, (size_t)K));
+    const size_t K = c->set[0].sb.kp_cap;
+    if (!c->d_tq_err) HIPC(c, (hipError_t)c->pool.group({DevPool::req(c->d_tq_err, K), DevPool::req(c->d_tq_valid, K)}));
     return VO_OK;
 }
 
 int vo_fetch_track_quality(vo_ctx* c, int frame, float* old_r, float* reproj_err, uint8_t* valid, int capacity, int* n_tracked)
 {
     if (!c || capacity < 0) return fail(c, VO_ERR_ARG, "vo_fetch_track_quality: bad arguments");
-    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
-        return fail(c, VO_ERR_STATE, "vo_fetch_track_quality: frame %d not in the last collected batch", frame);
-    for (const vo_ctx::Pending& q : c->pending)
-        if (q.set == c->last_step_set)
-            return fail(c, VO_ERR_STATE, "vo_fetch_track_quality: the collected batch's buffer set is reused by a pending batch");
-    hipSetDevice(c->device);
-    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    const vo_ctx::BufferSet* Sp = nullptr;
+    int rc = collected_set(c, frame, "vo_fetch_track_quality", &Sp);
+    if (rc) return rc;
+    const vo_ctx::BufferSet& S = *Sp;
     const int K = c->set[0].sb.kp_cap;
     int n = 0;
     HIPC(c, hipMemcpy(&n, S.gb.list_n + 4 * frame + 3, sizeof(int), hipMemcpyDeviceToHost));
@@ -1674,8 +1607,7 @@ int vo_fetch_track_quality(vo_ctx* c, int frame, float* old_r, float* reproj_err
         // the collected batch's geometry is complete (vo_step_collect waited for it) and a pending
         // batch works on the other set, so the kernel runs on the copy stream, which holds no work
         // between calls, beside whatever `stream` still has queued
-        int rc = tri_quality_buffers(c);
-        if (rc) return rc;
+        if ((rc = tri_quality_buffers(c))) return rc;
         tri_quality_launch(S.gb.oldpos + (size_t)frame * K * 4, S.gb.world + (size_t)frame * K * 3, S.gb.list_n + 4 * frame + 3, 4,
                            0, 1, K, c->calib, c->d_tq_err, c->d_tq_valid, c->copy_stream);
         if (reproj_err) HIPC(c, hipMemcpyAsync(reproj_err, c->d_tq_err, sizeof(float) * m, hipMemcpyDeviceToHost, c->copy_stream));
@@ -1741,19 +1673,16 @@ int vo_landmarks_world_dev(vo_ctx* c, const double* poses, int n_frames, float* 
     if (r > capacity) return fail(c, VO_ERR_CAPACITY, "vo_landmarks_world_dev: %ld rows exceed capacity %ld", r, capacity);
     hipSetDevice(c->device);
     if (nf > c->lmw_cap) {
-        hipFree(c->d_lmw_pose); hipFree(c->d_lmw_off);
-        c->d_lmw_pose = nullptr; c->d_lmw_off = nullptr; c->lmw_cap = 0;
         const int cap = std::max(nf, 1024);
-        HIPC(c, hipMalloc((void**)&c->d_lmw_pose, sizeof(double) * 16 * cap));
-        HIPC(c, hipMalloc((void**)&c->d_lmw_off, sizeof(long long) * (cap + 1)));
+        HIPC(c, (hipError_t)c->pool.grow({DevPool::req(c->d_lmw_pose, (size_t)16 * cap), DevPool::req(c->d_lmw_off, (size_t)cap + 1)}));
         c->lmw_cap = cap;
     }
     HIPC(c, hipMemcpyAsync(c->d_lmw_pose, poses, sizeof(double) * 16 * nf, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_lmw_off, c->lm_frame_off.data(), sizeof(long long) * (nf + 1), hipMemcpyHostToDevice,
                            c->stream));
     lm_world_launch(c->d_lmw_pose, c->d_lmw_off, nf, c->d_lmX, c->d_lmkeep, d_out, c->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, VO_ERR_HIP, "launch: %s", hipGetErrorString(e));
+    const int rc = launch_status(c);
+    if (rc) return rc;
     // d_out is read by the caller's streams (torch, RCCL) next: complete before returning
     HIPC(c, hipStreamSynchronize(c->stream));
     return VO_OK;
@@ -1808,7 +1737,7 @@ int vo_reset(vo_ctx* c)
     c->pending.clear();
     c->next_step_set = 0;
     c->next_slot = 0;
-    for (void* p : c->lm_retired) hipFree(p);
+    for (void*& p : c->lm_retired) c->pool.release(p);
     c->lm_retired.clear();
     c->last_step_set = -1;
     c->have_features = false;
@@ -1846,7 +1775,7 @@ int vo_track(vo_ctx* c, const uint8_t* old_l, const uint8_t* old_r, int n_old, c
     if (!c || n_old < 0 || n_cl < 0 || n_cr < 0) return fail(c, VO_ERR_ARG, "vo_track: bad arguments");
     const int K = c->set[0].sb.kp_cap, M = c->max_batch;
     if (n_old > K || n_cl > K || n_cr > K) return fail(c, VO_ERR_CAPACITY, "vo_track: more rows than max_keypoints");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     c->have_features = false;
     c->last_set = 0;                                   // set 0's descriptor slots are overwritten
     c->set[0].sel_used = false;
@@ -1885,63 +1814,49 @@ int vo_track(vo_ctx* c, const uint8_t* old_l, const uint8_t* old_r, int n_old, c
     return VO_OK;
 }
 
-int vo_triangulate(vo_ctx* c, const float* x1, const float* x2, int n, const double P1[12], const double P2[12], double* X)
+// two [n][2] float arrays interleaved into quads out [n][4] = (a.x, a.y, b.x, b.y)
+static void pack_quads(const float* a, const float* b, int n, float* out)
 {
-    if (!c || n < 0 || (n && (!x1 || !x2 || !X)) || !P1 || !P2) return fail(c, VO_ERR_ARG, "vo_triangulate: bad arguments");
-    BEGIN_CALL(c);
-    const vo_calib cal = calib_of(P1, P2, nullptr);
-    const int K = c->set[0].sb.kp_cap;
-    std::vector<float> q((size_t)std::min(n, K) * 4 + 4);
-    for (int b = 0; b < n; b += K) {
-        const int m = std::min(K, n - b);
-        for (int k = 0; k < m; ++k) {
-            q[4 * k] = x1[2 * (b + k)]; q[4 * k + 1] = x1[2 * (b + k) + 1];
-            q[4 * k + 2] = x2[2 * (b + k)]; q[4 * k + 3] = x2[2 * (b + k) + 1];
-        }
-        HIPC(c, hipMemcpyAsync(c->set[0].gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
-        triangulate_launch(c->set[0].gb.oldpos, m, cal, c->set[0].gb.world, c->stream);
-        HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, c->set[0].gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
-        int rc = finish(c);
-        if (rc) return rc;
-        g_prof = c->prof.on ? &c->prof : nullptr;
-    }
-    g_prof = nullptr;
-    return VO_OK;
+    for (int k = 0; k < n; ++k) { out[4 * k] = a[2 * k]; out[4 * k + 1] = a[2 * k + 1]; out[4 * k + 2] = b[2 * k]; out[4 * k + 3] = b[2 * k + 1]; }
 }
 
-int vo_triangulate_ex(vo_ctx* c, const float* x1, const float* x2, int n, const double P1[12], const double P2[12], double* X,
-                      float* reproj_err, uint8_t* valid)
+// vo_triangulate / vo_triangulate_ex: chunks of max_keypoints points through set 0's frame slot 0,
+// one k_tri_list each and, only when reproj_err or valid is asked for, one k_tri_quality
+static int triangulate_chunks(vo_ctx* c, const char* who, const float* x1, const float* x2, int n, const double P1[12],
+                              const double P2[12], double* X, float* reproj_err, uint8_t* valid)
 {
-    if (!reproj_err && !valid) return vo_triangulate(c, x1, x2, n, P1, P2, X);
-    if (!c || n < 0 || (n && (!x1 || !x2 || !X)) || !P1 || !P2) return fail(c, VO_ERR_ARG, "vo_triangulate_ex: bad arguments");
-    BEGIN_CALL(c);
-    if (n == 0) { g_prof = nullptr; return VO_OK; }
-    {
-        int rc = tri_quality_buffers(c);
-        if (rc) { g_prof = nullptr; return rc; }
-    }
+    if (!c || n < 0 || (n && (!x1 || !x2 || !X)) || !P1 || !P2) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    CallScope call(c); if (call.status) return call.status;
+    const bool quality = reproj_err || valid;
+    int rc = quality && n > 0 ? tri_quality_buffers(c) : VO_OK;
+    if (rc) return rc;
     const vo_calib cal = calib_of(P1, P2, nullptr);
     const int K = c->set[0].sb.kp_cap;
     const GeomBuffers& gb = c->set[0].gb;
     std::vector<float> q((size_t)std::min(n, K) * 4 + 4);
     for (int b = 0; b < n; b += K) {
         const int m = std::min(K, n - b);
-        for (int k = 0; k < m; ++k) {
-            q[4 * k] = x1[2 * (b + k)]; q[4 * k + 1] = x1[2 * (b + k) + 1];
-            q[4 * k + 2] = x2[2 * (b + k)]; q[4 * k + 3] = x2[2 * (b + k) + 1];
-        }
+        pack_quads(x1 + 2 * (size_t)b, x2 + 2 * (size_t)b, m, q.data());
         HIPC(c, hipMemcpyAsync(gb.oldpos, q.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, c->stream));
         triangulate_launch(gb.oldpos, m, cal, gb.world, c->stream);
-        tri_quality_launch(gb.oldpos, gb.world, nullptr, 0, m, 1, K, cal, c->d_tq_err, c->d_tq_valid, c->stream);
+        if (quality) tri_quality_launch(gb.oldpos, gb.world, nullptr, 0, m, 1, K, cal, c->d_tq_err, c->d_tq_valid, c->stream);
         HIPC(c, hipMemcpyAsync(X + 3 * (size_t)b, gb.world, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, c->stream));
         if (reproj_err) HIPC(c, hipMemcpyAsync(reproj_err + b, c->d_tq_err, sizeof(float) * m, hipMemcpyDeviceToHost, c->stream));
         if (valid) HIPC(c, hipMemcpyAsync(valid + b, c->d_tq_valid, (size_t)m, hipMemcpyDeviceToHost, c->stream));
-        int rc = finish(c);
-        if (rc) return rc;
-        g_prof = c->prof.on ? &c->prof : nullptr;
+        if ((rc = finish(c))) return rc;                // q is reused by the next chunk
     }
-    g_prof = nullptr;
     return VO_OK;
+}
+
+int vo_triangulate(vo_ctx* c, const float* x1, const float* x2, int n, const double P1[12], const double P2[12], double* X)
+{
+    return triangulate_chunks(c, "vo_triangulate", x1, x2, n, P1, P2, X, nullptr, nullptr);
+}
+
+int vo_triangulate_ex(vo_ctx* c, const float* x1, const float* x2, int n, const double P1[12], const double P2[12], double* X,
+                      float* reproj_err, uint8_t* valid)
+{
+    return triangulate_chunks(c, reproj_err || valid ? "vo_triangulate_ex" : "vo_triangulate", x1, x2, n, P1, P2, X, reproj_err, valid);
 }
 
 int vo_estworldpose(vo_ctx* c, const double* img, const double* world, int n, const double K9[9],
@@ -1955,7 +1870,7 @@ int vo_estworldpose(vo_ctx* c, const double* img, const double* world, int n, co
                     rp.max_num_trials, c->set[0].gb.n_hyp);
     if (n_inliers) *n_inliers = 0;
     if (n < 4) return fail(c, VO_ERR_TOO_FEW_POINTS, "estworldpose: need at least 4 points, got %d", n);
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     c->have_features = false;
     HIPC(c, hipMemcpyAsync(c->set[0].gb.imgpt, img, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->set[0].gb.world, world, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
@@ -2009,15 +1924,14 @@ int vo_refine_pose(vo_ctx* c, const double* img, const double* world, int n, con
     if ((bad = first_non_finite(T_in, 16)) >= 0) return fail(c, VO_ERR_ARG, "vo_refine_pose: T_in[%ld] is not finite", bad);
     if (T_in[12] != 0.0 || T_in[13] != 0.0 || T_in[14] != 0.0 || T_in[15] != 1.0)
         return fail(c, VO_ERR_ARG, "vo_refine_pose: the last row of T_in is not 0 0 0 1");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     if (n == 0) {                                       // nothing to launch: the pass over no points
         memcpy(T_out, T_in, sizeof(double) * 16);
         if (stats) *stats = vo_refine_stats{VO_REFINE_TOO_FEW, 0, 1, 0, 0.0, 0.0};
-        g_prof = nullptr;
         return VO_OK;
     }
     GeomBuffers& gb = c->set[0].gb;
-    HIPC(c, geom_alloc_refine(gb));
+    HIPC(c, geom_alloc_refine(c->pool, gb));
     c->have_features = false;
     c->set[0].refine_used = false;                      // slot 0 of the set's stats is overwritten
     std::vector<uint8_t> ones;
@@ -2047,7 +1961,7 @@ int vo_set_pose_refinement(vo_ctx* c, const vo_refine_params* p)
     if (const char* field = refine_params_refusal(*p))
         return fail(c, VO_ERR_ARG, "vo_set_pose_refinement: parameter out of range: %s", field);
     hipSetDevice(c->device);
-    for (int k = 0; k < 2; ++k) HIPC(c, geom_alloc_refine(c->set[k].gb));
+    for (int k = 0; k < 2; ++k) HIPC(c, geom_alloc_refine(c->pool, c->set[k].gb));
     c->refine = *p;
     c->refine_on = true;
     return VO_OK;
@@ -2056,15 +1970,12 @@ int vo_set_pose_refinement(vo_ctx* c, const vo_refine_params* p)
 int vo_fetch_pose_refinement(vo_ctx* c, int frame, vo_refine_stats* out)
 {
     if (!c || !out) return fail(c, VO_ERR_ARG, "vo_fetch_pose_refinement: bad arguments");
-    if (c->last_step_set < 0 || frame < 0 || frame >= c->last_step_B)
-        return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: frame %d not in the last collected batch", frame);
-    for (const vo_ctx::Pending& q : c->pending)
-        if (q.set == c->last_step_set)
-            return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: the collected batch's buffer set is reused by a pending batch");
-    const vo_ctx::BufferSet& S = c->set[c->last_step_set];
+    const vo_ctx::BufferSet* Sp = nullptr;
+    int rc = collected_set(c, frame, "vo_fetch_pose_refinement", &Sp);
+    if (rc) return rc;
+    const vo_ctx::BufferSet& S = *Sp;
     if (!S.refine_used || !S.gb.refine)
         return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: the batch ran without pose refinement (vo_set_pose_refinement)");
-    hipSetDevice(c->device);
     HIPC(c, hipMemcpy(out, S.gb.refine + frame, sizeof(*out), hipMemcpyDeviceToHost));
     return VO_OK;
 }
@@ -2077,11 +1988,11 @@ int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const
     if (!c->has_calib) return fail(c, VO_ERR_STATE, "vo_landmarks: no calibration");
     const int K = c->set[0].sb.kp_cap;
     if (S > K || Kn > K) return fail(c, VO_ERR_CAPACITY, "vo_landmarks: more rows than max_keypoints");
-    BEGIN_CALL(c);
+    CallScope call(c); if (call.status) return call.status;
     c->have_features = false;
     std::vector<float> sp((size_t)S * 4 + 4), op((size_t)Kn * 4 + 4);
-    for (int j = 0; j < S; ++j) { sp[4 * j] = l_pos[2 * j]; sp[4 * j + 1] = l_pos[2 * j + 1]; sp[4 * j + 2] = r_pos[2 * j]; sp[4 * j + 3] = r_pos[2 * j + 1]; }
-    for (int k = 0; k < Kn; ++k) { op[4 * k] = old_l[2 * k]; op[4 * k + 1] = old_l[2 * k + 1]; op[4 * k + 2] = old_r[2 * k]; op[4 * k + 3] = old_r[2 * k + 1]; }
+    pack_quads(l_pos, r_pos, S, sp.data());
+    pack_quads(old_l, old_r, Kn, op.data());
     int cnt[2] = {S, Kn};
     HIPC(c, hipMemcpyAsync(c->set[0].gb.spos, sp.data(), sizeof(float) * 4 * S, hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->set[0].gb.oldpos, op.data(), sizeof(float) * 4 * Kn, hipMemcpyHostToDevice, c->stream));

@@ -57,9 +57,9 @@ struct GeomBuffers {
     // at sum_{g<f} min(lm_rows[g], kp_cap) + r
 };
 
-hipError_t geom_alloc(GeomBuffers& g, int max_frames, int kp_cap, int n_hyp);
-hipError_t geom_alloc_refine(GeomBuffers& g);     // g.refine, once
-void geom_free(GeomBuffers& g);
+// what these allocate belongs to the pool (the context's), which frees it
+hipError_t geom_alloc(DevPool& pool, GeomBuffers& g, int max_frames, int kp_cap, int n_hyp);
+hipError_t geom_alloc_refine(DevPool& pool, GeomBuffers& g);     // g.refine, once
 
 // Fill the 4 x max_frames tracking match jobs starting at jobs[first].
 // Frame f: cur images 2f (left) / 2f+1 (right); prev frame = f-1, frame 0's

@@ -9,6 +9,7 @@
 #include <string>
 #include "vo.h"
 #include "vo_spec.h"
+#include "dev_pool.h"
 
 #define VO_WAVE 64
 
@@ -33,7 +34,8 @@ struct Profiler {
     void reset_totals();
     ~Profiler();
 };
-extern Profiler* g_prof;
+// the profiler of the API call running on this thread (vo_api.hip: CallScope), else null
+extern thread_local Profiler* g_prof;
 
 #define VO_LAUNCH_NAMED(name, kernel, grid, block, shmem, stream, ...)                     \
     do {                                                                                   \
@@ -161,9 +163,9 @@ void build_pyramid_geometry(Pyramid& py, int rows, int cols, int n_img, const vo
 const char* sift_params_refusal(const vo_sift_params& p);
 // View of images [img0, img0 + n) of b: every per-image array shifted (image-major layout).
 SiftBuffers sift_view(const SiftBuffers& b, const Pyramid& py, int img0, int n);
-hipError_t sift_alloc(SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_cap);
-hipError_t sift_alloc_select(SiftBuffers& b);     // selectStrongest's key arrays (first vo_set_strongest(n > 0))
-void sift_free(SiftBuffers& b);
+// what the *_alloc functions allocate belongs to the pool (the context's), which frees it
+hipError_t sift_alloc(DevPool& pool, SiftBuffers& b, const Pyramid& py, int kp_cap, int cand_cap);
+hipError_t sift_alloc_select(DevPool& pool, SiftBuffers& b);     // selectStrongest's key arrays (first vo_set_strongest(n > 0))
 // Enqueue the whole detect+describe pipeline for n_img images (<= allocated).
 // d_py is a device copy of py.  strongest > 0: SIFTPoints.selectStrongest(points, strongest) between
 // detection and description (k_sel_keys / k_sel_rank; needs sift_alloc_select); 0 launches neither.
@@ -253,10 +255,9 @@ struct MatchBuffers {
                                      // columns in one chunk, match -10 % isolated, full path +1.3 %, r06_y)
 #endif
 
-hipError_t match_alloc(MatchBuffers& b, int max_jobs, int row_cap);
+hipError_t match_alloc(DevPool& pool, MatchBuffers& b, int max_jobs, int row_cap);
 // View whose job slot 0 is slot k0 of b (partial-result rows of jobs k0, k0+1, ...).
 MatchBuffers match_view(const MatchBuffers& b, int k0);
-void match_free(MatchBuffers& b);
 // d_jobs: device array of n_jobs jobs (prepared once per context); job k uses
 // partial-result slot k.
 // The index composition after tracking step `step` of find_remaining_points (VO.m:287-290,
@@ -283,8 +284,7 @@ struct MatchExBuffers {
     float* metric = nullptr;
     int* back = nullptr;
 };
-hipError_t match_ex_alloc(MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back);   // all or nothing
-void match_ex_free(MatchExBuffers& x);
+hipError_t match_ex_alloc(DevPool& pool, MatchExBuffers& x, const MatchBuffers& b, const MatchJob& job_back);   // all or nothing
 // d_job: the job (device); its partials use b's slot 0 as in match_launch(b, d_job, 1, ...)
 void match_launch_ex(const MatchBuffers& b, const MatchJob* d_job, const MatchExBuffers& x, const vo_match_params& p, int unique,
                      hipStream_t s);

@@ -10,7 +10,7 @@ using namespace vo;
 
 // the profiler hooks sift.hip's host code references (unused here)
 namespace vo {
-Profiler* g_prof = nullptr;
+thread_local Profiler* g_prof = nullptr;
 void Profiler::begin(const char*, hipStream_t) {}
 void Profiler::end(hipStream_t) {}
 void Profiler::collect() {}
