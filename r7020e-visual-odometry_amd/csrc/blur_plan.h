@@ -38,9 +38,37 @@ constexpr bool bs_hl(int r, int cpl, int tag) { return cpl == 4 && r <= kBlurDpp
 // output columns per strip
 constexpr int bs_sw(int r, int cpl, int tag) { return 64 * cpl - (bs_hl(r, cpl, tag) ? 2 * bs_rh(r, cpl) : 0); }
 
+// staged row length of the LDS row exchange: the strip's input columns and the halo each side
+constexpr int bs_rw(int r, int cpl) { return 64 * cpl + 2 * bs_rh(r, cpl); }
+
 // band height bound of the staged octave-0 base (kTagBaseU8): 8.7 KB of staged rows, so 16
 // one-wave workgroups per CU fit (128: 11.1 KB, 14).  k_blur_stream's LDS is sized for it.
 constexpr int kBaseMaxTH = 96;
+
+// The staged octave-0 base keeps the u8 source rows of its band in LDS (sift.hip, U8Src).
+// staged row length in dwords: the upsampled span of a wave (64 CPL columns + 2 RH halo) needs
+// (64 CPL + 2 RH) / 2 + 3 source bytes; + 3 for the row's misalignment, + 4 for the word pair
+constexpr int bs_u8_dw(int r, int cpl) { return ((64 * cpl + 2 * bs_rh(r, cpl)) / 2 + 3 + 3 + 4 + 3) / 4; }
+// staged rows: a band reads F + TH upsampled rows (F = 2r + E, E < P), i.e. at most half as many
+// source rows + 3 (the neighbour row of each end, rounding)
+constexpr int bs_u8_rows(int r) { return (2 * r + BS_P + kBaseMaxTH) / 2 + 4; }
+// The source rows [sr0, sr1] that the band of th output rows from row y0 of the R-row upsampled
+// plane stages, of an image of src_rows rows.  The band reads the upsampled rows y0 - r - E ..
+// y0 - r - E + F + th - 1, F the ring-fill steps; rows past either edge of the plane are
+// reflected (101) back into it, which can reach beyond the range the unreflected rows span; an
+// upsampled row y reads source rows y / 2 and its neighbour above or below.
+// tests/test_blur_census.py holds sr1 - sr0 + 1 <= bs_u8_rows(r) over every streamed BaseU8 plan.
+struct BsU8Rows { int sr0, sr1; };
+constexpr BsU8Rows bs_u8_stage_rows(int r, int R, int src_rows, int y0, int th)
+{
+    const int F = (2 * r + BS_P - 1) / BS_P * BS_P, E = F - 2 * r;
+    const int p_lo = y0 - r - E, p_hi = y0 - r - E + F + th - 1;
+    int ymin = p_lo < 0 ? 0 : p_lo, ymax = p_hi >= R ? R - 1 : p_hi;
+    if (p_lo < 0) { const int f = -p_lo < R - 1 ? -p_lo : R - 1; ymax = ymax > f ? ymax : f; }
+    if (p_hi >= R) { const int f = 2 * R - 2 - p_hi > 0 ? 2 * R - 2 - p_hi : 0; ymin = ymin < f ? ymin : f; }
+    const int a = (ymin >> 1) - 1, b = (ymax >> 1) + 1;
+    return BsU8Rows{a > 0 ? a : 0, b < src_rows - 1 ? b : src_rows - 1};
+}
 
 enum class BlurRole { Level, BaseFloat, BaseU8 };
 

@@ -360,8 +360,6 @@ __device__ __forceinline__ void vo_ss_prio()
 {
     if constexpr (VO_SS_SETPRIO > 0) __builtin_amdgcn_s_setprio(VO_SS_SETPRIO);
 }
-// staged row length (bs_rh, blur_plan.h: halo floats each side)
-__host__ __device__ constexpr int bs_rw(int r, int cpl) { return 64 * cpl + 2 * bs_rh(r, cpl); }
 // Row-window exchange of the streaming blur.  Each lane holds CPL consecutive columns of the
 // input row; the row pass needs r columns either side.  Halo-lane layout (bs_hl: 4-column lanes,
 // r <= kBlurDppMaxR): the wave covers 64*CPL input columns starting RH left of its output
@@ -415,12 +413,8 @@ __device__ __forceinline__ void vo_dpp_window(const vec_t& vm, float* w)
 // the P steps of 16-B stores issued before it -- the base kernel's stream of 1 GB of stores was
 // paced by its tiny u8 loads.  With the loads gone the loop never waits on vmcnt.
 struct U8Src { const uint8_t* p; int ld, rows, cols; };
-// staged row length in dwords: the upsampled span of a wave (64 CPL columns + 2 RH halo) needs
-// (64 CPL + 2 RH) / 2 + 3 source bytes; + 3 for the row's misalignment, + 4 for the word pair
-__host__ __device__ constexpr int bs_u8_dw(int r, int cpl) { return ((64 * cpl + 2 * bs_rh(r, cpl)) / 2 + 3 + 3 + 4 + 3) / 4; }
-// staged rows: a band reads F + TH upsampled rows (F = 2r + E, E < P), i.e. at most half as many
-// source rows + 3 (the neighbour row of each end, rounding)
-__host__ __device__ constexpr int bs_u8_rows(int r) { return (2 * r + BS_P + kBaseMaxTH) / 2 + 4; }
+// (the staged row length bs_u8_dw, the staged rows' bound bs_u8_rows and the rows a band stages,
+// bs_u8_stage_rows, are in blur_plan.h, where the CPU suite holds the bound)
 
 __device__ __forceinline__ vo_f4 up4_from_words(uint32_t a0, uint32_t a1, uint32_t sa, uint32_t b0, uint32_t b1, uint32_t sb)
 {
@@ -503,13 +497,9 @@ __device__ __forceinline__ void blur_stream_body(const float* __restrict__ sp, i
     int sr0 = 0;
     uint32_t delta = 0;
     if constexpr (UP) {
-        const int p_lo = y0 - RAD - E, p_hi = y0 - RAD - E + F + TH - 1;
-        int ymin = p_lo < 0 ? 0 : p_lo, ymax = p_hi >= R ? R - 1 : p_hi;
-        if (p_lo < 0) ymax = max(ymax, min(-p_lo, R - 1));
-        if (p_hi >= R) ymin = min(ymin, max(2 * R - 2 - p_hi, 0));
-        sr0 = max(0, (ymin >> 1) - 1);
-        const int sr1 = min(u8.rows - 1, (ymax >> 1) + 1);
-        const int total = (sr1 - sr0 + 1) * SWD;           // <= bs_u8_rows(RAD) * SWD (kBaseMaxTH)
+        const BsU8Rows sr = bs_u8_stage_rows(RAD, R, u8.rows, y0, TH);
+        sr0 = sr.sr0;
+        const int total = (sr.sr1 - sr0 + 1) * SWD;        // <= bs_u8_rows(RAD) * SWD (kBaseMaxTH)
         delta = (uint32_t)(reinterpret_cast<uintptr_t>(u8.p) & 3);
         // range = the image's last byte rounded up to its dword: a buffer load returns 0 for a
         // whole dword that crosses the range's end, which would drop the last row's final bytes;

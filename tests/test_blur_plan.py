@@ -7,17 +7,19 @@ condition for the octave-0 base from the u8 image.
 The header is compiled with the host compiler (oracle/blur_plan_eval.cpp).  It must agree with the
 transcription everywhere but in one region: there the old caller took the u8 base (tabled radius,
 R >= 64) while the old launcher would not stream it (R < TH), and launched the tiled kernel with a
-null source plane.  The plan does not stream there either, so the caller stages the float plane."""
-import ctypes as C
-from pathlib import Path
+null source plane.  The plan does not stream there either, so the caller stages the float plane.
 
+The transcriptions of sift.hip's small_plan and fork octave used below live in tests/blur_census.py,
+which lists every launch of a call from these plans.  tests/test_blur_census.py walks this file's
+sweep (ROWS, COLS, N_IMG) once more for the staged u8 base: every band of every streamed BaseU8
+plan stages at most bs_u8_rows(r) source rows, the size of k_blur_stream's LDS array."""
 import numpy as np
 import pytest
 
-LEVEL, BASE_FLOAT, BASE_U8 = 0, 1, 2
-FIELDS = ("streamed", "cpl", "tag", "th", "n_bands", "n_strips", "full_bands")
+import blur_census
+from blur_census import BASE_FLOAT, BASE_U8, BS_P, FIELDS, LEVEL, fork_octave
+
 TABLED = (5, 6, 8, 10, 13)
-BS_P = 4
 
 ROWS = np.arange(16, 4097, dtype=np.int64)
 COLS = np.array(sorted({16, 128, 129, 1400, 1401, 2484, 4096}
@@ -29,20 +31,11 @@ RADII = (4, 5, 6, 7, 8, 10, 13, 14)
 
 @pytest.fixture(scope="module")
 def plan_lib(oracle):
-    lib = C.CDLL(str(Path(oracle.__file__).resolve().parent / "build" / "libblur_plan.so"))
-    P = C.POINTER(C.c_int)
-    lib.blur_plan_sweep.argtypes = [C.c_int, C.c_int, C.c_int, P, C.c_int, P, C.c_int, P]
-    lib.blur_plan_sweep.restype = None
-    assert lib.blur_plan_bs_p() == BS_P
-    return lib
+    return blur_census.load_plan_lib(oracle)
 
 
 def header_plan(lib, role, r, n_img, rows=ROWS, cols=COLS):
-    R, Cc = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(cols, np.int32)
-    out = np.full((len(FIELDS), len(R), len(Cc)), -1, np.int32)
-    P = C.POINTER(C.c_int)
-    lib.blur_plan_sweep(role, r, n_img, R.ctypes.data_as(P), len(R), Cc.ctypes.data_as(P), len(Cc), out.ctypes.data_as(P))
-    return dict(zip(FIELDS, out))
+    return blur_census.header_plan(lib, role, r, n_img, rows, cols)
 
 
 def old_bs_sw(r, cpl, tag):
@@ -138,31 +131,6 @@ def test_the_hole_shape_of_the_issue(plan_lib):
         assert new["streamed"][0, 0] == streams, n_img
         flt = header_plan(plan_lib, BASE_FLOAT, 5, n_img, [64], [4096])
         assert flt["streamed"][0, 0] == streams                   # the staged plane's blur is tiled there too
-
-
-def small_octave(dims, maxr=13):
-    """small_plan of sift.hip: the first octave from which all fit k_small_pyr's LDS."""
-    o_small = len(dims)
-    for o in range(len(dims) - 1, 0, -1):
-        px = [r * c for r, c in dims[o:]]
-        cap = (max(px) + 3) & ~3
-        bcap = (max(px[1:], default=0) + 3) & ~3
-        rt = max(r for r, _ in dims[o:]) + 2 * maxr
-        ct = max(c for _, c in dims[o:]) + 2 * maxr
-        lds = 4 * (3 * cap + bcap) + 4 * (rt + ct)
-        if max(px) > 9216 or lds > 160 * 1024:
-            break
-        o_small = o
-    return o_small
-
-
-def fork_octave(dims, full_bands):
-    """sift_enqueue_pyramid: octave 1, moved down past every octave still at full bands."""
-    o_small = small_octave(dims)
-    o_fork = min(1, o_small - 1)
-    while o_fork + 1 < o_small and full_bands(*dims[o_fork + 1]):
-        o_fork += 1
-    return o_fork
 
 
 @pytest.mark.parametrize("rows,cols", [(375, 1242), (1080, 1920)])
