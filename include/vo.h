@@ -23,6 +23,8 @@
  *   vo_match               matchFeatures(F1, F2)  VO.m:87,283,293,311,323
  *   vo_match_ex /          [indexPairs, matchMetric] = matchFeatures(F1, F2,
  *   vo_match_f32_ex        'Unique', u, 'MatchThreshold', t, 'MaxRatio', r)
+ *   vo_match_radius /      [indexPairs, matchMetric] = matchFeaturesInRadius(F1, F2, points2,
+ *   vo_match_radius_f32    centerPoints, radius, ...): guided stereo / guided tracking
  *   vo_track               find_remaining_points  VO.m:280-334 (4 matches +
  *                          gathers), fused on device
  *   vo_triangulate         triangulate(x1, x2, P1, P2)  VO.m:113-116,
@@ -347,6 +349,41 @@ int vo_match_ex(vo_ctx* ctx, const uint8_t* F1, int n1, const uint8_t* F2, int n
                 uint32_t* pairs, float* metric, int capacity, int* n_pairs);
 int vo_match_f32_ex(vo_ctx* ctx, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
                     const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs);
+
+/* ---- matchFeaturesInRadius ------------------------------------------------ */
+/* [indexPairs, matchMetric] = matchFeaturesInRadius(features1, features2, points2, centerPoints,
+ * radius, ...): matchFeatures whose candidates of F1 row i are only the F2 rows j whose point lies
+ * in the closed circle of radius r_i about centre i -- guided stereo (a disparity range about the
+ * left point) and guided tracking (about last frame's position or its reprojection).  The ratio
+ * test runs over the candidates alone, so a repeated structure elsewhere in the image does not
+ * kill the match; the result is not a filter of vo_match_ex's.
+ *  - points2 [n2][2] and centers [n1][2] single (x, y); radius [n_radius], n_radius = 1 (one radius
+ *    for every row) or n1.
+ *  - scores: vo_match_ex's sv(i, j) = 2 - 2c, c = ((float)dot * inv|F1_i|) * inv|F2_j|.
+ *  - candidates of row i: C_i = { j : d2(i, j) <= r2_i }, dx = x2_j - cx_i, dy = y2_j - cy_i,
+ *    d2 = dx * dx + dy * dy, r2_i = r_i * r_i: float32 basic operations in this order, no fma
+ *    (vo_spec.h: vo_radius_gate).  A point exactly on the circle is a candidate; a radius whose
+ *    square overflows to +inf admits every column.
+ *  - forward step: best and second-best sv over C_i (a multiset; ties -> lowest j).  No candidate:
+ *    no pair.  One candidate: the second is +inf, the ratio 0, accepted iff best <= 0.04f *
+ *    MatchThreshold.  An exact duplicate pair inside the circle gives 0 / 0 and fails, as in vo_match.
+ *  - unique: back(j) = argmin_i sv(i, j) over the rows i with j in C_i (the same gate, bit for bit),
+ *    lowest i on ties; an accepted (i, j) is kept iff back(j) == i.
+ *  - pairs ascending in F1, 1-based; metric[k] = sv of pair k; opts as vo_match_ex (NULL: the
+ *    context's vo_match_params, unique 0).
+ * VO_ERR_ARG, before anything is enqueued and naming the first offending row: a non-finite
+ * coordinate, a radius that is not finite and > 0, n_radius other than 1 or n1, bad opts.
+ * n1 = 0 or n2 = 0 is legal (no pair).  VO_ERR_CAPACITY, VO_ERR_STATE while step batches are pending
+ * and *n_pairs beyond capacity as vo_match_ex.
+ * vo_match_radius_f32 takes the matrices as MATLAB holds them: col_major applies to the features
+ * (ld1 / ld2, as vo_match_f32) and to the two point matrices (element (i, k) at P[i + k * n]).
+ * Feature rows must hold integers in [0, 255]; any other single features -> VO_ERR_ARG. */
+int vo_match_radius(vo_ctx* ctx, const uint8_t* F1, int n1, const uint8_t* F2, int n2,
+                    const float* points2, const float* centers, const float* radius, int n_radius,
+                    const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs);
+int vo_match_radius_f32(vo_ctx* ctx, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                        const float* points2, const float* centers, const float* radius, int n_radius,
+                        const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity, int* n_pairs);
 
 /* find_remaining_points (VO.m:280-334) on device.  old = previous frame's
  * stereo-aligned set (n_old rows, left/right row-aligned); cur = current

@@ -757,4 +757,43 @@ VO_HD void vo_refine_update(vo_refine_state* s, const double* sums, int behind, 
     }
 }
 
+/* ------------------------------------------------------------------------ */
+/* matchFeaturesInRadius: the spatial gate of one (F1 row, F2 column) pair    */
+/* and its lower bound over a box of positions.  (x2, y2) is the column's     */
+/* point, (cx, cy) the row's centre, r2 = r * r the row's squared radius.     */
+/* f32 basic ops in the order written, no contraction: two subtractions, two  */
+/* multiplies, one add.  The circle is closed (d2 == r2 is inside); r2 = +inf */
+/* (a radius whose square overflows) admits every column.                     */
+/* ------------------------------------------------------------------------ */
+VO_HD float vo_radius_d2(float x2, float y2, float cx, float cy)
+{
+    float dx = x2 - cx;
+    float dy = y2 - cy;
+    float sx = dx * dx;
+    float sy = dy * dy;
+    return sx + sy;
+}
+
+VO_HD int vo_radius_gate(float x2, float y2, float cx, float cy, float r2) { return vo_radius_d2(x2, y2, cx, cy) <= r2; }
+
+/* Lower bound of vo_radius_d2 between the point (px, py) and every point q   */
+/* of the box [xmin, xmax] x [ymin, ymax], whichever of the two is the centre */
+/* (the forward pass bounds a tile of F2 points against the row's centre, the */
+/* backward pass a tile of centres against the row's point).  It holds in     */
+/* float32, not only in real arithmetic: for px < xmin <= qx, round-to-       */
+/* nearest subtraction is monotone, so fl(xmin - px) <= fl(qx - px); for      */
+/* px > xmax >= qx likewise fl(px - xmax) <= fl(px - qx); fl(a - b) =         */
+/* -fl(b - a), so either is <= |dx| as vo_radius_d2 computes it whichever     */
+/* operand comes first; inside the interval the bound is 0.  Multiply and add */
+/* are monotone on non-negatives, so bx * bx + by * by <= dx * dx + dy * dy.  */
+/* ------------------------------------------------------------------------ */
+VO_HD float vo_radius_box_lb(float xmin, float xmax, float ymin, float ymax, float px, float py)
+{
+    float bx = fmaxf(fmaxf(xmin - px, px - xmax), 0.0f);
+    float by = fmaxf(fmaxf(ymin - py, py - ymax), 0.0f);
+    float sx = bx * bx;
+    float sy = by * by;
+    return sx + sy;
+}
+
 #endif /* VO_SPEC_H */

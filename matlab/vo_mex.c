@@ -3,7 +3,7 @@
  *
  * VO.m calls Computer Vision Toolbox functions; MATLAB resolves a name to the first match on
  * its path, so the `.m` files next to this gateway (undistortImage.m, detectSIFTFeatures.m,
- * extractFeatures.m, matchFeatures.m, triangulate.m, estworldpose.m, bundleAdjustmentMotion.m,
+ * extractFeatures.m, matchFeatures.m, matchFeaturesInRadius.m, triangulate.m, estworldpose.m, bundleAdjustmentMotion.m,
  * CreateLandmarksFromFeatures.m) shadow the
  * toolbox and the reference's own CreateLandmarksFromFeatures.m without editing VO.m.  Each
  * calls this one gateway with a command string:
@@ -29,6 +29,9 @@
  *        matchFeatures(F1, F2)                                   VO.m:87,283,293,311,323
  *        and its options 'Unique', 'MatchThreshold', 'MaxRatio' (names case-insensitive; 'Method',
  *        'Metric', 'Prenormalized' only at their defaults; anything else: vo:matchFeatures:options)
+ *   [indexPairs, matchMetric] = vo_mex('matchradius', F1, F2, points2, centerPoints, radius, name, value, ...)
+ *        matchFeaturesInRadius(F1, F2, points2, centerPoints, radius): guided stereo / tracking; all
+ *        five single; matchFeatures' options (vo:matchFeaturesInRadius:options)
  *   [X, reprojectionErrors, validIndex] = vo_mex('triangulate', x1, x2, P1, P2)
  *        triangulate                              VO.m:113-116, CreateLandmarksFromFeatures.m:7
  *        one output: vo_triangulate; two or three: vo_triangulate_ex (N x 1 single mean reprojection
@@ -316,10 +319,14 @@ static void cmd_describe(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prh
  * vo:matchFeatures:options. */
 extern __typeof__(vo_match_f32_ex) vo_match_f32_ex __attribute__((weak));
 
+/* the function whose options match_options is parsing: its name, and the identifier of its errors */
+static const char* g_opt_fn = "matchFeatures";
+static const char* g_opt_id = "vo:matchFeatures:options";
+
 static void bad_option(const char* why, const char* name)
 {
-    mexErrMsgIdAndTxt("vo:matchFeatures:options", "matchFeatures: %s '%s' (libvo implements Unique, MatchThreshold in (0, 25], "
-                      "MaxRatio in (0, 1] and the defaults of Method, Metric and Prenormalized)", why, name);
+    mexErrMsgIdAndTxt(g_opt_id, "%s: %s '%s' (libvo implements Unique, MatchThreshold in (0, 25], "
+                      "MaxRatio in (0, 1] and the defaults of Method, Metric and Prenormalized)", g_opt_fn, why, name);
 }
 
 static int same_nocase(const char* a, const char* b)
@@ -346,15 +353,16 @@ static int scalar_value(const mxArray* a, int any_numeric, double* v)
     }
 }
 
-/* matchFeatures' name-value pairs prhs[3..]: 1 if one of Unique / MatchThreshold / MaxRatio is
- * given (then *o holds them over the defaults).  Method, Metric and Prenormalized are accepted
- * only where they restate the default; anything else raises vo:matchFeatures:options. */
-static int match_options(int nrhs, const mxArray* prhs[], vo_match_opts* o)
+/* matchFeatures' name-value pairs prhs[first..] (matchFeaturesInRadius': the same rules): 1 if one
+ * of Unique / MatchThreshold / MaxRatio is given (then *o holds them over the defaults).  Method,
+ * Metric and Prenormalized are accepted only where they restate the default; anything else raises
+ * g_opt_id (vo:matchFeatures:options, vo:matchFeaturesInRadius:options). */
+static int match_options(int first, int nrhs, const mxArray* prhs[], vo_match_opts* o)
 {
     int given = 0;
     o->match_threshold = 1.0f; o->max_ratio = 0.6f; o->unique = 0; o->reserved = 0;
-    if ((nrhs - 3) % 2) bad_option("a name without a value after", "features2");
-    for (int k = 3; k < nrhs; k += 2) {
+    if ((nrhs - first) % 2) bad_option("a name without a value after", first == 3 ? "features2" : "radius");
+    for (int k = first; k < nrhs; k += 2) {
         char name[32], text[32];
         double v = 0.0;
         const mxArray* val = prhs[k + 1];
@@ -491,7 +499,9 @@ static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]
     for (int k = 1; k <= 2; ++k)
         if (mxGetM(prhs[k]) > 0) need_real(prhs[k], mxSINGLE_CLASS, -1, VO_DESC_LEN, k == 1 ? "features1" : "features2");
     vo_match_opts opts;
-    const int ex = match_options(nrhs, prhs, &opts) || nlhs > 1;
+    g_opt_fn = "matchFeatures";
+    g_opt_id = "vo:matchFeatures:options";
+    const int ex = match_options(3, nrhs, prhs, &opts) || nlhs > 1;
     if (ex && !vo_match_f32_ex)
         mexErrMsgIdAndTxt("vo:matchFeatures:options", "this libvo has no vo_match_f32_ex: matchFeatures(F1, F2) with the default "
                           "options and one output only");
@@ -505,6 +515,54 @@ static void cmd_match(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]
     const float* f2 = n2 ? mxGetSingles(prhs[2]) : NULL;
     if (ex) check(vo_match_f32_ex(g_ctx, f1, n1, n1 ? n1 : 1, f2, n2, n2 ? n2 : 1, 1, &opts, pr, mt, n1 + 1, &P));
     else check(vo_match_f32(g_ctx, f1, n1, n1 ? n1 : 1, f2, n2, n2 ? n2 : 1, 1, pr, n1 + 1, &P));
+    plhs[0] = mxCreateNumericMatrix(P, 2, mxUINT32_CLASS, mxREAL);
+    uint32_t* o = mxGetUint32s(plhs[0]);
+    for (int i = 0; i < P; ++i) { o[i] = pr[2 * i]; o[(size_t)P + i] = pr[2 * i + 1]; }
+    if (nlhs > 1) {
+        plhs[1] = mxCreateNumericMatrix(P, 1, mxSINGLE_CLASS, mxREAL);      /* matchMetric */
+        memcpy(mxGetSingles(plhs[1]), mt, sizeof(float) * (size_t)P);
+    }
+    mxFree(pr);
+    mxFree(mt);
+}
+
+/* vo_match_radius_f32 through a weak reference: with a libvo that lacks it 'matchradius' raises
+ * vo:matchFeaturesInRadius:unavailable and every other command runs as before */
+extern __typeof__(vo_match_radius_f32) vo_match_radius_f32 __attribute__((weak));
+
+/* [indexPairs, matchMetric] = vo_mex('matchradius', F1, F2, points2, centerPoints, radius, name, value, ...)
+ * matchFeaturesInRadius: F1 n1 x 128 and F2 n2 x 128 single as extractFeatures returned them,
+ * points2 n2 x 2 and centerPoints n1 x 2 single [x y], radius single, a scalar or n1 values -- all
+ * handed over as they lie (col_major = 1).  Shapes are checked here (vo:badArgument), the values by
+ * libvo; the options are matchFeatures' (vo:matchFeaturesInRadius:options). */
+static void cmd_matchradius(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs < 6) need_args(nrhs, 6, "matchradius");
+    if (nlhs > 2) mexErrMsgIdAndTxt("vo:matchFeaturesInRadius:options", "matchFeaturesInRadius returns at most [indexPairs, matchMetric]");
+    for (int k = 1; k <= 2; ++k)
+        if (mxGetM(prhs[k]) > 0) need_real(prhs[k], mxSINGLE_CLASS, -1, VO_DESC_LEN, k == 1 ? "features1" : "features2");
+    const int n1 = (int)mxGetM(prhs[1]), n2 = (int)mxGetM(prhs[2]);
+    need_real(prhs[3], mxSINGLE_CLASS, n2, 2, "points2");
+    need_real(prhs[4], mxSINGLE_CLASS, n1, 2, "centerPoints");
+    need_real(prhs[5], mxSINGLE_CLASS, -1, -1, "radius");
+    const int nr = (int)(mxGetM(prhs[5]) * mxGetN(prhs[5]));
+    if ((mxGetM(prhs[5]) != 1 && mxGetN(prhs[5]) != 1) || (nr != 1 && nr != n1))
+        mexErrMsgIdAndTxt("vo:badArgument", "radius must be a scalar or hold one value per row of features1");
+    vo_match_opts opts;
+    g_opt_fn = "matchFeaturesInRadius";
+    g_opt_id = "vo:matchFeaturesInRadius:options";
+    match_options(6, nrhs, prhs, &opts);
+    if (!vo_match_radius_f32)
+        mexErrMsgIdAndTxt("vo:matchFeaturesInRadius:unavailable", "this libvo has no vo_match_radius_f32: match with matchFeatures "
+                          "and filter by distance, or link a newer libvo");
+    need_ctx(0, 0);
+    int P = 0;
+    uint32_t* pr = (uint32_t*)mxMalloc(sizeof(uint32_t) * 2 * ((size_t)n1 + 1));
+    float* mt = (float*)mxMalloc(sizeof(float) * ((size_t)n1 + 1));
+    const int rc = vo_match_radius_f32(g_ctx, n1 ? mxGetSingles(prhs[1]) : NULL, n1, n1 ? n1 : 1, n2 ? mxGetSingles(prhs[2]) : NULL, n2,
+                                       n2 ? n2 : 1, 1, n2 ? mxGetSingles(prhs[3]) : NULL, n1 ? mxGetSingles(prhs[4]) : NULL,
+                                       mxGetSingles(prhs[5]), nr, &opts, pr, mt, n1 + 1, &P);
+    if (rc != VO_OK) { mxFree(pr); mxFree(mt); check(rc); }
     plhs[0] = mxCreateNumericMatrix(P, 2, mxUINT32_CLASS, mxREAL);
     uint32_t* o = mxGetUint32s(plhs[0]);
     for (int i = 0; i < P; ++i) { o[i] = pr[2 * i]; o[(size_t)P + i] = pr[2 * i + 1]; }
@@ -738,6 +796,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "distortion")) cmd_distortion(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "strongest")) cmd_strongest(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "match")) cmd_match(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "matchradius")) cmd_matchradius(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "triangulate")) cmd_triangulate(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "refinepose")) cmd_refinepose(nlhs, plhs, nrhs, prhs);

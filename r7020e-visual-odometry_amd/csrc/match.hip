@@ -99,6 +99,9 @@ __device__ __forceinline__ v4i load_frag(const uint8_t* row, int off)
 #define VO_MP_BLOCKS 5            // workgroups per CU the register budget of k_match_partial<1> is sized for (92 VGPRs)
 #endif
 #define MP_NBUF 2
+#ifndef VO_RADIUS_PREREJECT
+#define VO_RADIUS_PREREJECT 1     // k_match_radius: skip a tile whose box lies outside every row's circle (0: the A/B build of DESIGN.md 9n)
+#endif
 // NB: 32-row F1 sub-blocks per wave (MP_ROWS * NB rows per workgroup); NB = 2 runs two
 // independent MFMA chains per tile on the same F2 fragments (half the LDS reads per MFMA)
 // SWAP: the job's row side is the spec's F2 and its column side the spec's F1 (the backward pass
@@ -512,6 +515,235 @@ void match_launch_ex(const MatchBuffers& b, const MatchJob* d_job, const MatchEx
     if (unique)
         VO_LAUNCH_NAMED("k_match_partial_back", (k_match_partial<1, true>), dim3(VO_STEREO_GRID), dim3(256), 0, s,
                         (const MatchJob*)x.job_back, 1, x.partial_back, b.row_cap, b.n_chunks);
+    VO_LAUNCH(k_match_finish_unique, dim3(1), dim3(256), 0, s, d_job, (const MatchTop2*)b.partial,
+              (const MatchTop2*)x.partial_back, b.row_cap, b.n_chunks, p.match_threshold * 0.04f, p.max_ratio, unique, x.metric);
+}
+
+// ---------------------------------------------------------------------------
+// matchFeaturesInRadius (vo_match_radius): matchFeatures whose candidates of F1 row i are the F2
+// columns j with vo_radius_gate(x2_j, y2_j, cx_i, cy_i, r_i * r_i) ("In radius").
+// ---------------------------------------------------------------------------
+// One wave per aligned 32-row tile of either side (blocks [0, tiles1): F1, the rest: F2): lane l < 32
+// writes row 32 tile + l's geometry -- F1: {cx, cy, r2 = r * r, 0}, F2: {x, y, 0, 0} -- and the
+// half-wave reduces the tile's bounding box and, on the F1 side, its largest r2.  P holds the
+// points as the caller does: row-major [n][2], or col_major: point (i, k) at P[i + k * n].
+__global__ __launch_bounds__(64) void k_radius_meta(const float* __restrict__ centers, const float* __restrict__ radius, int n_radius,
+                                                    int n1, const float* __restrict__ pts2, int n2, int col_major,
+                                                    vo_geo4* __restrict__ geo1, vo_geo4* __restrict__ box1,
+                                                    vo_geo4* __restrict__ geo2, vo_geo4* __restrict__ box2)
+{
+    const int tiles1 = (n1 + 31) >> 5, lane = threadIdx.x;
+    const bool first = (int)blockIdx.x < tiles1;
+    const int tile = first ? blockIdx.x : blockIdx.x - tiles1, n = first ? n1 : n2;
+    const float* P = first ? centers : pts2;
+    const int i = 32 * tile + lane;
+    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, rmax = 0.0f;
+    if (lane < 32 && i < n) {
+        const float x = col_major ? P[i] : P[2 * (size_t)i], y = col_major ? P[(size_t)n + i] : P[2 * (size_t)i + 1];
+        float r2 = 0.0f;
+        if (first) { const float r = radius[n_radius == 1 ? 0 : i]; r2 = r * r; }
+        (first ? geo1 : geo2)[i] = vo_geo4{x, y, r2, 0.0f};
+        xmin = xmax = x; ymin = ymax = y; rmax = r2;
+    }
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+        xmin = fminf(xmin, __shfl_xor(xmin, off)); xmax = fmaxf(xmax, __shfl_xor(xmax, off));
+        ymin = fminf(ymin, __shfl_xor(ymin, off)); ymax = fmaxf(ymax, __shfl_xor(ymax, off));
+        rmax = fmaxf(rmax, __shfl_xor(rmax, off));
+    }
+    if (lane == 0) {
+        vo_geo4* box = (first ? box1 : box2) + 2 * (size_t)tile;
+        box[0] = vo_geo4{xmin, xmax, ymin, ymax};
+        box[1] = vo_geo4{rmax, 0.0f, 0.0f, 0.0f};
+    }
+}
+
+// One side of an in-radius pass: n descriptor rows, their metadata, geometry and tile boxes
+struct RadiusSide {
+    const uint8_t* d; const DescMeta* m; const vo_geo4* geo; const vo_geo4* box;
+    int n, pad;
+};
+
+// k_match_partial<1, SWAP>'s tile scheme for a single job whose sizes the host knows: the same MFMA
+// on (a - 128) x (b - 128) with the row-sum correction, the transposed tile (lane l holds row
+// l & 31 of side R and 16 of the tile's columns of side Cs), the double-buffered column tile in LDS
+// and the same MatchTop2 partials.  The tile's LDS rows also carry the columns' geometry and the
+// tile's box.  !SWAP: R = F1 (centre and r2 per row), Cs = F2 (a point per column); SWAP (the
+// backward pass of Unique): R = F2, Cs = F1.
+// The gate: in the epilogue the lane sets cv[reg] = -INF for the columns outside the circle,
+// evaluating vo_radius_gate on the spec's operands (the column's / row's point, the row's / column's
+// centre and r2) in either pass, so the two passes agree bit for bit on who is a candidate.  The
+// pre-test and the top-2 update are k_match_partial's: a row without a candidate ends with idx -1,
+// one with a single candidate with second = -INF, which k_match_finish_unique turns into "no pair"
+// and "ratio 0".
+// Tile pre-reject: the wave skips the tile's MFMAs and epilogue when no live lane's
+// vo_radius_box_lb against the tile's box is <= r2 (its own; SWAP: the tile's largest).  The bound
+// is <= vo_radius_d2 of every column of the tile in float32 (the argument is vo_spec.h's), so a
+// skipped tile holds no candidate of any of the wave's rows; the per-element gate is exact without
+// it.  The loads, LDS stores and barriers stay unconditional.
+template <bool SWAP>
+__global__ __launch_bounds__(256, 4) void k_match_radius(RadiusSide R, RadiusSide Cs, MatchTop2* __restrict__ partial, int row_cap)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t bt[MP_NBUF][32 * MP_LDS_ROW];
+    __shared__ __attribute__((aligned(16))) int bck[MP_NBUF][32];
+    __shared__ __attribute__((aligned(16))) float binb[MP_NBUF][32];
+    __shared__ __attribute__((aligned(16))) float bgx[MP_NBUF][32], bgy[MP_NBUF][32], bgr[MP_NBUF][32];
+    __shared__ __attribute__((aligned(16))) float bbox[MP_NBUF][8];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, l31 = lane & 31;
+    const int lr = tid >> 3, lseg = tid & 7;              // loader: row lr of the tile, bytes [16 lseg, +16)
+    const int n1 = R.n, n2 = Cs.n;                        // rows and columns of this pass
+    const int nch = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
+    const int total = ((n1 + MP_ROWS - 1) / MP_ROWS) * nch;
+    for (int t = blockIdx.x; t < total; t += gridDim.x) {       // workgroup-uniform
+        const int blk = t / nch, chunk = t - blk * nch;
+        const int i0 = blk * MP_ROWS + 32 * wave, j0 = chunk * VO_MATCH_CHUNK;
+        const int j1 = min(j0 + VO_MATCH_CHUNK, n2);
+        const int ia = i0 + l31;
+        const bool live = ia < n1;
+        v4i a[4];
+        int rk1 = -2097152;
+        float ina1 = 0.0f;
+        vo_geo4 rg = vo_geo4{0.0f, 0.0f, -1.0f, 0.0f};          // a dead lane's r2 admits nothing
+        if (live) {
+            const uint8_t* row = R.d + (size_t)ia * VO_DESC_LEN;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) a[kk] = load_frag(row, 32 * kk + 16 * h);
+            const DescMeta m = gld_meta(R.m + ia);
+            rk1 = 128 * m.sum - 2097152;
+            ina1 = m.inv_norm;
+            rg = gld(R.geo + ia);
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) a[kk] = (v4i){0, 0, 0, 0};
+        }
+        float best1 = -INFINITY, second1 = -INFINITY;
+        int bidx1 = -1;
+        // loader: column jt + lr (clamped into the chunk; the epilogue masks columns >= j1); thread
+        // lseg 0 of a row brings its metadata, lseg 1 its geometry, and two threads the tile's box
+        v4i gv;
+        DescMeta gm;
+        vo_geo4 gg = vo_geo4{0.0f, 0.0f, 0.0f, 0.0f}, gb = vo_geo4{0.0f, 0.0f, 0.0f, 0.0f};
+        auto gload = [&](int jt) {
+            const int jc = min(jt + lr, j1 - 1);
+            gv = gld(reinterpret_cast<const v4i*>(Cs.d + (size_t)jc * VO_DESC_LEN + 16 * lseg));
+            if (lseg == 0) gm = gld_meta(Cs.m + jc);
+            if (lseg == 1) gg = gld(Cs.geo + jc);
+            if (lseg == 2 && lr < 2) gb = gld(Cs.box + 2 * (size_t)(jt >> 5) + lr);
+        };
+        auto lstore = [&](int buf) {                       // stored as b - 128 (the MFMA operand)
+            *reinterpret_cast<v4i*>(&bt[buf][lr * MP_LDS_ROW + 16 * lseg]) =
+                gv ^ (v4i){(int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080};
+            if (lseg == 0) { bck[buf][lr] = 128 * gm.sum; binb[buf][lr] = gm.inv_norm; }
+            if (lseg == 1) { bgx[buf][lr] = gg.x; bgy[buf][lr] = gg.y; bgr[buf][lr] = gg.z; }
+            if (lseg == 2 && lr < 2) *reinterpret_cast<vo_geo4*>(&bbox[buf][4 * lr]) = gb;
+        };
+        auto tile = [&](int bi, int jt) {
+            // D = column tile (A operand, from LDS) x rows (B operand, registers): lane l holds row
+            // i0 + l31 and columns jt + (reg & 3) + 8 (reg >> 2) + 4 h, ascending in reg
+            v4i b[4];
+            const uint8_t* brow = &bt[bi][l31 * MP_LDS_ROW + 16 * h];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) b[kk] = *reinterpret_cast<const v4i*>(brow + 32 * kk);
+            v16i acc = (v16i){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(b[kk], a[kk], acc, 0, 0, 0);
+            float cv[16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const v4i ck4 = *reinterpret_cast<const v4i*>(&bck[bi][8 * q + 4 * h]);
+                const vo_f4 ib4 = *reinterpret_cast<const vo_f4*>(&binb[bi][8 * q + 4 * h]);
+                const vo_f4 gx4 = *reinterpret_cast<const vo_f4*>(&bgx[bi][8 * q + 4 * h]);
+                const vo_f4 gy4 = *reinterpret_cast<const vo_f4*>(&bgy[bi][8 * q + 4 * h]);
+                const vo_f4 gr4 = *reinterpret_cast<const vo_f4*>(&bgr[bi][8 * q + 4 * h]);
+#pragma unroll
+                for (int i = 0; i < 4; i += 2) {
+                    // c = ((float)dot * inv|F1|) * inv|F2| in the spec's operand order, as k_match_partial
+                    const vo_f2 fp = vo_f2{(float)(acc[4 * q + i] + rk1 + ck4[i]), (float)(acc[4 * q + i + 1] + rk1 + ck4[i + 1])};
+                    const vo_f2 cp = SWAP ? (fp * vo_f2{ib4[i], ib4[i + 1]}) * vo_f2{ina1, ina1}
+                                          : (fp * vo_f2{ina1, ina1}) * vo_f2{ib4[i], ib4[i + 1]};
+                    cv[4 * q + i] = cp.x;
+                    cv[4 * q + i + 1] = cp.y;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    // the gate, on the spec's operands in either pass: (F2 point, F1 centre, F1 r2)
+                    const bool in = SWAP ? vo_radius_gate(rg.x, rg.y, gx4[i], gy4[i], gr4[i])
+                                         : vo_radius_gate(gx4[i], gy4[i], rg.x, rg.y, rg.z);
+                    cv[4 * q + i] = in ? cv[4 * q + i] : -INFINITY;
+                }
+            }
+            if (jt + 32 > j1) {                            // wave-uniform: the ragged last tile
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg)
+                    cv[reg] = jt + (reg & 3) + 8 * (reg >> 2) + 4 * h < j1 ? cv[reg] : -INFINITY;
+            }
+            // k_match_partial's exact pre-test and in-order top-2 update
+            float m = fmaxf(fmaxf(fmaxf(cv[0], cv[1]), fmaxf(cv[2], cv[3])), fmaxf(fmaxf(cv[4], cv[5]), fmaxf(cv[6], cv[7])));
+            m = fmaxf(m, fmaxf(fmaxf(fmaxf(cv[8], cv[9]), fmaxf(cv[10], cv[11])), fmaxf(fmaxf(cv[12], cv[13]), fmaxf(cv[14], cv[15]))));
+            if (__builtin_amdgcn_ballot_w64(m > second1)) {
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const float c = cv[reg];
+                    const bool g1 = c > best1, g2 = c > second1;
+                    second1 = g1 ? best1 : (g2 ? c : second1);
+                    best1 = g1 ? c : best1;
+                    bidx1 = g1 ? jt + (reg & 3) + 8 * (reg >> 2) + 4 * h : bidx1;
+                }
+            }
+        };
+        gload(j0);
+        __syncthreads();                                   // previous task's readers are done with the LDS tile
+        lstore(0);
+        if (j0 + 32 < j1) gload(j0 + 32);
+        int buf = 0;
+        for (int jt = j0; jt < j1; jt += 32, buf ^= 1) {
+            __syncthreads();                               // tile jt visible; tile jt-32's buffer free
+            if (jt + 32 < j1) {
+                lstore(buf ^ 1);                           // tile jt+32 (loaded one iteration ago)
+                if (jt + 64 < j1) gload(jt + 64);
+            }
+#if VO_RADIUS_PREREJECT
+            const vo_f4 bx = *reinterpret_cast<const vo_f4*>(&bbox[buf][0]);
+            const float lb = vo_radius_box_lb(bx.x, bx.y, bx.z, bx.w, rg.x, rg.y);
+            if (__builtin_amdgcn_ballot_w64(live && lb <= (SWAP ? bbox[buf][4] : rg.z))) tile(buf, jt);
+#else
+            tile(buf, jt);
+#endif
+        }
+        const float ob = __shfl_xor(best1, 32), os = __shfl_xor(second1, 32);
+        const int oi = __shfl_xor(bidx1, 32);
+        top2c_merge(best1, bidx1, second1, ob, oi, os);
+        if (h == 0 && live) {
+            MatchTop2 mt;
+            mt.best = best1; mt.idx = bidx1; mt.second = second1; mt.pad = 0;
+            partial[(size_t)chunk * row_cap + ia] = mt;
+        }
+    }
+}
+
+hipError_t match_radius_alloc(DevPool& pool, MatchRadiusBuffers& r, const MatchBuffers& b)
+{
+    const size_t R = b.row_cap, T = 2 * ((R + 31) / 32);
+    return (hipError_t)pool.group({DevPool::req(r.pts2, 2 * R), DevPool::req(r.centers, 2 * R), DevPool::req(r.radius, R),
+                                   DevPool::req(r.geo1, R), DevPool::req(r.geo2, R), DevPool::req(r.box1, T),
+                                   DevPool::req(r.box2, T)});
+}
+
+void match_radius_launch(const MatchBuffers& b, const MatchJob* d_job, const MatchExBuffers& x, const MatchRadiusBuffers& r,
+                         const uint8_t* d1, const DescMeta* m1, int n1, const uint8_t* d2, const DescMeta* m2, int n2,
+                         int col_major, int n_radius, const vo_match_params& p, int unique, hipStream_t s)
+{
+    if (n1 <= 0 || n2 <= 0) return;
+    VO_LAUNCH(k_radius_meta, dim3((n1 + 31) / 32 + (n2 + 31) / 32), dim3(64), 0, s, (const float*)r.centers,
+              (const float*)r.radius, n_radius, n1, (const float*)r.pts2, n2, col_major, r.geo1, r.box1, r.geo2, r.box2);
+    const RadiusSide S1{d1, m1, r.geo1, r.box1, n1, 0}, S2{d2, m2, r.geo2, r.box2, n2, 0};
+    const int nc1 = (n1 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK, nc2 = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
+    const int fwd = ((n1 + MP_ROWS - 1) / MP_ROWS) * nc2, back = ((n2 + MP_ROWS - 1) / MP_ROWS) * nc1;
+    VO_LAUNCH_NAMED("k_match_radius", k_match_radius<false>, dim3(std::min(fwd, VO_STEREO_GRID)), dim3(256), 0, s, S1, S2,
+                    b.partial, b.row_cap);
+    if (unique)
+        VO_LAUNCH_NAMED("k_match_radius_back", k_match_radius<true>, dim3(std::min(back, VO_STEREO_GRID)), dim3(256), 0, s, S2, S1,
+                        x.partial_back, b.row_cap);
     VO_LAUNCH(k_match_finish_unique, dim3(1), dim3(256), 0, s, d_job, (const MatchTop2*)b.partial,
               (const MatchTop2*)x.partial_back, b.row_cap, b.n_chunks, p.match_threshold * 0.04f, p.max_ratio, unique, x.metric);
 }

@@ -161,6 +161,7 @@ struct vo_ctx {
     float* d_fbt = nullptr;
     int* d_fres = nullptr;
     MatchExBuffers mx;               // vo_match_ex / vo_match_f32_ex (allocated on first use)
+    MatchRadiusBuffers mr;           // vo_match_radius / vo_match_radius_f32 (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
@@ -1019,6 +1020,97 @@ int vo_match_f32_ex(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2
     if (n_pairs) *n_pairs = P;
     if (P > capacity) return fail(c, VO_ERR_CAPACITY, "vo_match_f32_ex: %d pairs exceed capacity %d", P, capacity);
     return VO_OK;
+}
+
+// ---- matchFeaturesInRadius -----------------------------------------------------------------
+// the in-radius entries' own arguments, checked before anything is enqueued: n_radius 1 or n1,
+// finite coordinates, finite radii > 0 (the first offending index is named)
+static int radius_args_check(vo_ctx* c, const char* who, int n1, int n2, const float* points2, const float* centers,
+                             const float* radius, int n_radius, int col_major)
+{
+    if ((n2 && !points2) || (n1 && !centers) || !radius) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    if (n_radius != 1 && n_radius != n1) return fail(c, VO_ERR_ARG, "%s: n_radius %d is neither 1 nor n1 = %d", who, n_radius, n1);
+    const float* P[2] = {points2, centers};
+    const int n[2] = {n2, n1};
+    for (int s = 0; s < 2; ++s)
+        for (int i = 0; i < n[s]; ++i) {
+            const float x = col_major ? P[s][i] : P[s][2 * (size_t)i], y = col_major ? P[s][(size_t)n[s] + i] : P[s][2 * (size_t)i + 1];
+            if (!std::isfinite(x) || !std::isfinite(y))
+                return fail(c, VO_ERR_ARG, "%s: %s row %d (%g, %g) is not finite", who, s ? "centers" : "points2", i, (double)x, (double)y);
+        }
+    for (int k = 0; k < n_radius; ++k)
+        if (!(std::isfinite(radius[k]) && radius[k] > 0.0f))
+            return fail(c, VO_ERR_ARG, "%s: radius %d (%g) is not finite and > 0", who, k, (double)radius[k]);
+    return VO_OK;
+}
+
+// the in-radius match of the two staged descriptor sets, inside a call (as match_staged)
+static int match_radius_staged(vo_ctx* c, int n1, int n2, const float* points2, const float* centers, const float* radius,
+                               int n_radius, int col_major, const vo_match_params& p, int unique, uint32_t* pairs, float* metric,
+                               int capacity, int* n_pairs, const char* who)
+{
+    if (n_pairs) *n_pairs = 0;
+    if (n1 == 0 || n2 == 0) return VO_OK;                 // no pair; nothing is launched
+    int rc = match_ex_buffers(c, who);
+    if (rc) return rc;
+    if (!c->mr.pts2) {
+        const hipError_t e = match_radius_alloc(c->pool, c->mr, c->set[0].mb);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    int nn[2] = {n1, n2};
+    HIPC(c, hipMemcpyAsync(c->d_fn, nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->mr.pts2, points2, sizeof(float) * 2 * n2, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->mr.centers, centers, sizeof(float) * 2 * n1, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->mr.radius, radius, sizeof(float) * n_radius, hipMemcpyHostToDevice, c->stream));
+    desc_meta_launch(c->d_fd[0], c->d_fm[0], n1, c->stream);
+    desc_meta_launch(c->d_fd[1], c->d_fm[1], n2, c->stream);
+    match_radius_launch(c->set[0].mb, c->d_job_single, c->mx, c->mr, c->d_fd[0], c->d_fm[0], n1, c->d_fd[1], c->d_fm[1], n2,
+                        col_major, n_radius, p, unique, c->stream);
+    int P = 0;
+    HIPC(c, hipMemcpyAsync(&P, c->d_mn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    rc = finish(c);
+    if (rc) return rc;
+    if (n_pairs) *n_pairs = P;
+    const int m = std::min(P, capacity);
+    if ((rc = read_pairs(c, c->d_mi, c->d_mj, m, pairs))) return rc;
+    if (m > 0 && metric) HIPC(c, hipMemcpy(metric, c->mx.metric, sizeof(float) * m, hipMemcpyDeviceToHost));
+    if (P > capacity) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed capacity %d", who, P, capacity);
+    return VO_OK;
+}
+
+int vo_match_radius(vo_ctx* c, const uint8_t* F1, int n1, const uint8_t* F2, int n2, const float* points2, const float* centers,
+                    const float* radius, int n_radius, const vo_match_opts* opts, uint32_t* pairs, float* metric, int capacity,
+                    int* n_pairs)
+{
+    const char* who = "vo_match_radius";
+    if (!c || n1 < 0 || n2 < 0 || (n1 && !F1) || (n2 && !F2)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    vo_match_params p;
+    int unique = 0;
+    int rc = match_opts_resolve(c, opts, &p, &unique, who);
+    if (rc || (rc = radius_args_check(c, who, n1, n2, points2, centers, radius, n_radius, 0))) return rc;
+    if (n1 > c->set[0].sb.kp_cap || n2 > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: more rows than max_keypoints", who);
+    CallScope call(c); if (call.status) return call.status;
+    if (n1) HIPC(c, hipMemcpyAsync(c->d_fd[0], F1, (size_t)n1 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPC(c, hipMemcpyAsync(c->d_fd[1], F2, (size_t)n2 * VO_DESC_LEN, hipMemcpyHostToDevice, c->stream));
+    return match_radius_staged(c, n1, n2, points2, centers, radius, n_radius, 0, p, unique, pairs, metric, capacity, n_pairs, who);
+}
+
+int vo_match_radius_f32(vo_ctx* c, const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major,
+                        const float* points2, const float* centers, const float* radius, int n_radius, const vo_match_opts* opts,
+                        uint32_t* pairs, float* metric, int capacity, int* n_pairs)
+{
+    const char* who = "vo_match_radius_f32";
+    if (!c || n1 < 0 || n2 < 0 || (col_major != 0 && col_major != 1)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    vo_match_params p;
+    int unique = 0;
+    int rc = match_opts_resolve(c, opts, &p, &unique, who);
+    if (rc || (rc = radius_args_check(c, who, n1, n2, points2, centers, radius, n_radius, col_major))) return rc;
+    int bad = 0;
+    if ((rc = stage_f32(c, F1, n1, ld1, F2, n2, ld2, col_major, &bad, who)) != VO_OK) return rc;
+    if (bad) return fail(c, VO_ERR_ARG, "%s: features must hold integers in [0, 255] (general single features are not matched in radius)", who);
+    CallScope call(c); if (call.status) return call.status;
+    return match_radius_staged(c, n1, n2, points2, centers, radius, n_radius, col_major, p, unique, pairs, metric, capacity,
+                               n_pairs, who);
 }
 
 // vo_pair_stats.flags / vo_step_out.flags of one frame's n images: VO_FLAG_KEYPOINTS if an

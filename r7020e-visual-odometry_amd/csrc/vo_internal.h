@@ -290,6 +290,29 @@ void match_launch_ex(const MatchBuffers& b, const MatchJob* d_job, const MatchEx
                      hipStream_t s);
 void match_f32_launch_ex(const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, float* A, float* BT,
                          int* res, float* best, int* back, const vo_match_params& p, int unique, hipStream_t s);
+// vo_match_radius / vo_match_radius_f32 (matchFeaturesInRadius): what they need beyond MatchBuffers
+// and MatchExBuffers, allocated by the first such call.  pts2 / centers / radius are the caller's
+// arrays as they lie; geo1 [row_cap] = {cx, cy, r2, 0} per F1 row, geo2 [row_cap] = {x, y, 0, 0} per
+// F2 row; box1 / box2 two float4 per aligned 32-row tile: {xmin, xmax, ymin, ymax} of the tile's
+// positions and {largest r2, 0, 0, 0} (F1 side; 0 on the F2 side).
+typedef float vo_geo4 __attribute__((ext_vector_type(4)));
+struct MatchRadiusBuffers {
+    float* pts2 = nullptr;           // [row_cap][2]
+    float* centers = nullptr;        // [row_cap][2]
+    float* radius = nullptr;         // [row_cap]
+    vo_geo4* geo1 = nullptr;
+    vo_geo4* geo2 = nullptr;
+    vo_geo4* box1 = nullptr;         // [2 * ceil(row_cap / 32)]
+    vo_geo4* box2 = nullptr;
+};
+hipError_t match_radius_alloc(DevPool& pool, MatchRadiusBuffers& r, const MatchBuffers& b);   // all or nothing
+// One in-radius match of the two staged descriptor sets d1 / d2 (metadata m1 / m2, n1, n2 > 0 rows):
+// k_radius_meta over r's raw arrays (col_major: point (i, k) at P[i + k * n]; n_radius 1 or n1), the
+// gated forward pass into b's slot 0, with `unique` the gated backward pass into x.partial_back,
+// then k_match_finish_unique on d_job (whose counts are n1, n2).
+void match_radius_launch(const MatchBuffers& b, const MatchJob* d_job, const MatchExBuffers& x, const MatchRadiusBuffers& r,
+                         const uint8_t* d1, const DescMeta* m1, int n1, const uint8_t* d2, const DescMeta* m2, int n2,
+                         int col_major, int n_radius, const vo_match_params& p, int unique, hipStream_t s);
 void desc_meta_launch(const uint8_t* desc, DescMeta* meta, int n, hipStream_t s);
 void pack_f32_desc_launch(const float* F, int n, int ld, int col_major, uint8_t* out, int* bad, hipStream_t s);
 // matchFeatures on general single features (not u8-valued): normalised rows A [n1][128], F2

@@ -129,6 +129,7 @@ EXPORTS = [
     "vo_check_points", "vo_describe", "vo_describe_batch",
     "vo_triangulate_ex", "vo_fetch_track_quality",
     "vo_default_refine_params", "vo_refine_pose", "vo_set_pose_refinement", "vo_fetch_pose_refinement",
+    "vo_match_radius", "vo_match_radius_f32",
 ]
 
 _libs: dict = {}
@@ -176,6 +177,12 @@ def load_library(path: str | os.PathLike | None = None):
                               C.c_int, P(C.c_int)]
     L.vo_match_f32_ex.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int, C.c_int, C.c_int, P(MatchOpts),
                                   P(C.c_uint32), P(C.c_float), C.c_int, P(C.c_int)]
+    if hasattr(L, "vo_match_radius"):    # (absent from an older library timed beside this one: tools/match_radius_times.py)
+        L.vo_match_radius.argtypes = [vp, P(C.c_uint8), C.c_int, P(C.c_uint8), C.c_int, P(C.c_float), P(C.c_float), P(C.c_float),
+                                      C.c_int, P(MatchOpts), P(C.c_uint32), P(C.c_float), C.c_int, P(C.c_int)]
+        L.vo_match_radius_f32.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, P(C.c_float), C.c_int, C.c_int, C.c_int,
+                                          P(C.c_float), P(C.c_float), P(C.c_float), C.c_int, P(MatchOpts), P(C.c_uint32),
+                                          P(C.c_float), C.c_int, P(C.c_int)]
     L.vo_undistort.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(Distortion), P(C.c_uint8), C.c_int]
     L.vo_undistort_batch_dev.argtypes = [vp, vp, C.c_int, P(Distortion), vp]
     L.vo_set_distortion.argtypes = [vp, P(Distortion), P(Distortion)]
@@ -238,6 +245,39 @@ def load_library(path: str | os.PathLike | None = None):
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
+
+
+def _f32_views(F1, F2, who: str):
+    """Two n x 128 float32 matrices as the f32 entries take them, without a copy where their
+    storage allows: -> (A, ld1, B, ld2, col_major).  A Fortran-ordered array (MATLAB's layout) and
+    a C-ordered one (any row stride) go through as they lie; the second follows the first's order."""
+    def view(F):
+        F = np.asarray(F)
+        if F.dtype != np.float32 or F.ndim != 2 or F.shape[1] != 128:
+            raise VOError(VO_ERR_ARG, f"{who}: n x 128 float32 matrices")
+        if F.strides[0] == 4 and F.strides[1] % 4 == 0 and F.shape[0] > 0:       # column-major
+            return F, F.strides[1] // 4, 1
+        if F.strides[1] == 4 and F.strides[0] % 4 == 0:
+            return F, max(F.strides[0] // 4, 128), 0
+        F = np.ascontiguousarray(F)
+        return F, 128, 0
+    (A, la, ca), (B, lb, cb) = view(F1), view(F2)
+    if A.shape[0] and B.shape[0] and ca != cb:
+        B, lb, cb = (np.asfortranarray(B), B.shape[0], 1) if ca else (np.ascontiguousarray(B), 128, 0)
+    return A, la, B, lb, (ca if A.shape[0] else cb)
+
+
+def _radius_args(n1: int, n2: int, points2, centers, radius, who: str, order: str = "C"):
+    """points2 n2 x 2, centers n1 x 2 and radius (a scalar or n1 values) as float32 arrays in
+    storage order `order`; the values themselves are checked by libvo."""
+    P2 = np.asarray(points2, np.float32).reshape(-1, 2) if np.size(points2) else np.zeros((0, 2), np.float32)
+    Cn = np.asarray(centers, np.float32).reshape(-1, 2) if np.size(centers) else np.zeros((0, 2), np.float32)
+    r = np.ascontiguousarray(np.asarray(radius, np.float32).reshape(-1))
+    if P2.shape[0] != n2 or Cn.shape[0] != n1:
+        raise VOError(VO_ERR_ARG, f"{who}: points2 must be n2 x 2 and centers n1 x 2")
+    P2 = np.asfortranarray(P2) if order == "F" else np.ascontiguousarray(P2)
+    Cn = np.asfortranarray(Cn) if order == "F" else np.ascontiguousarray(Cn)
+    return P2, Cn, r
 
 
 def default_sift_params(max_keypoints: int = 16384) -> SiftParams:
@@ -544,20 +584,7 @@ class Context:
         (vo_match_f32): a Fortran-ordered array (MATLAB's layout) goes through without a
         transpose, a C-ordered one (any row stride) likewise.  Keywords as for match()
         (vo_match_f32_ex)."""
-        def view(F):
-            F = np.asarray(F)
-            if F.dtype != np.float32 or F.ndim != 2 or F.shape[1] != 128:
-                raise VOError(VO_ERR_ARG, "match_f32: n x 128 float32 matrices")
-            if F.strides[0] == 4 and F.strides[1] % 4 == 0 and F.shape[0] > 0:       # column-major
-                return F, F.strides[1] // 4, 1
-            if F.strides[1] == 4 and F.strides[0] % 4 == 0:
-                return F, max(F.strides[0] // 4, 128), 0
-            F = np.ascontiguousarray(F)
-            return F, 128, 0
-        (A, la, ca), (B, lb, cb) = view(F1), view(F2)
-        if A.shape[0] and B.shape[0] and ca != cb:
-            B, lb, cb = (np.asfortranarray(B), B.shape[0], 1) if ca else (np.ascontiguousarray(B), 128, 0)
-        order = ca if A.shape[0] else cb
+        A, la, B, lb, order = _f32_views(F1, F2, "match_f32")
         cap = max(A.shape[0], 1)
         pairs = np.zeros((cap, 2), np.uint32)
         n = C.c_int(0)
@@ -571,6 +598,44 @@ class Context:
         metric = np.zeros(cap, np.float32)
         self._check(self.lib.vo_match_f32_ex(self.h, pa, A.shape[0], la, pb, B.shape[0], lb, order, C.byref(opts),
                                              _p(pairs, C.c_uint32), _p(metric, C.c_float), cap, C.byref(n)))
+        return (pairs[: n.value].copy(), metric[: n.value].copy()) if return_metric else pairs[: n.value].copy()
+
+    # ---- matchFeaturesInRadius ----
+    def match_in_radius(self, F1: np.ndarray, F2: np.ndarray, points2, centers, radius, *, unique: bool = False,
+                        match_threshold: float | None = None, max_ratio: float | None = None, return_metric: bool = False):
+        """matchFeaturesInRadius(F1, F2, points2, centerPoints, radius) on uint8 descriptors
+        (vo_match_radius): F1 row i is matched only against the F2 rows whose point (points2, n2 x 2)
+        lies within radius (a scalar, or one per F1 row) of centers[i], the circle closed; the ratio
+        test and Unique run over those candidates alone.  Keywords as for match()."""
+        F1 = np.ascontiguousarray(F1, np.uint8).reshape(-1, 128)
+        F2 = np.ascontiguousarray(F2, np.uint8).reshape(-1, 128)
+        P2, Cn, r = _radius_args(F1.shape[0], F2.shape[0], points2, centers, radius, "match_in_radius")
+        cap = max(F1.shape[0], 1)
+        pairs = np.zeros((cap, 2), np.uint32)
+        metric = np.zeros(cap, np.float32)
+        n = C.c_int(0)
+        opts = self._match_opts(unique, match_threshold, max_ratio)
+        self._check(self.lib.vo_match_radius(self.h, _p(F1, C.c_uint8), F1.shape[0], _p(F2, C.c_uint8), F2.shape[0],
+                                             _p(P2, C.c_float), _p(Cn, C.c_float), _p(r, C.c_float), len(r), C.byref(opts),
+                                             _p(pairs, C.c_uint32), _p(metric, C.c_float), cap, C.byref(n)))
+        return (pairs[: n.value].copy(), metric[: n.value].copy()) if return_metric else pairs[: n.value].copy()
+
+    def match_in_radius_f32(self, F1: np.ndarray, F2: np.ndarray, points2, centers, radius, *, unique: bool = False,
+                            match_threshold: float | None = None, max_ratio: float | None = None, return_metric: bool = False):
+        """match_in_radius on single-precision n x 128 matrices with integer values 0..255 in their
+        own storage order (vo_match_radius_f32); the point matrices go in the features' order."""
+        A, la, B, lb, order = _f32_views(F1, F2, "match_in_radius_f32")
+        P2, Cn, r = _radius_args(A.shape[0], B.shape[0], points2, centers, radius, "match_in_radius_f32", "F" if order else "C")
+        cap = max(A.shape[0], 1)
+        pairs = np.zeros((cap, 2), np.uint32)
+        metric = np.zeros(cap, np.float32)
+        n = C.c_int(0)
+        pa = A.ctypes.data_as(C.POINTER(C.c_float)) if A.shape[0] else None
+        pb = B.ctypes.data_as(C.POINTER(C.c_float)) if B.shape[0] else None
+        opts = self._match_opts(unique, match_threshold, max_ratio)
+        self._check(self.lib.vo_match_radius_f32(self.h, pa, A.shape[0], la, pb, B.shape[0], lb, order, _p(P2, C.c_float),
+                                                 _p(Cn, C.c_float), _p(r, C.c_float), len(r), C.byref(opts),
+                                                 _p(pairs, C.c_uint32), _p(metric, C.c_float), cap, C.byref(n)))
         return (pairs[: n.value].copy(), metric[: n.value].copy()) if return_metric else pairs[: n.value].copy()
 
     # ---- benchmark workload: SIFT + stereo match of B pairs resident on device ----
@@ -969,3 +1034,17 @@ def matchFeatures(features1: np.ndarray, features2: np.ndarray, *, unique: bool 
     Keywords as for Context.match; return_metric=True returns (indexPairs, matchMetric)."""
     return _default_ctx(375, 1242).match(features1, features2, unique=unique, match_threshold=match_threshold,
                                          max_ratio=max_ratio, return_metric=return_metric)
+
+
+def matchFeaturesInRadius(features1: np.ndarray, features2: np.ndarray, points2, centerPoints, radius, *, unique: bool = False,
+                          match_threshold: float | None = None, max_ratio: float | None = None, return_metric: bool = False):
+    """matchFeaturesInRadius(features1, features2, points2, centerPoints, radius): matchFeatures
+    restricted, for every row of features1, to the features2 rows whose point lies within `radius`
+    (a scalar or one per row) of that row's centre.  points2 may be an n2 x 2 array or a keypoint
+    array with fields x, y (what detectSIFTFeatures returns).  Keywords as for matchFeatures."""
+    p2 = np.asarray(points2)
+    if p2.dtype.names and "x" in p2.dtype.names:
+        p2 = np.stack([p2["x"], p2["y"]], 1)
+    return _default_ctx(375, 1242).match_in_radius(features1, features2, p2, centerPoints, radius, unique=unique,
+                                                   match_threshold=match_threshold, max_ratio=max_ratio,
+                                                   return_metric=return_metric)
