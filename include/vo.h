@@ -37,6 +37,8 @@
  *   vo_refine_pose         bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose,
  *   vo_set_pose_refinement intrinsics) on estworldpose's pose and inliers (VO.m:123-130): as a
  *   vo_fetch_pose_refinement call, and as an optional stage of the loop body
+ *   vo_est_fundamental /   estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method = "MSAC" |
+ *   vo_est_fundamental_batch "Norm8Point"): the epipolar check of 2-D/2-D matches after matchFeatures
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
  *                          CreateLandmarksFromFeatures.m:1-21
  *   vo_step / vo_step_batch the whole loop body VO.m:70-161 (features stay
@@ -502,6 +504,70 @@ void vo_default_refine_params(vo_refine_params* p);
 int vo_refine_pose(vo_ctx* ctx, const double* img, const double* world, int n, const uint8_t* use,
                    const double K[9], const double T_in[16], const vo_refine_params* p,
                    double T_out[16], vo_refine_stats* stats);
+
+/* ---- estimateFundamentalMatrix: the epipolar check of 2-D/2-D matches ---- */
+/* [F, inliersIndex, status] = estimateFundamentalMatrix(matchedPoints1, matchedPoints2,
+ * Method = "MSAC" | "Norm8Point", NumTrials, DistanceThreshold, Confidence), the geometric filter a
+ * feature pipeline applies right after matchFeatures.  Convention: [x2 1] F [x1 1]' = 0, F 3x3
+ * row-major with unit Frobenius norm and F[8] >= 0; points are single 1-based pixels.
+ *
+ * Spec (vo_spec.h vo_fund_*, shared by the device and the CPU reference; f64, + - * / and sqrt in
+ * the order written there, no contraction, so both give the same bytes):
+ *  - a fit normalises each image's points (centroid c, mean distance d, s = sqrt(2) / d; a scale
+ *    that is not finite: no model), sums the 45 entries of A'A for the rows
+ *    [bx ax, bx ay, bx, by ax, by ay, by, ax, ay, 1], takes the eigenvector of its smallest
+ *    eigenvalue by cyclic two-sided Jacobi (at most 30 sweeps; a pair is skipped when
+ *    |a_pq| <= 2^-53 (|a_pp| + |a_qq|)), removes the smallest singular value with the smallest
+ *    eigenvector v of Fh'Fh (F' = Fh - (Fh v) v'), denormalises (T2' F' T1), divides by the Frobenius
+ *    norm and negates if F[8] < 0; a non-finite F: no model;
+ *  - a sample's 8 points are summed sequentially in sample order; a fit over a mask in 64 partials
+ *    (partial l: the used points k = l mod 64, ascending) joined by p[i] += p[i + off],
+ *    off = 32 .. 1, in three passes (centroids, mean distances, the 45 sums);
+ *  - the distance is Sampson's, in px^2; inlier iff d < distance_threshold (a NaN fails); the MSAC
+ *    score is the sum of min(d, threshold) in the same 64 partials;
+ *  - MSAC: slot s of the problem with key k draws 8 indices per attempt from two Philox4x32-10 calls
+ *    (counter {s, attempt, k, 0xF8A70000 / 0xF8A70001}, key {seed, 0x9E3779B9}), up to 16 attempts
+ *    for 8 distinct ones; a slot without a sample or without a model is no trial.  Slots are replayed
+ *    in order, a strictly smaller score wins, and after each improvement the trial bound becomes
+ *    min(bound, ceil(log(1 - conf) / log(1 - w^8))), w = n_in / n (log(1 - w^8) == 0: no bound);
+ *  - the mask is the best slot's inliers and F the masked fit over it.
+ * Status (the return value of the single call, status[f] of the batch): VO_OK; VO_ERR_TOO_FEW_POINTS
+ * for n < 8 (the toolbox's status 1); VO_ERR_NO_CONSENSUS for no valid slot, fewer than 8 inliers or
+ * a refit without a model (status 2) -- F and the mask are then 0.  VO_FUND_NORM8 is the masked fit
+ * over all n points, no sampling (mask all 1).  RANSAC, LMedS, LTS and the algebraic distance are
+ * not implemented: any other method is VO_ERR_ARG. */
+#define VO_FUND_NORM8 0
+#define VO_FUND_MSAC  1
+
+typedef struct {
+    int32_t  method;              /* VO_FUND_NORM8 or VO_FUND_MSAC (default) */
+    int32_t  num_trials;          /* NumTrials, 1 .. 100000; default 500 */
+    double   distance_threshold;  /* DistanceThreshold, px^2, finite and > 0; default 0.01 */
+    double   confidence;          /* Confidence, percent, in (0, 100); default 99 */
+    uint32_t seed;                /* Philox key word; default 0x5EED */
+} vo_fund_params;
+
+void vo_default_fund_params(vo_fund_params* p);
+
+/* x1, x2 [n][2] single host buffers (as vo_triangulate takes them) -> F [9], inliers [n] (0/1, may be
+ * NULL), *n_inliers (may be NULL).  params NULL = the defaults; key is mixed into the Philox counter
+ * (a frame index, say).  Returns the status above.  VO_ERR_ARG, checked on the host before anything
+ * is enqueued and naming the first offending row: a non-finite coordinate, parameters outside the
+ * ranges above.  VO_ERR_CAPACITY for n > max_keypoints, VO_ERR_STATE while step batches are pending.
+ * n < 8 launches nothing.  The first call that launches allocates the call's own buffers (17 bytes
+ * per point, 6 KiB per problem); a context that never calls allocates and launches nothing.  The
+ * loop state (features, pose, landmarks) and every other entry are untouched. */
+int vo_est_fundamental(vo_ctx* ctx, const float* x1, const float* x2, int n, const vo_fund_params* params,
+                       uint32_t key, double F[9], uint8_t* inliers, int* n_inliers);
+
+/* B problems (0 .. max_batch) in one launch: problem f has n_pts[f] points (0 .. pts_stride) at
+ * x1 / x2 + f * pts_stride * 2, pts_stride <= max_keypoints, and key key0 + f.  Outputs F [B][9],
+ * inliers [B][pts_stride] (may be NULL; 0 beyond n_pts[f]), n_inliers [B] (may be NULL), status [B].
+ * Problem f's outputs equal the single call's with key0 + f, by bytes.  Returns VO_OK when it ran
+ * (per-problem outcomes are in status), or the refusals of the single call. */
+int vo_est_fundamental_batch(vo_ctx* ctx, const float* x1, const float* x2, int pts_stride, const int32_t* n_pts, int B,
+                             const vo_fund_params* params, uint32_t key0, double* F, uint8_t* inliers,
+                             int32_t* n_inliers, int32_t* status);
 
 /* new-landmark filter (VO.m:145-158) + CreateLandmarksFromFeatures.
  * l_pos/r_pos [S][2] current stereo-matched locations; old_l/old_r [K][2]

@@ -796,4 +796,335 @@ VO_HD float vo_radius_box_lb(float xmin, float xmax, float ymin, float ymax, flo
     return sx + sy;
 }
 
+/* ------------------------------------------------------------------------ */
+/* estimateFundamentalMatrix: normalised 8-point fit, Sampson distance and   */
+/* the MSAC loop's pieces.  One definition for the kernel (k_fund_msac,      */
+/* geom.hip) and the CPU reference (tests/fund_ref), equal by bytes: f64     */
+/* only, + - * / and sqrt in the order written, no contraction, no libm      */
+/* (vo_log_d for the trial bound).  Convention: [x2 1] F [x1 1]' = 0, F 3x3  */
+/* row-major; points are single 1-based pixels widened to double.            */
+/*                                                                           */
+/* Work arrays (the 9x9 problem's 45 + 81 doubles) are addressed with a      */
+/* stride: element e of an array lives at a[e * stride].  The reference      */
+/* passes 1; the kernel keeps a chunk's hypotheses in LDS, element-major      */
+/* across the chunk's slots (stride = slots), so lanes on neighbouring slots */
+/* touch neighbouring banks.  The stride moves values, it computes nothing.  */
+/* ------------------------------------------------------------------------ */
+#define VO_FUND_SAMPLE 8
+#define VO_FUND_ATTEMPTS 16          /* draws of 8 indices before a slot is invalid */
+#define VO_FUND_NSUM 45              /* upper triangle of A'A, row-major */
+#define VO_FUND_NWORK (45 + 81)      /* ... and the eigenvector matrix */
+#define VO_FUND_LANES 64             /* partial sums of a masked fit: partial l adds the used points k = l (mod 64) */
+#define VO_FUND_SWEEP_CAP 30         /* cyclic Jacobi sweeps, at most */
+#define VO_FUND_SKIP_EPS 1.1102230246251565e-16   /* 2^-53: a_pq is negligible beside |a_pp| + |a_qq| */
+#define VO_FUND_SQRT2 1.4142135623730951
+#define VO_FUND_TAG0 0xF8A70000u     /* Philox counter word 3 of the two draws (k_msac's is 0x5EED) */
+#define VO_FUND_TAG1 0xF8A70001u
+#define VO_FUND_NO_BOUND 0x7fffffff
+
+/* index of (i, j), i <= j, in the row-major upper triangle of an n x n symmetric matrix */
+VO_HD int vo_fund_tri(int n, int i, int j) { return i * n - (i * (i - 1)) / 2 + (j - i); }
+
+VO_HD int vo_fund_finite(double v) { return v - v == 0.0; }
+
+/* One rotation's parameters from (a_pp, a_qq, a_pq).  Returns 1 (skip: nothing is written) iff
+ * |a_pq| <= 2^-53 (|a_pp| + |a_qq|) (a NaN is never skipped); otherwise
+ *   theta = (a_qq - a_pp) / (2 a_pq),  t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)),  sgn(0) = 1,
+ *   c = 1 / sqrt(t^2 + 1),  s = t c. */
+VO_HD int vo_fund_rot(double app, double aqq, double apq, double* t, double* c, double* s)
+{
+    if (fabs(apq) <= VO_FUND_SKIP_EPS * (fabs(app) + fabs(aqq))) return 1;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double tt = (theta < 0.0 ? -1.0 : 1.0) / den;
+    const double cc = 1.0 / sqrt(tt * tt + 1.0);
+    *t = tt; *c = cc; *s = tt * cc;
+    return 0;
+}
+
+/* (x, y) <- (c x - s y, s x + c y): what a rotation does to (a_kp, a_kq), k != p, q, and to (v_kp, v_kq), every k */
+VO_HD void vo_fund_rot_xy(double c, double s, double* x, double* y)
+{
+    const double x0 = *x, y0 = *y;
+    *x = c * x0 - s * y0;
+    *y = s * x0 + c * y0;
+}
+
+/* index of the smallest diagonal entry of A (ties: the lowest; a NaN never wins) */
+VO_HD int vo_fund_argmin_diag(const double* A, int n, int stride)
+{
+    int jmin = 0;
+    double dmin = A[0];
+    for (int j = 1; j < n; ++j) {
+        const double d = A[vo_fund_tri(n, j, j) * stride];
+        if (d < dmin || (dmin != dmin && d == d)) { dmin = d; jmin = j; }
+    }
+    return jmin;
+}
+
+/* Cyclic two-sided Jacobi on the symmetric n x n matrix A (upper triangle, vo_fund_tri) with the
+ * eigenvector matrix V (n x n row-major, set to the identity here) carried along.  Pairs (p, q),
+ * p < q, row-major; each pair is vo_fund_rot on (a_pp, a_qq, a_pq), then, unless skipped,
+ *   a_pp -= t a_pq,  a_qq += t a_pq,  a_pq = 0,  and vo_fund_rot_xy on every (a_kp, a_kq), (v_kp, v_kq).
+ * The element updates of one rotation are independent of one another, so their order (and who
+ * performs them: the kernel spreads them over a group of lanes) does not change a bit.
+ * The loop ends after the first sweep that rotates nothing, or after VO_FUND_SWEEP_CAP sweeps.
+ * Returns the index of the smallest diagonal entry (vo_fund_argmin_diag), whose eigenvector is
+ * column j of V: V[k * n + j].  *sweeps_out (may be NULL) counts the sweeps run. */
+VO_HD int vo_fund_jacobi(double* A, double* V, int n, int stride, int* sweeps_out)
+{
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) V[(i * n + j) * stride] = i == j ? 1.0 : 0.0;
+    int sweeps = 0;
+    for (; sweeps < VO_FUND_SWEEP_CAP;) {
+        int rotated = 0;
+        for (int p = 0; p < n - 1; ++p) {
+            for (int q = p + 1; q < n; ++q) {
+                const int ipp = vo_fund_tri(n, p, p) * stride, iqq = vo_fund_tri(n, q, q) * stride;
+                const int ipq = vo_fund_tri(n, p, q) * stride;
+                const double apq = A[ipq], app = A[ipp], aqq = A[iqq];
+                double t, c, s;
+                if (vo_fund_rot(app, aqq, apq, &t, &c, &s)) continue;
+                rotated = 1;
+                A[ipp] = app - t * apq;
+                A[iqq] = aqq + t * apq;
+                A[ipq] = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    if (k == p || k == q) continue;
+                    const int ikp = (k < p ? vo_fund_tri(n, k, p) : vo_fund_tri(n, p, k)) * stride;
+                    const int ikq = (k < q ? vo_fund_tri(n, k, q) : vo_fund_tri(n, q, k)) * stride;
+                    double x = A[ikp], y = A[ikq];
+                    vo_fund_rot_xy(c, s, &x, &y);
+                    A[ikp] = x;
+                    A[ikq] = y;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const int ikp = (k * n + p) * stride, ikq = (k * n + q) * stride;
+                    double x = V[ikp], y = V[ikq];
+                    vo_fund_rot_xy(c, s, &x, &y);
+                    V[ikp] = x;
+                    V[ikq] = y;
+                }
+            }
+        }
+        ++sweeps;
+        if (!rotated) break;
+    }
+    if (sweeps_out) *sweeps_out = sweeps;
+    return vo_fund_argmin_diag(A, n, stride);
+}
+
+/* One image's normalisation from its sums: centroid c = sum / m, then (second call) the scale
+ * s = sqrt(2) / (dsum / m).  T = [s 0 -s cx; 0 s -s cy; 0 0 1] is kept as N = (s, cx, cy). */
+VO_HD double vo_fund_dist(double x, double y, double cx, double cy)
+{
+    double dx = x - cx, dy = y - cy;
+    return sqrt(dx * dx + dy * dy);
+}
+
+/* the 45 products of one normalised pair's design row, added to acc[q * stride] (upper triangle, row-major):
+ * a = s1 (x1 - c1), b = s2 (x2 - c2), row = [bx ax, bx ay, bx, by ax, by ay, by, ax, ay, 1] */
+VO_HD void vo_fund_row(const double* N1, const double* N2, double x1, double y1, double x2, double y2, double* acc, int stride)
+{
+    double ax = N1[0] * (x1 - N1[1]), ay = N1[0] * (y1 - N1[2]);
+    double bx = N2[0] * (x2 - N2[1]), by = N2[0] * (y2 - N2[2]);
+    double r[9];
+    r[0] = bx * ax; r[1] = bx * ay; r[2] = bx; r[3] = by * ax; r[4] = by * ay; r[5] = by; r[6] = ax; r[7] = ay; r[8] = 1.0;
+    int q = 0;
+    VO_UNROLL
+    for (int i = 0; i < 9; ++i) {
+        VO_UNROLL
+        for (int j = i; j < 9; ++j) {
+            acc[q * stride] = acc[q * stride] + r[i] * r[j];
+            ++q;
+        }
+    }
+}
+
+/* A sample's fit: the 8 points idx[0..7] of x1 / x2 ([n][2] single) summed sequentially in sample
+ * order from +0, in three passes (centroids, mean distances, the 45 sums).  Writes N1, N2 and
+ * M[q * stride]; returns 0 (no model) when either scale is not finite. */
+VO_HD int vo_fund_fit_sample(const float* x1, const float* x2, const uint32_t* idx, double* N1, double* N2, double* M, int stride)
+{
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    VO_UNROLL
+    for (int k = 0; k < VO_FUND_SAMPLE; ++k) {
+        s[0] = s[0] + (double)x1[2 * idx[k]]; s[1] = s[1] + (double)x1[2 * idx[k] + 1];
+        s[2] = s[2] + (double)x2[2 * idx[k]]; s[3] = s[3] + (double)x2[2 * idx[k] + 1];
+    }
+    const double m = (double)VO_FUND_SAMPLE;
+    N1[1] = s[0] / m; N1[2] = s[1] / m; N2[1] = s[2] / m; N2[2] = s[3] / m;
+    double d1 = 0.0, d2 = 0.0;
+    VO_UNROLL
+    for (int k = 0; k < VO_FUND_SAMPLE; ++k) {
+        d1 = d1 + vo_fund_dist((double)x1[2 * idx[k]], (double)x1[2 * idx[k] + 1], N1[1], N1[2]);
+        d2 = d2 + vo_fund_dist((double)x2[2 * idx[k]], (double)x2[2 * idx[k] + 1], N2[1], N2[2]);
+    }
+    N1[0] = VO_FUND_SQRT2 / (d1 / m);
+    N2[0] = VO_FUND_SQRT2 / (d2 / m);
+    if (!vo_fund_finite(N1[0]) || !vo_fund_finite(N2[0])) return 0;
+    for (int q = 0; q < VO_FUND_NSUM; ++q) M[q * stride] = 0.0;
+    for (int k = 0; k < VO_FUND_SAMPLE; ++k)
+        vo_fund_row(N1, N2, (double)x1[2 * idx[k]], (double)x1[2 * idx[k] + 1], (double)x2[2 * idx[k]], (double)x2[2 * idx[k] + 1], M,
+                    stride);
+    return 1;
+}
+
+/* From M (W[0..44]) and the two normalisations to F: the null vector of M (Jacobi at 9x9, V in
+ * W[45..125]), rank 2 by v = the smallest eigenvector of Fh' Fh (Jacobi at 3x3, in W[0..5] and
+ * W[45..53], which the 9x9 problem no longer needs) and F' = Fh - (Fh v) v', then F = T2' F' T1,
+ * divided by its Frobenius norm (squares summed in index order) and negated if F[8] < 0.
+ * Returns 0 (no model, F untouched) when a value of F is not finite.  sweeps (may be NULL): the
+ * two Jacobi calls' sweep counts. */
+VO_HD int vo_fund_solve_tail(double* W, int stride, int j9, const double* N1, const double* N2, double* F, int* sweeps);
+
+VO_HD int vo_fund_solve(double* W, int stride, const double* N1, const double* N2, double* F, int* sweeps)
+{
+    const int j9 = vo_fund_jacobi(W, W + VO_FUND_NSUM * stride, 9, stride, sweeps);
+    return vo_fund_solve_tail(W, stride, j9, N1, N2, F, sweeps);
+}
+
+/* vo_fund_solve after its 9x9 Jacobi, whose result is column j9 of V */
+VO_HD int vo_fund_solve_tail(double* W, int stride, int j9, const double* N1, const double* N2, double* F, int* sweeps)
+{
+    double* V = W + VO_FUND_NSUM * stride;
+    double Fh[9];
+    VO_UNROLL
+    for (int k = 0; k < 9; ++k) Fh[k] = V[(k * 9 + j9) * stride];
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        VO_UNROLL
+        for (int j = i; j < 3; ++j)
+            W[vo_fund_tri(3, i, j) * stride] = (Fh[i] * Fh[j] + Fh[3 + i] * Fh[3 + j]) + Fh[6 + i] * Fh[6 + j];
+    }
+    const int j3 = vo_fund_jacobi(W, V, 3, stride, sweeps ? sweeps + 1 : sweeps);
+    double v[3], Fv[3], G[9], H[9];
+    VO_UNROLL
+    for (int k = 0; k < 3; ++k) v[k] = V[(k * 3 + j3) * stride];
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) Fv[i] = (Fh[3 * i] * v[0] + Fh[3 * i + 1] * v[1]) + Fh[3 * i + 2] * v[2];
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        VO_UNROLL
+        for (int j = 0; j < 3; ++j) G[3 * i + j] = Fh[3 * i + j] - Fv[i] * v[j];
+    }
+    const double s1 = N1[0], ox1 = -(N1[0] * N1[1]), oy1 = -(N1[0] * N1[2]);
+    const double s2 = N2[0], ox2 = -(N2[0] * N2[1]), oy2 = -(N2[0] * N2[2]);
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {                     /* H = F' T1 */
+        H[3 * i] = G[3 * i] * s1;
+        H[3 * i + 1] = G[3 * i + 1] * s1;
+        H[3 * i + 2] = (G[3 * i] * ox1 + G[3 * i + 1] * oy1) + G[3 * i + 2];
+    }
+    VO_UNROLL
+    for (int j = 0; j < 3; ++j) {                     /* G = T2' H */
+        G[j] = s2 * H[j];
+        G[3 + j] = s2 * H[3 + j];
+        G[6 + j] = (ox2 * H[j] + oy2 * H[3 + j]) + H[6 + j];
+    }
+    double nn = 0.0;
+    VO_UNROLL
+    for (int k = 0; k < 9; ++k) nn = nn + G[k] * G[k];
+    nn = sqrt(nn);
+    int ok = 1;
+    VO_UNROLL
+    for (int k = 0; k < 9; ++k) {
+        G[k] = G[k] / nn;
+        if (!vo_fund_finite(G[k])) ok = 0;
+    }
+    if (!ok) return 0;
+    const int neg = G[8] < 0.0;
+    VO_UNROLL
+    for (int k = 0; k < 9; ++k) F[k] = neg ? -G[k] : G[k];
+    return 1;
+}
+
+/* Sampson distance of one pair (px^2): r^2 / ((F x1)_0^2 + (F x1)_1^2 + (F' x2)_0^2 + (F' x2)_1^2),
+ * r = x2' F x1.  0 / 0 is NaN, which fails every comparison (no inlier, scored as the threshold). */
+VO_HD double vo_fund_sampson(const double* F, double x1, double y1, double x2, double y2)
+{
+    double l0 = (F[0] * x1 + F[1] * y1) + F[2];
+    double l1 = (F[3] * x1 + F[4] * y1) + F[5];
+    double l2 = (F[6] * x1 + F[7] * y1) + F[8];
+    double r = (x2 * l0 + y2 * l1) + l2;
+    double m0 = (F[0] * x2 + F[3] * y2) + F[6];
+    double m1 = (F[1] * x2 + F[4] * y2) + F[7];
+    double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+    return (r * r) / den;
+}
+
+/* Slot `slot` of the problem with key `key`: up to 16 attempts, each 8 indices from two Philox
+ * calls (counter {slot, attempt, key, TAG0 / TAG1}, key words {seed, 0x9E3779B9}); the first
+ * attempt whose 8 indices are distinct is the sample.  Returns 0 when all 16 fail (n < 8 always
+ * does); *attempts (may be NULL) gets the attempts used. */
+VO_HD int vo_fund_sample(uint32_t seed, uint32_t key, uint32_t slot, uint32_t n, uint32_t* idx, int* attempts)
+{
+    int ok = 0;
+    uint32_t att = 0;
+    for (; att < VO_FUND_ATTEMPTS && !ok; ++att) {
+        vo_u32x4 c0 = {{slot, att, key, VO_FUND_TAG0}};
+        vo_u32x4 c1 = {{slot, att, key, VO_FUND_TAG1}};
+        vo_u32x4 r0 = vo_philox4x32_10(c0, seed, 0x9E3779B9u);
+        vo_u32x4 r1 = vo_philox4x32_10(c1, seed, 0x9E3779B9u);
+        VO_UNROLL
+        for (int q = 0; q < 4; ++q) { idx[q] = vo_rand_index(r0.v[q], n); idx[4 + q] = vo_rand_index(r1.v[q], n); }
+        ok = 1;
+        VO_UNROLL
+        for (int i = 0; i < VO_FUND_SAMPLE; ++i) {
+            VO_UNROLL
+            for (int j = i + 1; j < VO_FUND_SAMPLE; ++j)
+                if (idx[i] == idx[j]) ok = 0;
+        }
+    }
+    if (attempts) *attempts = (int)att;
+    return ok;
+}
+
+/* Trials after which a sample of 8 inliers was drawn with probability conf (a fraction), at the
+ * inlier ratio w = n_in / n: ceil(log(1 - conf) / log(1 - w^8)), w^8 = ((w w)^2)^2.  w^8 >= 1 gives
+ * 1; log(1 - w^8) == 0 (w^8 below half an ulp of 1, w < 0.01) gives VO_FUND_NO_BOUND: no inlier
+ * ratio that small ends the loop early. */
+VO_HD int vo_fund_trials_needed(int n_in, int n, double conf)
+{
+    double w = (double)n_in / (double)n;
+    double w2 = w * w;
+    double w4 = w2 * w2;
+    double w8 = w4 * w4;
+    if (w8 >= 1.0) return 1;
+    double den = vo_log_d(1.0 - w8);
+    if (den == 0.0) return VO_FUND_NO_BOUND;
+    double N = ceil(vo_log_d(1.0 - conf) / den);
+    if (N > 2147483647.0) return VO_FUND_NO_BOUND;
+    if (N < 1.0) return 1;
+    return (int)N;
+}
+
+/* The sequential MSAC loop, replayed slot by slot in slot order over (valid, score, n_in):
+ *     vo_fund_replay_begin(&r, num_trials);
+ *     for slot = 0 .. num_trials - 1, while !vo_fund_replay_done(&r):  vo_fund_replay_slot(...)
+ * An invalid slot (no 8 distinct indices, or a sample without a model) counts as no trial.  A valid
+ * one counts, and replaces the best iff its score is strictly smaller; the bound is then
+ * min(bound, vo_fund_trials_needed).  Done once trials >= bound.  Returns 1 when the slot became
+ * the best (the caller keeps its F). */
+typedef struct { int bound, trials, best, best_in; double best_score; } vo_fund_replay;
+
+VO_HD void vo_fund_replay_begin(vo_fund_replay* r, int num_trials)
+{
+    r->bound = num_trials; r->trials = 0; r->best = -1; r->best_in = 0;
+    r->best_score = vo_u64_as_f64(0x7ff0000000000000ULL);
+}
+
+VO_HD int vo_fund_replay_done(const vo_fund_replay* r) { return r->trials >= r->bound; }
+
+VO_HD int vo_fund_replay_slot(vo_fund_replay* r, int slot, int valid, double score, int n_in, int n, double conf)
+{
+    if (!valid) return 0;
+    r->trials = r->trials + 1;
+    if (!(score < r->best_score)) return 0;
+    r->best_score = score; r->best = slot; r->best_in = n_in;
+    int need = vo_fund_trials_needed(n_in, n, conf);
+    if (need < r->bound) r->bound = need;
+    return 1;
+}
+
 #endif /* VO_SPEC_H */

@@ -41,6 +41,10 @@
  *   [refinedA, reprojectionErrors] = vo_mex('refinepose', xyzPoints, imagePoints, A, K, opts)
  *        bundleAdjustmentMotion(xyzPoints, imagePoints, absolutePose, intrinsics) right after
  *        estworldpose (VO.m:123-130): vo_refine_pose; M x 1 double pixel distances at the refined pose
+ *   [F, inliersIndex, status] = vo_mex('fundamental', matchedPoints1, matchedPoints2, opts)
+ *        estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method = "MSAC" | "Norm8Point"), the
+ *        epipolar check right after matchFeatures: vo_est_fundamental; F 3 x 3 double with
+ *        [x2 1] F [x1 1]' = 0, M x 1 logical, int32 status (0, 1 = fewer than 8 points, 2 = not enough inliers)
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
  *        CreateLandmarksFromFeatures.m:2-18 (the rows before the :20 append)
  *   [rel_A, A, status, nLandmarks] = vo_mex('step', Il, Ir, P1, P2)
@@ -725,6 +729,71 @@ static void cmd_refinepose(int nlhs, mxArray* plhs[], int nrhs, const mxArray* p
     mxFree(img);
 }
 
+/* vo_est_fundamental through a weak reference: with a libvo that lacks it 'fundamental' raises
+ * vo:estimateFundamentalMatrix:unavailable and every other command runs as before */
+extern __typeof__(vo_est_fundamental) vo_est_fundamental __attribute__((weak));
+extern __typeof__(vo_default_fund_params) vo_default_fund_params __attribute__((weak));
+
+/* [F, inliersIndex, status] = vo_mex('fundamental', matchedPoints1, matchedPoints2, opts)
+ * matchedPoints M x 2 single or double; opts (optional) = [Method NumTrials DistanceThreshold Confidence]
+ * double, Method 0 = Norm8Point, 1 = MSAC.  Without the status output the two failures raise
+ * vision:estimateFundamentalMatrix:notEnoughPts / :notEnoughInliers, as the toolbox does; with it F is
+ * zeros(3) and inliersIndex all false. */
+static void cmd_fundamental(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs != 3 && nrhs != 4) need_args(nrhs, 3, "fundamental");
+    if (nlhs > 3) mexErrMsgIdAndTxt("vo:badArgument", "estimateFundamentalMatrix returns at most [F, inliersIndex, status]");
+    if (!vo_est_fundamental || !vo_default_fund_params)
+        mexErrMsgIdAndTxt("vo:estimateFundamentalMatrix:unavailable", "this libvo has no vo_est_fundamental: call the toolbox's "
+                          "estimateFundamentalMatrix, or link a newer libvo");
+    int n = 0, n2 = 0;
+    float* x1 = points_f32(prhs[1], 2, &n, "matchedPoints1");
+    float* x2 = points_f32(prhs[2], 2, &n2, "matchedPoints2");
+    if (n != n2) mexErrMsgIdAndTxt("vo:badArgument", "matchedPoints1 and matchedPoints2 differ in length");
+    vo_fund_params fp;
+    vo_default_fund_params(&fp);
+    if (nrhs == 4) {
+        need_real(prhs[3], mxDOUBLE_CLASS, 1, 4, "opts");
+        const double* o = mxGetDoubles(prhs[3]);
+        fp.method = (o[0] == 0.0 || o[0] == 1.0) ? (int32_t)o[0] : -1;                                          /* -1, 0: refused by libvo */
+        fp.num_trials = (o[1] >= 1.0 && o[1] <= 100000.0 && o[1] == (double)(int32_t)o[1]) ? (int32_t)o[1] : 0;
+        fp.distance_threshold = o[2];
+        fp.confidence = o[3];
+    }
+    need_ctx(0, 0);
+    double F[9];
+    uint8_t* inl = (uint8_t*)mxMalloc((size_t)n + 1);
+    memset(inl, 0, (size_t)n + 1);
+    const int rc = vo_est_fundamental(g_ctx, x1, x2, n, &fp, 0, F, inl, NULL);
+    mxFree(x1);
+    mxFree(x2);
+    if (rc == VO_ERR_TOO_FEW_POINTS || rc == VO_ERR_NO_CONSENSUS) {
+        if (nlhs < 3) {
+            mxFree(inl);
+            mexErrMsgIdAndTxt(rc == VO_ERR_TOO_FEW_POINTS ? "vision:estimateFundamentalMatrix:notEnoughPts"
+                                                          : "vision:estimateFundamentalMatrix:notEnoughInliers",
+                              "%s", vo_last_error(g_ctx));
+        }
+    } else if (rc != VO_OK) {
+        mxFree(inl);
+        check(rc);
+    }
+    plhs[0] = mxCreateDoubleMatrix(3, 3, mxREAL);
+    double* o = mxGetDoubles(plhs[0]);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) o[j * 3 + i] = F[3 * i + j];
+    if (nlhs > 1) {
+        plhs[1] = mxCreateLogicalMatrix(n, 1);
+        mxLogical* L = mxGetLogicals(plhs[1]);
+        for (int i = 0; i < n; ++i) L[i] = inl[i] != 0;
+    }
+    if (nlhs > 2) {
+        plhs[2] = mxCreateNumericMatrix(1, 1, mxINT32_CLASS, mxREAL);
+        *mxGetInt32s(plhs[2]) = rc == VO_OK ? 0 : (rc == VO_ERR_TOO_FEW_POINTS ? 1 : 2);
+    }
+    mxFree(inl);
+}
+
 /* CreateLandmarksFromFeatures(features_l, features_r, P1, P2, pose, ~) rows (:2-18): VO.m:145-158
  * has already filtered the points, so libvo's own filter runs against no old points (K = 0). */
 static void cmd_landmarks(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
@@ -800,6 +869,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "triangulate")) cmd_triangulate(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "refinepose")) cmd_refinepose(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "fundamental")) cmd_fundamental(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks")) cmd_landmarks(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step")) cmd_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks_all")) cmd_landmarks_all(nlhs, plhs, nrhs, prhs);

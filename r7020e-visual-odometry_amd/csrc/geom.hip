@@ -15,6 +15,10 @@
 //   bundleAdjustmentMotion (after VO.m:123-127, optional)  k_refine_pose: one wave per frame runs
 //       the Levenberg-Marquardt loop of vo_spec.h's vo_refine_* over the MSAC inliers and replaces
 //       the frame's pose.
+//   estimateFundamentalMatrix (after matchFeatures; vo_est_fundamental)  k_fund_msac: one block per
+//       problem, k_msac's lazy chunks over vo_spec.h's vo_fund_* -- normalised 8-point hypotheses whose
+//       9 x 9 Jacobi eigenproblems live in LDS, eight lanes per hypothesis; Sampson scores, the replay,
+//       the best slot's mask and the masked refit in the same launch.
 //   landmarks(VO.m:145-160, CreateLandmarksFromFeatures.m)  k_stereo_pos,
 //       k_lm_filter (any-x-or-y equality test, quirk Q3) + block compaction,
 //       k_lm_tri (odd rows, z gates).  (One fused block per frame measured
@@ -752,6 +756,279 @@ __global__ __launch_bounds__(64) void k_refine_pose(RefineArgs a)
 }
 
 // ---------------------------------------------------------------------------
+// estimateFundamentalMatrix (vo_est_fundamental; vo_spec.h vo_fund_*)
+// ---------------------------------------------------------------------------
+struct FundArgs {
+    const float* x1; const float* x2; const int* n; int stride;    // problem f: x1 + f * stride * 2, n[f] points
+    FundHyp* hyp; FundOut* out; uint8_t* inliers;                  // hyp [B][VO_FUND_CHUNK], inliers [B][stride]
+    int method, num_trials;
+    double thr, conf;
+    uint32_t seed, key0;
+};
+
+#define VO_FUND_T 512             // 8 waves, two per SIMD: 256 VGPRs each, which the solve needs to stay out of scratch
+#define VO_FUND_WAVES (VO_FUND_T / 64)
+#define VO_FUND_GROUP 8           // lanes that share one hypothesis' 9x9 Jacobi: 64 slots x 8 lanes = the block
+static_assert(VO_FUND_CHUNK == 64 && VO_FUND_CHUNK * VO_FUND_GROUP == VO_FUND_T, "one group of lanes per slot of the chunk");
+
+// vo_fund_jacobi at 9 x 9 by a group of 8 lanes of one wave, lane g of the group.  A rotation's 16
+// independent element pairs -- (a_kp, a_kq) for the 7 k outside {p, q}, (v_kp, v_kq) for the 9 rows --
+// are two per lane: lane g < 7 takes the A pair of the g-th such k and V's row g + 1, lane 7 V's rows
+// 0 and 8; lane 0 also writes a_pp, a_qq, a_pq.  Every lane evaluates vo_fund_rot on the same three
+// values, so the skip and the sweep count are uniform in the group, and each element goes through
+// vo_fund_rot_xy exactly as in the serial loop: the bits are vo_fund_jacobi's.  The group's lanes run
+// in lockstep (one wave, the same control flow) and the LDS serves a wave's accesses in program order:
+// within a rotation every load is issued before the first store, and no two lanes touch one element,
+// so no barrier is needed; the accesses are volatile so that none is kept in a register or moved
+// across another.  Ap, Vp: column i of the element-major block (stride VO_FUND_CHUNK).
+typedef volatile __attribute__((address_space(3))) double lds_vf64;
+__device__ __forceinline__ int fund_jacobi9_group(double* Ap, double* Vp, int g)
+{
+    lds_vf64* A = (lds_vf64*)Ap;                          // (named LDS: volatile accesses through a generic pointer stay flat)
+    lds_vf64* V = (lds_vf64*)Vp;
+    constexpr int n = 9, S = VO_FUND_CHUNK;
+    for (int e = g; e < n * n; e += VO_FUND_GROUP) V[e * S] = (e / n == e % n) ? 1.0 : 0.0;
+    for (int sweeps = 0; sweeps < VO_FUND_SWEEP_CAP; ++sweeps) {
+        int rotated = 0;
+        for (int p = 0; p < n - 1; ++p) {
+            for (int q = p + 1; q < n; ++q) {
+                const int ipp = vo_fund_tri(n, p, p) * S, iqq = vo_fund_tri(n, q, q) * S, ipq = vo_fund_tri(n, p, q) * S;
+                const double apq = A[ipq], app = A[ipp], aqq = A[iqq];
+                double t, c, s;
+                if (vo_fund_rot(app, aqq, apq, &t, &c, &s)) continue;
+                rotated = 1;
+                int i0, i1;                                   // the lane's first pair
+                if (g < 7) {
+                    int k = g;
+                    if (k >= p) ++k;
+                    if (k >= q) ++k;
+                    i0 = (k < p ? vo_fund_tri(n, k, p) : vo_fund_tri(n, p, k)) * S;
+                    i1 = (k < q ? vo_fund_tri(n, k, q) : vo_fund_tri(n, q, k)) * S;
+                } else {
+                    i0 = p * S;                               // V's row 0
+                    i1 = q * S;
+                }
+                lds_vf64* B = g < 7 ? A : V;
+                const int r = g < 7 ? g + 1 : 8;              // ... and V's row r as the second
+                const int j0 = (r * n + p) * S, j1 = (r * n + q) * S;
+                double x0 = B[i0], y0 = B[i1], x1 = V[j0], y1 = V[j1];
+                vo_fund_rot_xy(c, s, &x0, &y0);
+                vo_fund_rot_xy(c, s, &x1, &y1);
+                B[i0] = x0; B[i1] = y0;
+                V[j0] = x1; V[j1] = y1;
+                if (g == 0) {
+                    A[ipp] = app - t * apq;
+                    A[iqq] = aqq + t * apq;
+                    A[ipq] = 0.0;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    return vo_fund_argmin_diag(Ap, n, S);
+}
+
+// The solve of one column of W by its group: the 9 x 9 Jacobi by all lanes of the group, the rest
+// (vo_fund_solve_tail: rank 2 with the serial 3 x 3 Jacobi, denormalisation) by the group's lane 0,
+// which holds N1, N2 and gets F.  Called by whole waves; `member`: the lane's group has a slot,
+// `ok` (uniform in the group): the slot has a design matrix.  -> the model flag, valid in lane 0.
+__device__ __forceinline__ int fund_solve_group(double* W, int g, int member, int ok, const double* N1, const double* N2, double* F)
+{
+    int j9 = 0;
+    if (member && ok) j9 = fund_jacobi9_group(W, W + VO_FUND_NSUM * VO_FUND_CHUNK, g);
+    int res = 0;
+    if (member && ok && g == 0) res = vo_fund_solve_tail(W, VO_FUND_CHUNK, j9, N1, N2, F, nullptr);
+    return res;
+}
+
+// slot `slot` of the problem, as the chunk's slot i, by the group of 8 lanes tid / 8 == i: lane 0 of
+// the group draws the sample and sums the design matrix into column i of the element-major LDS
+// block W (element e at W[e * 64 + i]), the group solves it, lane 0 stores F.  Called by whole waves.
+__device__ __forceinline__ void fund_hyp_slot(const FundArgs& a, const float* x1, const float* x2, int n, uint32_t key, int slot,
+                                              int i, int member, int lane, double* W, FundHyp* hyp)
+{
+    const int g = lane & (VO_FUND_GROUP - 1);
+    double N1[3], N2[3], F[9];
+    int ok = 0;
+    if (member && g == 0) {
+        uint32_t idx[VO_FUND_SAMPLE];
+        ok = vo_fund_sample(a.seed, key, (uint32_t)slot, (uint32_t)n, idx, nullptr);
+        if (ok) ok = vo_fund_fit_sample(x1, x2, idx, N1, N2, W + i, VO_FUND_CHUNK);
+    }
+    ok = __shfl(ok, lane & ~(VO_FUND_GROUP - 1));
+    ok = fund_solve_group(W + i, g, member, ok, N1, N2, F);
+    if (member && g == 0) {
+        FundHyp* h = hyp + i;
+        h->valid = ok;
+        if (ok) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) h->F[q] = F[q];
+        }
+    }
+}
+
+// MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed shuffle tree (msac_score_slot)
+__device__ __forceinline__ void fund_score_slot(FundHyp* h, const float* x1, const float* x2, int n, double thr, int lane)
+{
+    double F[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) F[q] = h->F[q];
+    double part = 0.0;
+    int cnt = 0;
+    for (int k = lane; k < n; k += VO_FUND_LANES) {
+        const float2 p1 = ((const float2*)x1)[k], p2 = ((const float2*)x2)[k];
+        double e = vo_fund_sampson(F, (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y);
+        if (e < thr) cnt++;
+        part = part + (e < thr ? e : thr);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        part = part + __shfl_down(part, off);
+        cnt += __shfl_xor(cnt, off);
+    }
+    if (lane == 0) { h->score = part; h->n_in = cnt; }
+}
+
+__device__ __forceinline__ double fund_wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);      // the tree's p[0] in every lane (refine_pass)
+    return v;
+}
+
+// The masked Norm8 fit by one wave: lane l is partial l of the three passes; the 45 sums of the last
+// pass accumulate in LDS (column l of W), are joined through registers and land in column 0, which
+// the wave's first group solves.  -> 1 and F (valid in lane 0), or 0, wave-uniform.
+__device__ __forceinline__ int fund_refit(const float* x1, const float* x2, const uint8_t* mask, int n, int lane, double* W, double* F)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int m = 0;
+    for (int k = lane; k < n; k += VO_FUND_LANES) {
+        if (!mask[k]) continue;
+        const float2 p1 = ((const float2*)x1)[k], p2 = ((const float2*)x2)[k];
+        ++m;
+        s0 = s0 + (double)p1.x; s1 = s1 + (double)p1.y; s2 = s2 + (double)p2.x; s3 = s3 + (double)p2.y;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m += __shfl_xor(m, off);
+    s0 = fund_wave_sum(s0); s1 = fund_wave_sum(s1); s2 = fund_wave_sum(s2); s3 = fund_wave_sum(s3);
+    double N1[3], N2[3];
+    N1[1] = s0 / (double)m; N1[2] = s1 / (double)m; N2[1] = s2 / (double)m; N2[2] = s3 / (double)m;
+    double d1 = 0.0, d2 = 0.0;
+    for (int k = lane; k < n; k += VO_FUND_LANES) {
+        if (!mask[k]) continue;
+        const float2 p1 = ((const float2*)x1)[k], p2 = ((const float2*)x2)[k];
+        d1 = d1 + vo_fund_dist((double)p1.x, (double)p1.y, N1[1], N1[2]);
+        d2 = d2 + vo_fund_dist((double)p2.x, (double)p2.y, N2[1], N2[2]);
+    }
+    d1 = fund_wave_sum(d1); d2 = fund_wave_sum(d2);
+    N1[0] = VO_FUND_SQRT2 / (d1 / (double)m);
+    N2[0] = VO_FUND_SQRT2 / (d2 / (double)m);
+    if (!vo_fund_finite(N1[0]) || !vo_fund_finite(N2[0])) return 0;            // wave-uniform: the sums are
+    for (int q = 0; q < VO_FUND_NSUM; ++q) W[q * VO_FUND_CHUNK + lane] = 0.0;
+    for (int k = lane; k < n; k += VO_FUND_LANES) {
+        if (!mask[k]) continue;
+        const float2 p1 = ((const float2*)x1)[k], p2 = ((const float2*)x2)[k];
+        vo_fund_row(N1, N2, (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y, W + lane, VO_FUND_CHUNK);
+    }
+    for (int q = 0; q < VO_FUND_NSUM; ++q) {
+        const double v = fund_wave_sum(W[q * VO_FUND_CHUNK + lane]);
+        if (lane == 0) W[q * VO_FUND_CHUNK] = v;
+    }
+    const int ok = fund_solve_group(W, lane & (VO_FUND_GROUP - 1), lane < VO_FUND_GROUP, 1, N1, N2, F);   // lanes 0 .. 7 on column 0
+    return __shfl(ok, 0);
+}
+
+// One 512-thread block per problem, k_msac's lazy chunks: generate the chunk's 64 hypotheses (a
+// group of 8 lanes each, so every lane of the block works on the Jacobi solves: fund_jacobi9_group),
+// score the valid ones (wave per slot), replay the sequential loop over the chunk (thread 0), stop at
+// the chunk where the replay stops; then the best slot's mask and the masked refit (wave 0) in the
+// same launch.  Only the chunk's slots and the best F so far are kept: memory per problem does not
+// grow with num_trials.  The 9x9 eigenproblem's 45 + 81 doubles per hypothesis live in LDS,
+// element-major across the chunk (63 KiB), addressed with runtime indices there instead of in scratch.
+__global__ __launch_bounds__(VO_FUND_T) void k_fund_msac(FundArgs a)
+{
+    __shared__ double s_w[VO_FUND_NWORK * VO_FUND_CHUNK];
+    __shared__ double s_F[9];
+    __shared__ int s_done, s_status;
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int n = a.n[f];
+    n = n < 0 ? 0 : (n > a.stride ? a.stride : n);
+    const float* x1 = a.x1 + (size_t)f * a.stride * 2;
+    const float* x2 = a.x2 + (size_t)f * a.stride * 2;
+    FundHyp* hyp = a.hyp + (size_t)f * VO_FUND_CHUNK;
+    FundOut* out = a.out + f;
+    uint8_t* mask = a.inliers + (size_t)f * a.stride;
+    const uint32_t key = a.key0 + (uint32_t)f;
+    int status = n < VO_FUND_SAMPLE ? VO_ERR_TOO_FEW_POINTS : VO_OK;
+    if (status == VO_OK && a.method == VO_FUND_MSAC) {
+        vo_fund_replay r;                                   // thread 0's
+        vo_fund_replay_begin(&r, a.num_trials);
+        if (tid == 0) s_done = 0;
+        __syncthreads();
+        for (int c0 = 0; c0 < a.num_trials && !s_done; c0 += VO_FUND_CHUNK) {
+            const int cn = min(VO_FUND_CHUNK, a.num_trials - c0);
+            const int i = tid / VO_FUND_GROUP;
+            fund_hyp_slot(a, x1, x2, n, key, c0 + i, i, i < cn, lane, s_w, hyp);
+            __syncthreads();                                    // the chunk's slots are written
+            for (int s = wv; s < cn; s += VO_FUND_WAVES)
+                if (hyp[s].valid) fund_score_slot(hyp + s, x1, x2, n, a.thr, lane);
+            __syncthreads();                                    // ... and scored
+            if (tid == 0) {
+                for (int s = 0; s < cn && !vo_fund_replay_done(&r); ++s) {
+                    const FundHyp* h = hyp + s;
+                    if (vo_fund_replay_slot(&r, c0 + s, h->valid, h->score, h->n_in, n, a.conf)) {
+#pragma unroll
+                        for (int q = 0; q < 9; ++q) s_F[q] = h->F[q];
+                    }
+                }
+                s_done = vo_fund_replay_done(&r);
+            }
+            __syncthreads();
+        }
+        if (tid == 0) s_status = (r.best < 0 || r.best_in < VO_FUND_SAMPLE) ? VO_ERR_NO_CONSENSUS : VO_OK;
+        __syncthreads();
+        status = s_status;
+    }
+    if (status == VO_OK) {                                  // the mask the refit runs over
+        double F[9];
+        if (a.method == VO_FUND_MSAC) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) F[q] = s_F[q];
+        }
+        for (int k = tid; k < n; k += VO_FUND_T) {
+            int in = 1;
+            if (a.method == VO_FUND_MSAC) {
+                const float2 p1 = ((const float2*)x1)[k], p2 = ((const float2*)x2)[k];
+                in = vo_fund_sampson(F, (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y) < a.thr;
+            }
+            mask[k] = (uint8_t)in;
+        }
+        __syncthreads();                                    // the mask is written (status is block-uniform)
+    }
+    if (wv) return;
+    double F[9];
+    int cnt = 0;
+    if (status == VO_OK) {
+        for (int k = lane; k < n; k += VO_FUND_LANES) cnt += mask[k];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+        if (!fund_refit(x1, x2, mask, n, lane, s_w, F)) status = VO_ERR_NO_CONSENSUS;
+    }
+    if (status != VO_OK) {
+        cnt = 0;
+        for (int k = lane; k < n; k += VO_FUND_LANES) mask[k] = 0;
+    }
+    for (int k = n + lane; k < a.stride; k += VO_FUND_LANES) mask[k] = 0;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) out->F[q] = status == VO_OK ? F[q] : 0.0;
+        out->status = status;
+        out->n_inliers = cnt;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // landmarks
 // ---------------------------------------------------------------------------
 // stereo subset positions of frame f (VO.m:141-142): spos[f][j] = (lx, ly, rx, ry)
@@ -1042,6 +1319,36 @@ void refine_launch(GeomBuffers& g, const double* img, const double* world, const
     a.p = p;
     memcpy(a.K, K, sizeof(a.K));
     VO_LAUNCH(k_refine_pose, dim3(frames), dim3(64), 0, s, a);
+}
+
+hipError_t fund_reserve(DevPool& pool, FundBuffers& fb, int B, int pts_stride)
+{
+    const size_t pts = (size_t)B * pts_stride;
+    if (pts > fb.cap_pts) {
+        const int e = pool.grow({DevPool::req(fb.x1, 2 * pts), DevPool::req(fb.x2, 2 * pts), DevPool::req(fb.inliers, pts)});
+        if (e) return (hipError_t)e;
+        fb.cap_pts = pts;
+    }
+    if (B > fb.cap_B) {
+        const int e = pool.grow({DevPool::req(fb.n, (size_t)B), DevPool::req(fb.hyp, (size_t)B * VO_FUND_CHUNK),
+                                 DevPool::req(fb.out, (size_t)B)});
+        if (e) return (hipError_t)e;
+        fb.cap_B = B;
+    }
+    return hipSuccess;
+}
+
+void fund_launch(FundBuffers& fb, int B, int pts_stride, const vo_fund_params& p, uint32_t key0, hipStream_t s)
+{
+    if (B <= 0) return;
+    FundArgs a;
+    a.x1 = fb.x1; a.x2 = fb.x2; a.n = fb.n; a.stride = pts_stride;
+    a.hyp = fb.hyp; a.out = fb.out; a.inliers = fb.inliers;
+    a.method = p.method; a.num_trials = p.num_trials;
+    a.thr = p.distance_threshold;
+    a.conf = p.confidence / 100.0;
+    a.seed = p.seed; a.key0 = key0;
+    VO_LAUNCH(k_fund_msac, dim3(B), dim3(VO_FUND_T), 0, s, a);
 }
 
 void landmarks_launch(GeomBuffers& g, const int* kn, const vo_calib& c, hipStream_t s)

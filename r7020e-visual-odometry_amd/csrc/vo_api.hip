@@ -162,6 +162,7 @@ struct vo_ctx {
     int* d_fres = nullptr;
     MatchExBuffers mx;               // vo_match_ex / vo_match_f32_ex (allocated on first use)
     MatchRadiusBuffers mr;           // vo_match_radius / vo_match_radius_f32 (allocated on first use)
+    FundBuffers fund;                // vo_est_fundamental / vo_est_fundamental_batch (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
@@ -239,6 +240,10 @@ void vo_default_ransac_params(vo_ransac_params* p)
 void vo_default_refine_params(vo_refine_params* p)
 {
     p->max_iterations = 20; p->relative_tolerance = 1e-9; p->absolute_tolerance = 0.0; p->lambda0 = 1e-3;
+}
+void vo_default_fund_params(vo_fund_params* p)
+{
+    p->method = VO_FUND_MSAC; p->num_trials = 500; p->distance_threshold = 0.01; p->confidence = 99.0; p->seed = 0x5EED;
 }
 
 const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -2070,6 +2075,86 @@ int vo_fetch_pose_refinement(vo_ctx* c, int frame, vo_refine_stats* out)
         return fail(c, VO_ERR_STATE, "vo_fetch_pose_refinement: the batch ran without pose refinement (vo_set_pose_refinement)");
     HIPC(c, hipMemcpy(out, S.gb.refine + frame, sizeof(*out), hipMemcpyDeviceToHost));
     return VO_OK;
+}
+
+// -> nullptr when the block is inside the ranges of include/vo.h, else the offending field
+static const char* fund_params_refusal(const vo_fund_params& p)
+{
+    if (p.method != VO_FUND_NORM8 && p.method != VO_FUND_MSAC) return "method (VO_FUND_NORM8 or VO_FUND_MSAC)";
+    if (p.num_trials < 1 || p.num_trials > 100000) return "num_trials";
+    if (!(p.distance_threshold > 0.0 && p.distance_threshold - p.distance_threshold == 0.0)) return "distance_threshold";
+    if (!(p.confidence > 0.0 && p.confidence < 100.0)) return "confidence";
+    return nullptr;
+}
+
+int vo_est_fundamental_batch(vo_ctx* c, const float* x1, const float* x2, int pts_stride, const int32_t* n_pts, int B,
+                             const vo_fund_params* params, uint32_t key0, double* F, uint8_t* inliers, int32_t* n_inliers,
+                             int32_t* status)
+{
+    const char* who = "vo_est_fundamental";
+    if (!c || B < 0 || pts_stride < 0 || (B && (!n_pts || !F || !status))) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    if (B > c->max_batch) return fail(c, VO_ERR_CAPACITY, "%s: %d problems exceed max_batch %d", who, B, c->max_batch);
+    if (pts_stride > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "%s: %d points exceed max_keypoints", who, pts_stride);
+    vo_fund_params p;
+    if (params) p = *params; else vo_default_fund_params(&p);
+    if (const char* field = fund_params_refusal(p)) return fail(c, VO_ERR_ARG, "%s: parameter out of range: %s", who, field);
+    bool any = false;
+    for (int f = 0; f < B; ++f) {
+        const int n = n_pts[f];
+        if (n < 0 || n > pts_stride) return fail(c, VO_ERR_ARG, "%s: n_pts[%d] = %d is outside 0 .. pts_stride", who, f, n);
+        if (n && (!x1 || !x2)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+        for (int side = 0; side < 2; ++side) {
+            const float* x = (side ? x2 : x1) + (size_t)f * pts_stride * 2;
+            for (long e = 0; e < 2L * n; ++e)
+                if (!std::isfinite(x[e]))
+                    return fail(c, VO_ERR_ARG, "%s: matchedPoints%d(%ld, %ld) of problem %d is not finite (point index %ld)", who,
+                                side + 1, e / 2 + 1, e % 2 + 1, f, e / 2);
+        }
+        any = any || n >= VO_FUND_SAMPLE;
+    }
+    CallScope call(c); if (call.status) return call.status;
+    for (int f = 0; f < B; ++f) {                           // what a problem with n < 8 gives; the rest is overwritten
+        for (int q = 0; q < 9; ++q) F[9 * (size_t)f + q] = 0.0;
+        status[f] = VO_ERR_TOO_FEW_POINTS;
+        if (n_inliers) n_inliers[f] = 0;
+    }
+    if (inliers && B) memset(inliers, 0, (size_t)B * pts_stride);
+    if (!any) return VO_OK;                                 // nothing to launch
+    FundBuffers& fb = c->fund;
+    {
+        const hipError_t e = fund_reserve(c->pool, fb, B, pts_stride);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t pts = (size_t)B * pts_stride;
+    HIPC(c, hipMemcpyAsync(fb.x1, x1, sizeof(float) * 2 * pts, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(fb.x2, x2, sizeof(float) * 2 * pts, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(fb.n, n_pts, sizeof(int) * B, hipMemcpyHostToDevice, c->stream));
+    fund_launch(fb, B, pts_stride, p, key0, c->stream);
+    std::vector<FundOut> out((size_t)B);
+    HIPC(c, hipMemcpyAsync(out.data(), fb.out, sizeof(FundOut) * B, hipMemcpyDeviceToHost, c->stream));
+    if (inliers) HIPC(c, hipMemcpyAsync(inliers, fb.inliers, pts, hipMemcpyDeviceToHost, c->stream));
+    int rc = finish(c);
+    if (rc) return rc;
+    for (int f = 0; f < B; ++f) {
+        memcpy(F + 9 * (size_t)f, out[f].F, sizeof(double) * 9);
+        status[f] = out[f].status;
+        if (n_inliers) n_inliers[f] = out[f].n_inliers;
+    }
+    return VO_OK;
+}
+
+int vo_est_fundamental(vo_ctx* c, const float* x1, const float* x2, int n, const vo_fund_params* params, uint32_t key,
+                       double F[9], uint8_t* inliers, int* n_inliers)
+{
+    if (!c || n < 0 || !F) return fail(c, VO_ERR_ARG, "vo_est_fundamental: bad arguments");
+    if (n > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_est_fundamental: %d points exceed max_keypoints", n);
+    int32_t n32 = n, nin = 0, st = VO_OK;
+    int rc = vo_est_fundamental_batch(c, x1, x2, n, &n32, 1, params, key, F, inliers, &nin, &st);
+    if (n_inliers) *n_inliers = nin;
+    if (rc) return rc;
+    if (st == VO_ERR_TOO_FEW_POINTS) return fail(c, st, "estimateFundamentalMatrix: need at least 8 points, got %d", n);
+    if (st == VO_ERR_NO_CONSENSUS) return fail(c, st, "estimateFundamentalMatrix: no consensus (no model with >= 8 inliers)");
+    return st;
 }
 
 int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const float* old_l, const float* old_r, int Kn,

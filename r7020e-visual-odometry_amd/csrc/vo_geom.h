@@ -117,6 +117,25 @@ void estworldpose_launch(GeomBuffers& g, const double* img, const double* world,
 // whose g.fg[f].status is not VO_OK are left alone (stats: TOO_FEW, n_used 0, passes 0).
 void refine_launch(GeomBuffers& g, const double* img, const double* world, const uint8_t* use, const int* n, int n_stride,
                    const double K[9], const vo_refine_params& p, int frames, int need_ok, hipStream_t s);
+// estimateFundamentalMatrix (vo_est_fundamental / vo_est_fundamental_batch): buffers of their own,
+// allocated by fund_reserve at the first call and grown to the largest B x pts_stride seen, so the
+// loop's buffer sets are never touched.
+#define VO_FUND_CHUNK 64           // hypothesis slots per chunk of k_fund_msac
+struct FundHyp { double F[9]; double score; int valid; int n_in; };
+struct FundOut { double F[9]; int status; int n_inliers; };
+struct FundBuffers {
+    size_t cap_pts = 0; int cap_B = 0;
+    float* x1 = nullptr; float* x2 = nullptr;     // [B][pts_stride][2]
+    uint8_t* inliers = nullptr;                   // [B][pts_stride]
+    int* n = nullptr;                             // [B]
+    FundHyp* hyp = nullptr;                       // [B][VO_FUND_CHUNK]: the current chunk's slots
+    FundOut* out = nullptr;                       // [B]
+};
+hipError_t fund_reserve(DevPool& pool, FundBuffers& fb, int B, int pts_stride);   // all or nothing
+// k_fund_msac, one block per problem: problem f has fb.n[f] points at fb.x1 / fb.x2 + f * pts_stride * 2
+// and the Philox key key0 + f; results in fb.out[f] and fb.inliers + f * pts_stride.
+void fund_launch(FundBuffers& fb, int B, int pts_stride, const vo_fund_params& p, uint32_t key0, hipStream_t s);
+
 // landmark filter + CreateLandmarksFromFeatures on g.spos/g.s_n (frame 0) vs
 // g.oldpos with *kn old rows.
 void landmarks_launch(GeomBuffers& g, const int* kn, const vo_calib& c, hipStream_t s);

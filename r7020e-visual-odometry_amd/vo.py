@@ -12,6 +12,7 @@ running on the MI355X through libvo.so:
     triangulate                            VO.m:113-116
     estworldpose                           VO.m:123-127
     bundleAdjustmentMotion                 after VO.m:123-127 (refine_pose, set_pose_refinement)
+    estimateFundamentalMatrix              after matchFeatures (est_fundamental, est_fundamental_batch)
     CreateLandmarksFromFeatures           CreateLandmarksFromFeatures.m:1-21
     VisualOdometry.step                    the VO.m loop body (VO.m:70-161)
 
@@ -72,6 +73,13 @@ class RefineParams(C.Structure):
                 ("absolute_tolerance", C.c_double), ("lambda0", C.c_double)]
 
 
+class FundParams(C.Structure):
+    """vo_fund_params: estimateFundamentalMatrix's Method (VO_FUND_NORM8 / VO_FUND_MSAC), NumTrials,
+    DistanceThreshold (px^2), Confidence (percent) and the Philox seed."""
+    _fields_ = [("method", C.c_int32), ("num_trials", C.c_int32), ("distance_threshold", C.c_double),
+                ("confidence", C.c_double), ("seed", C.c_uint32)]
+
+
 class RefineStats(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("passes", C.c_int32), ("accepted", C.c_int32),
                 ("cost_initial", C.c_double), ("cost_final", C.c_double)]
@@ -113,6 +121,11 @@ REFINE_STATS_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("passes", 
 # vo_refine_stats.status
 VO_REFINE_CONVERGED, VO_REFINE_MAX_ITER, VO_REFINE_DAMPING, VO_REFINE_DEGENERATE, VO_REFINE_TOO_FEW = 0, 1, 2, -1, -3
 
+# vo_fund_params.method
+VO_FUND_NORM8, VO_FUND_MSAC = 0, 1
+FUND_METHODS = {"Norm8Point": VO_FUND_NORM8, "MSAC": VO_FUND_MSAC}
+FUND_MAX_TRIALS = 100000
+
 # exported symbols (tests check the library exports every one)
 EXPORTS = [
     "vo_default_sift_params", "vo_default_match_params", "vo_default_ransac_params", "vo_create", "vo_destroy",
@@ -130,6 +143,7 @@ EXPORTS = [
     "vo_triangulate_ex", "vo_fetch_track_quality",
     "vo_default_refine_params", "vo_refine_pose", "vo_set_pose_refinement", "vo_fetch_pose_refinement",
     "vo_match_radius", "vo_match_radius_f32",
+    "vo_default_fund_params", "vo_est_fundamental", "vo_est_fundamental_batch",
 ]
 
 _libs: dict = {}
@@ -209,6 +223,13 @@ def load_library(path: str | os.PathLike | None = None):
                                      P(RefineParams), P(C.c_double), P(RefineStats)]
         L.vo_set_pose_refinement.argtypes = [vp, P(RefineParams)]
         L.vo_fetch_pose_refinement.argtypes = [vp, C.c_int, P(RefineStats)]
+    if hasattr(L, "vo_est_fundamental"):     # (absent from an older library timed beside this one)
+        L.vo_default_fund_params.argtypes = [P(FundParams)]
+        L.vo_default_fund_params.restype = None
+        L.vo_est_fundamental.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(FundParams), C.c_uint32, P(C.c_double),
+                                         P(C.c_uint8), P(C.c_int)]
+        L.vo_est_fundamental_batch.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_int32), C.c_int, P(FundParams),
+                                               C.c_uint32, P(C.c_double), P(C.c_uint8), P(C.c_int32), P(C.c_int32)]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
                                P(C.c_double), P(C.c_double), C.c_int, P(C.c_int)]
     L.vo_step.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(StepOut)]
@@ -309,6 +330,56 @@ def default_refine_params(**overrides) -> RefineParams:
             raise VOError(VO_ERR_ARG, f"default_refine_params: no field {k}")
         setattr(p, k, v)
     return p
+
+
+def default_fund_params(**overrides) -> FundParams:
+    """vo_default_fund_params (MSAC, 500 trials, DistanceThreshold 0.01 px^2, Confidence 99 %, seed
+    0x5EED), with any field overridden by keyword.  Host only: no library, no device."""
+    p = FundParams(VO_FUND_MSAC, 500, 0.01, 99.0, 0x5EED)
+    for k, v in overrides.items():
+        if k not in dict(FundParams._fields_):
+            raise VOError(VO_ERR_ARG, f"default_fund_params: no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def check_fund_params(p: FundParams) -> None:
+    """vo_est_fundamental's parameter ranges (include/vo.h), checked on the host: VOError(VO_ERR_ARG)
+    naming the offending field."""
+    bad = None
+    if p.method not in (VO_FUND_NORM8, VO_FUND_MSAC):
+        bad = "method (VO_FUND_NORM8 or VO_FUND_MSAC; RANSAC, LMedS and LTS are not implemented)"
+    elif not 1 <= p.num_trials <= FUND_MAX_TRIALS:
+        bad = "num_trials"
+    elif not (np.isfinite(p.distance_threshold) and p.distance_threshold > 0.0):
+        bad = "distance_threshold"
+    elif not 0.0 < p.confidence < 100.0:
+        bad = "confidence"
+    if bad:
+        raise VOError(VO_ERR_ARG, f"est_fundamental: parameter out of range: {bad}")
+
+
+def fund_points(matchedPoints1, matchedPoints2, who: str = "est_fundamental"):
+    """The two point lists as [n][2] float32 (n x 2 arrays, or keypoint arrays with fields x, y), checked
+    on the host: equal lengths and finite coordinates, else VOError(VO_ERR_ARG) naming the first
+    offending row."""
+    out = []
+    for k, pts in enumerate((matchedPoints1, matchedPoints2)):
+        a = np.asarray(pts)
+        if a.dtype.names and "x" in a.dtype.names:
+            a = np.stack([a["x"], a["y"]], 1)
+        if a.size == 0:
+            a = np.zeros((0, 2), np.float32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise VOError(VO_ERR_ARG, f"{who}: matchedPoints{k + 1} must be n x 2")
+        a = np.ascontiguousarray(a, np.float32)
+        bad = np.flatnonzero(~np.isfinite(a).all(1))
+        if len(bad):
+            raise VOError(VO_ERR_ARG, f"{who}: matchedPoints{k + 1} row {int(bad[0])} is not finite")
+        out.append(a)
+    if len(out[0]) != len(out[1]):
+        raise VOError(VO_ERR_ARG, f"{who}: matchedPoints1 and matchedPoints2 differ in length")
+    return out[0], out[1]
 
 
 def _refine_stats(s: RefineStats) -> np.ndarray:
@@ -773,6 +844,51 @@ class Context:
         self._check(self.lib.vo_fetch_pose_refinement(self.h, frame, C.byref(st)))
         return _refine_stats(st)
 
+    # ---- estimateFundamentalMatrix ----
+    def est_fundamental(self, matchedPoints1, matchedPoints2, params: FundParams | None = None, key: int = 0,
+                        raise_on_failure: bool = False):
+        """[F, inliersIndex, status] = estimateFundamentalMatrix(matchedPoints1, matchedPoints2, ...)
+        (vo_est_fundamental) -> (status, F 3x3 with [x2 1] F [x1 1]' = 0, inlier mask [n] bool, n_inliers).
+        status is VO_OK, VO_ERR_TOO_FEW_POINTS (n < 8) or VO_ERR_NO_CONSENSUS (F and the mask are then 0);
+        with raise_on_failure the last two raise, as the toolbox does when status is not requested."""
+        x1, x2 = fund_points(matchedPoints1, matchedPoints2)
+        p = params if params is not None else default_fund_params()
+        check_fund_params(p)
+        n = len(x1)
+        F = np.zeros(9)
+        inl = np.zeros(max(n, 1), np.uint8)
+        nin = C.c_int(0)
+        rc = self.lib.vo_est_fundamental(self.h, _p(x1, C.c_float), _p(x2, C.c_float), n, C.byref(p), int(key) & 0xFFFFFFFF,
+                                         _p(F, C.c_double), _p(inl, C.c_uint8), C.byref(nin))
+        self._check(rc, allow=() if raise_on_failure else (VO_ERR_TOO_FEW_POINTS, VO_ERR_NO_CONSENSUS))
+        return rc, F.reshape(3, 3), inl[:n].astype(bool), nin.value
+
+    def est_fundamental_batch(self, x1, x2, n_pts, params: FundParams | None = None, key0: int = 0):
+        """B problems in one launch (vo_est_fundamental_batch): x1, x2 [B][pts_stride][2] float32, problem f
+        uses its first n_pts[f] rows and the key key0 + f -> (status [B], F [B, 3, 3], inliers
+        [B, pts_stride] bool, n_inliers [B])."""
+        x1 = np.ascontiguousarray(x1, np.float32)
+        x2 = np.ascontiguousarray(x2, np.float32)
+        n_pts = np.ascontiguousarray(n_pts, np.int32).reshape(-1)
+        B = len(n_pts)
+        if x1.shape != x2.shape or x1.ndim != 3 or x1.shape[0] != B or x1.shape[2] != 2:
+            raise VOError(VO_ERR_ARG, "est_fundamental_batch: x1 and x2 must both be [B][pts_stride][2]")
+        stride = x1.shape[1]
+        for f in range(B):
+            if not 0 <= n_pts[f] <= stride:
+                raise VOError(VO_ERR_ARG, f"est_fundamental_batch: n_pts[{f}] is outside 0 .. pts_stride")
+            fund_points(x1[f, :n_pts[f]], x2[f, :n_pts[f]], f"est_fundamental_batch: problem {f}")
+        p = params if params is not None else default_fund_params()
+        check_fund_params(p)
+        F = np.zeros((max(B, 1), 9))
+        inl = np.zeros((max(B, 1), max(stride, 1)), np.uint8)
+        nin = np.zeros(max(B, 1), np.int32)
+        st = np.zeros(max(B, 1), np.int32)
+        self._check(self.lib.vo_est_fundamental_batch(self.h, _p(x1, C.c_float), _p(x2, C.c_float), stride, _p(n_pts, C.c_int32), B,
+                                                      C.byref(p), int(key0) & 0xFFFFFFFF, _p(F, C.c_double), _p(inl, C.c_uint8),
+                                                      _p(nin, C.c_int32), _p(st, C.c_int32)))
+        return st[:B], F[:B].reshape(B, 3, 3), inl[:B, :stride].astype(bool), nin[:B]
+
     # ---- new-landmark filter + CreateLandmarksFromFeatures ----
     def landmarks(self, l_pos, r_pos, old_l, old_r, pose) -> np.ndarray:
         a = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (l_pos, r_pos, old_l, old_r)]
@@ -1048,3 +1164,23 @@ def matchFeaturesInRadius(features1: np.ndarray, features2: np.ndarray, points2,
     return _default_ctx(375, 1242).match_in_radius(features1, features2, p2, centerPoints, radius, unique=unique,
                                                    match_threshold=match_threshold, max_ratio=max_ratio,
                                                    return_metric=return_metric)
+
+
+def estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method: str = "MSAC", NumTrials: int = 500,
+                              DistanceThreshold: float = 0.01, Confidence: float = 99.0, key: int = 0, **other):
+    """[F, inliersIndex, status] = estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method=...,
+    NumTrials=..., DistanceThreshold=..., Confidence=...) -> (F 3x3, inliersIndex [n] bool, status).
+    Method "MSAC" or "Norm8Point"; "RANSAC", "LMedS", "LTS", DistanceType "Algebraic" and every other
+    option are not implemented: VOError(VO_ERR_ARG).  status follows the toolbox: 0, 1 (fewer than 8
+    points), 2 (not enough inliers); F is then zero."""
+    if other.get("DistanceType", "Sampson") != "Sampson" or set(other) - {"DistanceType"}:
+        raise VOError(VO_ERR_ARG, "estimateFundamentalMatrix: only Method, NumTrials, DistanceThreshold, Confidence and "
+                                  "DistanceType 'Sampson' are implemented")
+    if Method not in FUND_METHODS:
+        raise VOError(VO_ERR_ARG, f"estimateFundamentalMatrix: Method {Method!r} is not implemented (MSAC, Norm8Point)")
+    x1, x2 = fund_points(matchedPoints1, matchedPoints2, "estimateFundamentalMatrix")
+    p = default_fund_params(method=FUND_METHODS[Method], num_trials=int(NumTrials), distance_threshold=float(DistanceThreshold),
+                            confidence=float(Confidence))
+    check_fund_params(p)
+    rc, F, inl, _ = _default_ctx(375, 1242).est_fundamental(x1, x2, p, key)
+    return F, inl, {VO_OK: 0, VO_ERR_TOO_FEW_POINTS: 1, VO_ERR_NO_CONSENSUS: 2}[rc]
