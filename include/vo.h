@@ -39,6 +39,8 @@
  *   vo_fetch_pose_refinement call, and as an optional stage of the loop body
  *   vo_est_fundamental /   estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method = "MSAC" |
  *   vo_est_fundamental_batch "Norm8Point"): the epipolar check of 2-D/2-D matches after matchFeatures
+ *   vo_track_points /      vision.PointTracker (initialize on one image, step on the next): pyramidal
+ *   vo_track_points_batch  Lucas-Kanade with MaxBidirectionalError, between frames or between the cameras
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
  *                          CreateLandmarksFromFeatures.m:1-21
  *   vo_step / vo_step_batch the whole loop body VO.m:70-161 (features stay
@@ -568,6 +570,80 @@ int vo_est_fundamental(vo_ctx* ctx, const float* x1, const float* x2, int n, con
 int vo_est_fundamental_batch(vo_ctx* ctx, const float* x1, const float* x2, int pts_stride, const int32_t* n_pts, int B,
                              const vo_fund_params* params, uint32_t key0, double* F, uint8_t* inliers,
                              int32_t* n_inliers, int32_t* status);
+
+/* ---- vision.PointTracker: pyramidal Lucas-Kanade point tracking ---- */
+/* [points, validity, scores] = tracker(I) of a vision.PointTracker initialised on the first image:
+ * every point is carried from img0 to img1 with sub-pixel precision, no second detection, and an
+ * optional forward-backward test.  The toolbox's tracker is closed; the spec chosen here is the
+ * algorithm of OpenCV 4.x calcOpticalFlowPyrLK in fixed point (vo_spec.h vo_klt_*, DESIGN 3.5.3,
+ * shared by the device and the CPU reference, so both give the same bytes):
+ *  - pyramid: u8 levels of (rows + 1) / 2 x (cols + 1) / 2, 5 x 5 binomial under reflect-101;
+ *  - per level, coarse to fine, a bw x bh window: 14-bit bilinear weights, grey levels with 5
+ *    fractional bits, Scharr derivatives, reads clamped to the level; the template's 2 x 2
+ *    gradient matrix (flat iff minEig < 1e-4 or det < FLT_EPSILON), then up to max_iterations
+ *    steps, stopping when |delta|^2 <= 1e-4 (EPS), when two successive steps cancel to 0.01 px
+ *    (OSC, half a step back) or at the budget (MAXIT).  A window corner i is out iff i.x < -bw,
+ *    i.x >= cols_l, i.y < -bh or i.y >= rows_l;
+ *  - a template that is out or flat, or an iteration whose window is out, at a level above 0
+ *    leaves the level's starting estimate as it was (levels_skipped counts them); at level 0 it
+ *    ends the point.  After level 0 a result outside [0, cols - 1] x [0, rows - 1] is lost;
+ *  - score = 1 - sqrt(SSD / (bw bh)) / 8160 from one more window pass at the result (0 for a point
+ *    that is not valid) [EXT: the toolbox says only "based on SSD"];
+ *  - with a finite max_bidirectional_error every forward-valid point is tracked back from its
+ *    result, img1 -> img0, same parameters, no guess; valid iff that pass is valid and the
+ *    distance to the original point is <= the maximum.
+ * Points are single 1-based pixels, x = column.  A point that is not valid returns its input
+ * position.  With img0 the left image, img1 the right one and guess = left - (d, 0) this is stereo
+ * tracking. */
+#define VO_KLT_OK 0            /* tracked */
+#define VO_KLT_TEMPLATE_OUT 1  /* level-0 template window outside the admissible range */
+#define VO_KLT_LOST 2          /* window left the level during the level-0 iterations, or the result left the image */
+#define VO_KLT_FLAT 3          /* level-0 minEig / determinant test */
+#define VO_KLT_BIDIR 4         /* back pass failed or bidirectional error above the maximum */
+#define VO_KLT_STOP_NONE 0
+#define VO_KLT_STOP_EPS 1
+#define VO_KLT_STOP_OSC 2
+#define VO_KLT_STOP_MAXIT 3
+
+typedef struct {
+    int32_t num_pyramid_levels;      /* 1 .. 6, default 3 (NumPyramidLevels) */
+    int32_t block_size[2];           /* {height, width}, odd, 5 .. 31, default 31 31 (BlockSize) */
+    int32_t max_iterations;          /* 1 .. 50, default 30 (MaxIterations) */
+    float   max_bidirectional_error; /* > 0, or +inf (default): off (MaxBidirectionalError) */
+} vo_klt_params;
+
+/* stop and iterations are those of the forward pass at level 0; bidir_error is NaN unless the back
+ * pass ran and was valid */
+typedef struct { uint8_t status, stop, iterations, levels_skipped; float bidir_error; } vo_klt_info;
+
+void vo_default_klt_params(vo_klt_params* p);
+
+/* img0, img1: host images taken as vo_sift_ex takes them (rows x cols the context's; row-major with
+ * row stride ld >= cols, or col_major with column stride ld >= rows).  pts0 [n][2], guess [n][2]
+ * (may be NULL: start from pts0), params NULL = the defaults -> pts1 [n][2], valid [n], scores [n]
+ * (may be NULL), info [n] (may be NULL).  VO_ERR_ARG, decided on the host before anything is
+ * enqueued and naming the first offending point or field: a point or guess that is not finite or
+ * has |x| or |y| >= 2^20, parameters outside the ranges above.  VO_ERR_CAPACITY for n >
+ * max_keypoints, VO_ERR_STATE while step batches are pending.  n = 0 launches nothing.  The first
+ * call that launches allocates the call's own buffers (pyramid planes of both images, points and
+ * results; they grow to the largest batch seen); a context that never calls allocates and launches
+ * nothing.  The loop state, have_features and every other entry are untouched. */
+int vo_track_points(vo_ctx* ctx, const uint8_t* img0, const uint8_t* img1, int rows, int cols, int ld, int col_major,
+                    const float* pts0, const float* guess, int n, const vo_klt_params* params, float* pts1, uint8_t* valid,
+                    float* scores, vo_klt_info* info);
+
+/* n_pairs (1 .. max_batch) pairs in one launch: imgs0 / imgs1 hold the pairs' first / second images
+ * consecutively (as vo_describe_batch takes images); pair f has n_pts[f] points (0 .. pts_stride) at
+ * pts0 / guess + f * pts_stride * 2, pts_stride <= max_keypoints.  Outputs [n_pairs][pts_stride];
+ * rows beyond n_pts[f] are untouched.  Pair f equals the single call, by bytes. */
+int vo_track_points_batch(vo_ctx* ctx, const uint8_t* imgs0, const uint8_t* imgs1, int ld, int col_major, int n_pairs,
+                          const float* pts0, const float* guess, const int32_t* n_pts, int pts_stride,
+                          const vo_klt_params* params, float* pts1, uint8_t* valid, float* scores, vo_klt_info* info);
+
+/* diagnostic: level `level` of image 2 * pair + which (which 0: img0, 1: img1) of the last launching
+ * track call -> out (tightly packed rows), *rows, *cols.  VO_ERR_STATE before such a call,
+ * VO_ERR_CAPACITY (with *rows, *cols set) when capacity < rows * cols. */
+int vo_fetch_klt_level(vo_ctx* ctx, int image, int level, uint8_t* out, int capacity, int* rows, int* cols);
 
 /* new-landmark filter (VO.m:145-158) + CreateLandmarksFromFeatures.
  * l_pos/r_pos [S][2] current stereo-matched locations; old_l/old_r [K][2]

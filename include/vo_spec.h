@@ -1127,4 +1127,153 @@ VO_HD int vo_fund_replay_slot(vo_fund_replay* r, int slot, int valid, double sco
     return 1;
 }
 
+/* ------------------------------------------------------------------------ */
+/* vision.PointTracker: pyramidal Lucas-Kanade in fixed point (the algorithm */
+/* of OpenCV 4.x calcOpticalFlowPyrLK, restated).  Shared by   */
+/* k_klt_pyr / k_klt_track and the CPU reference (tests/klt_ref).            */
+/*                                                                           */
+/* Pyramid: u8; level l + 1 has (rows_l + 1) / 2 x (cols_l + 1) / 2 pixels,   */
+/* each the 5 x 5 binomial w_i w_j, w = 1 4 6 4 1 (the 25 weights add to 256), */
+/* of level l under reflect-101, (sum + 128) >> 8 (vo_klt_pyr_pixel).         */
+/* Reads while tracking clamp the pixel index to the level (replicate).      */
+/*                                                                           */
+/* Bounds (what the kernel's packing relies on).  A pixel is 0 .. 255.  The   */
+/* three rounded weights w00, w01, w10 are >= 0 and their exact sum           */
+/* (1 - ab) 16384 is <= 16384, so rounding each to nearest makes their sum    */
+/* at most 16385: w11 = 16384 - w00 - w01 - w10 >= -1, and the four weights   */
+/* add to 16384 by construction.                                              */
+/*  - I = bil(pixel, 9): the sum lies in [-255, 255 * 16385], so              */
+/*    I in [(-255 + 256) >> 9, (255 * 16385 + 256) >> 9] = [0, 8160]; the same */
+/*    for the second image's sample, hence |diff| <= 8160.                    */
+/*  - |gx|, |gy| <= (3 + 10 + 3) * 255 = 4080, so with w11 >= 0 (all but the  */
+/*    one-ulp case above) |Ix| <= (4080 * 16384 + 8192) >> 14 = 4080; with     */
+/*    w11 = -1 the a-priori bound is (4080 * 16386 + 8192) >> 14 = 4081.  I,   */
+/*    Ix, Iy fit int16 either way.                                            */
+/*  - a lane's partial over 16 samples: |diff Ix| <= 8160 * 4081 = 33300960,  */
+/*    x 16 = 532815360 < 2^31; Ix^2 <= 16654561, x 16 < 2^28; diff^2 <=        */
+/*    66585600, x 16 = 1065369600 < 2^31.  int32 holds every partial.         */
+/*  - a 31 x 31 window: 961 * 33300960 = 3.2e10 > 2^31: window sums are int64. */
+/* Every window sum is therefore an exact integer and its order is free; the  */
+/* float part below is f32 basic operations in the order written.             */
+/* ------------------------------------------------------------------------ */
+#define VO_KLT_OK 0
+#define VO_KLT_TEMPLATE_OUT 1
+#define VO_KLT_LOST 2
+#define VO_KLT_FLAT 3
+#define VO_KLT_BIDIR 4
+#define VO_KLT_STOP_NONE 0
+#define VO_KLT_STOP_EPS 1
+#define VO_KLT_STOP_OSC 2
+#define VO_KLT_STOP_MAXIT 3
+#define VO_KLT_MAX_LEVELS 6
+#define VO_KLT_MIN_WIN 5
+#define VO_KLT_MAX_WIN 31
+#define VO_KLT_MAX_ITER 50
+#define VO_KLT_LANE_SAMPLES 16                /* ceil(961 / 64): samples s = lane + 64 k, k < 16 */
+#define VO_KLT_W_ONE 16384
+#define VO_KLT_FS 9.5367431640625e-07f        /* 2^-20 */
+#define VO_KLT_MIN_EIG 1e-4f
+#define VO_KLT_EPS2 1e-4f                     /* (0.01 px)^2 */
+#define VO_KLT_OSC 0.01f
+#define VO_KLT_SCORE_DEN 8160.0f              /* 255 * 32 */
+
+/* sizes of level l (l >= 0) of a rows x cols image */
+VO_HD int vo_klt_level_dim(int n, int l)
+{
+    for (int k = 0; k < l; ++k) n = (n + 1) / 2;
+    return n;
+}
+
+/* pixel (r, c) of level l + 1 from level l (src, rows x cols, row stride ld) */
+VO_HD int vo_klt_pyr_pixel(const uint8_t* src, int rows, int cols, int ld, int r, int c)
+{
+    const int w[5] = {1, 4, 6, 4, 1};
+    int sum = 0;
+    VO_UNROLL
+    for (int i = -2; i <= 2; ++i) {
+        const uint8_t* row = src + (long)vo_reflect101(2 * r + i, rows) * ld;
+        int h = 0;
+        VO_UNROLL
+        for (int j = -2; j <= 2; ++j) h += w[j + 2] * (int)row[vo_reflect101(2 * c + j, cols)];
+        sum += w[i + 2] * h;
+    }
+    return (sum + 128) >> 8;
+}
+
+VO_HD int vo_klt_scharr(int a0, int a1, int b0, int b1, int c0, int c1)   /* 3 (a1 - a0) + 10 (b1 - b0) + 3 (c1 - c0) */
+{
+    return 3 * (a1 - a0) + 10 * (b1 - b0) + 3 * (c1 - c0);
+}
+
+/* Window corner q -> 1 and (ix, iy, w[4] = w00 w01 w10 w11), or 0 when the corner is out:
+ * i.x < -bw || i.x >= cols || i.y < -bh || i.y >= rows.  The test is made on floorf's float (the
+ * same outcome as on the integer wherever the integer exists; a corner too far for an int, or a
+ * NaN, is out), so no conversion overflows. */
+VO_HD int vo_klt_corner(float qx, float qy, int bw, int bh, int rows, int cols, int* ix, int* iy, int* w)
+{
+    const float fx = floorf(qx), fy = floorf(qy);
+    if (!(fx >= (float)(-bw) && fx < (float)cols && fy >= (float)(-bh) && fy < (float)rows)) return 0;
+    const float a = qx - fx, b = qy - fy;
+    *ix = (int)fx; *iy = (int)fy;
+    w[0] = (int)rintf((1.0f - a) * (1.0f - b) * 16384.0f);
+    w[1] = (int)rintf(a * (1.0f - b) * 16384.0f);
+    w[2] = (int)rintf((1.0f - a) * b * 16384.0f);
+    w[3] = VO_KLT_W_ONE - w[0] - w[1] - w[2];
+    return 1;
+}
+
+VO_HD int vo_klt_bil(int f00, int f01, int f10, int f11, const int* w, int n)
+{
+    return (f00 * w[0] + f01 * w[1] + f10 * w[2] + f11 * w[3] + (1 << (n - 1))) >> n;
+}
+
+/* the template's sums -> 1 and (A11, A12, A22, 1 / D), or 0: flat */
+VO_HD int vo_klt_gradient_matrix(int64_t sxx, int64_t sxy, int64_t syy, int bw, int bh, float* A)
+{
+    const float A11 = (float)sxx * VO_KLT_FS, A12 = (float)sxy * VO_KLT_FS, A22 = (float)syy * VO_KLT_FS;
+    const float D = A11 * A22 - A12 * A12;
+    const float d = A11 - A22;
+    const float minEig = (A22 + A11 - sqrtf(d * d + 4.0f * A12 * A12)) / (float)(2 * bw * bh);
+    if (minEig < VO_KLT_MIN_EIG || D < VO_FLT_EPSILON) return 0;
+    A[0] = A11; A[1] = A12; A[2] = A22; A[3] = 1.0f / D;
+    return 1;
+}
+
+/* one iteration's sums -> delta */
+VO_HD void vo_klt_delta(const float* A, int64_t s1, int64_t s2, float* dx, float* dy)
+{
+    const float b1 = (float)s1 * VO_KLT_FS, b2 = (float)s2 * VO_KLT_FS;
+    *dx = (A[1] * b2 - A[2] * b1) * A[3];
+    *dy = (A[1] * b1 - A[0] * b2) * A[3];
+}
+
+/* After q += delta, next = q + h: the stop of iteration j (prev: the delta of iteration j - 1).
+ * OSC moves next back by half the step. */
+VO_HD int vo_klt_stop(int j, float dx, float dy, float pdx, float pdy, float* nx, float* ny)
+{
+    if (dx * dx + dy * dy <= VO_KLT_EPS2) return VO_KLT_STOP_EPS;
+    if (j > 0 && fabsf(dx + pdx) < VO_KLT_OSC && fabsf(dy + pdy) < VO_KLT_OSC) {
+        *nx = *nx - 0.5f * dx; *ny = *ny - 0.5f * dy;
+        return VO_KLT_STOP_OSC;
+    }
+    return VO_KLT_STOP_NONE;
+}
+
+VO_HD float vo_klt_score(int64_t s2, int bw, int bh)
+{
+    return 1.0f - sqrtf((float)s2 / (float)(bw * bh)) / VO_KLT_SCORE_DEN;
+}
+
+/* after level 0: inside [0, cols - 1] x [0, rows - 1] (a NaN is outside) */
+VO_HD int vo_klt_inside(float x, float y, int rows, int cols)
+{
+    return x >= 0.0f && x <= (float)(cols - 1) && y >= 0.0f && y <= (float)(rows - 1);
+}
+
+VO_HD float vo_klt_bidir_error(float x, float y, float x0, float y0)
+{
+    const float dx = x - x0, dy = y - y0;
+    return sqrtf(dx * dx + dy * dy);
+}
+
 #endif /* VO_SPEC_H */

@@ -45,6 +45,9 @@
  *        estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method = "MSAC" | "Norm8Point"), the
  *        epipolar check right after matchFeatures: vo_est_fundamental; F 3 x 3 double with
  *        [x2 1] F [x1 1]' = 0, M x 1 logical, int32 status (0, 1 = fewer than 8 points, 2 = not enough inliers)
+ *   [points, validity, scores] = vo_mex('trackpoints', I0, I1, points, opts)
+ *        one step of a vision.PointTracker initialised with points on I0 and stepped to I1 (pyramidal
+ *        Lucas-Kanade): vo_track_points; M x 2 single, M x 1 logical, M x 1 single (matlab/voPointTracker.m)
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
  *        CreateLandmarksFromFeatures.m:2-18 (the rows before the :20 append)
  *   [rel_A, A, status, nLandmarks] = vo_mex('step', Il, Ir, P1, P2)
@@ -794,6 +797,62 @@ static void cmd_fundamental(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     mxFree(inl);
 }
 
+/* vo_track_points through a weak reference: with a libvo that lacks it 'trackpoints' raises
+ * vo:PointTracker:unavailable and every other command runs as before */
+extern __typeof__(vo_track_points) vo_track_points __attribute__((weak));
+extern __typeof__(vo_default_klt_params) vo_default_klt_params __attribute__((weak));
+
+/* [points, validity, scores] = vo_mex('trackpoints', I0, I1, points, opts)
+ * I0, I1 uint8 images of one size; points M x 2 single or double [x y] 1-based; opts (optional) =
+ * [NumPyramidLevels BlockHeight BlockWidth MaxIterations MaxBidirectionalError] double (Inf: no
+ * bidirectional test).  A point that is not valid keeps its input position, as the toolbox's does. */
+static void cmd_trackpoints(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs != 4 && nrhs != 5) need_args(nrhs, 4, "trackpoints");
+    if (nlhs > 3) mexErrMsgIdAndTxt("vo:badArgument", "trackpoints returns at most [points, validity, scores]");
+    if (!vo_track_points || !vo_default_klt_params)
+        mexErrMsgIdAndTxt("vo:PointTracker:unavailable", "this libvo has no vo_track_points: use the toolbox's "
+                          "vision.PointTracker, or link a newer libvo");
+    const mxArray* I0 = prhs[1];
+    const mxArray* I1 = prhs[2];
+    need_real(I0, mxUINT8_CLASS, -1, -1, "I0");
+    need_real(I1, mxUINT8_CLASS, (long)mxGetM(I0), (long)mxGetN(I0), "I1");
+    vo_klt_params kp;
+    vo_default_klt_params(&kp);
+    if (nrhs == 5) {
+        need_real(prhs[4], mxDOUBLE_CLASS, 1, 5, "opts");
+        const double* o = mxGetDoubles(prhs[4]);
+        int32_t* f[4] = {&kp.num_pyramid_levels, &kp.block_size[0], &kp.block_size[1], &kp.max_iterations};
+        for (int k = 0; k < 4; ++k)                                   /* not an integer in 0 .. 1000: 0, refused by libvo */
+            *f[k] = (o[k] >= 0.0 && o[k] <= 1000.0 && o[k] == (double)(int32_t)o[k]) ? (int32_t)o[k] : 0;
+        kp.max_bidirectional_error = (float)o[4];
+    }
+    int n = 0;
+    float* pts = points_f32(prhs[3], 2, &n, "points");
+    const int rows = (int)mxGetM(I0), cols = (int)mxGetN(I0);
+    float* out = (float*)mxMalloc(sizeof(float) * 2 * ((size_t)n + 1));
+    float* sc = (float*)mxMalloc(sizeof(float) * ((size_t)n + 1));
+    uint8_t* ok = (uint8_t*)mxMalloc((size_t)n + 1);
+    need_ctx(rows, cols);
+    const int rc = vo_track_points(g_ctx, mxGetUint8s(I0), mxGetUint8s(I1), rows, cols, rows, 1, pts, NULL, n, &kp, out, ok, sc, NULL);
+    mxFree(pts);
+    if (rc != VO_OK) { mxFree(out); mxFree(sc); mxFree(ok); check(rc); }
+    plhs[0] = mxCreateNumericMatrix(n, 2, mxSINGLE_CLASS, mxREAL);
+    float* P = n ? mxGetSingles(plhs[0]) : NULL;
+    for (int i = 0; i < n; ++i) { P[i] = out[2 * i]; P[(size_t)n + i] = out[2 * i + 1]; }
+    if (nlhs > 1) {
+        plhs[1] = mxCreateLogicalMatrix(n, 1);
+        mxLogical* L = mxGetLogicals(plhs[1]);
+        for (int i = 0; i < n; ++i) L[i] = ok[i] != 0;
+    }
+    if (nlhs > 2) {
+        plhs[2] = mxCreateNumericMatrix(n, 1, mxSINGLE_CLASS, mxREAL);
+        float* S = n ? mxGetSingles(plhs[2]) : NULL;
+        for (int i = 0; i < n; ++i) S[i] = sc[i];
+    }
+    mxFree(out); mxFree(sc); mxFree(ok);
+}
+
 /* CreateLandmarksFromFeatures(features_l, features_r, P1, P2, pose, ~) rows (:2-18): VO.m:145-158
  * has already filtered the points, so libvo's own filter runs against no old points (K = 0). */
 static void cmd_landmarks(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
@@ -870,6 +929,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "estworldpose")) cmd_estworldpose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "refinepose")) cmd_refinepose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fundamental")) cmd_fundamental(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "trackpoints")) cmd_trackpoints(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks")) cmd_landmarks(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step")) cmd_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks_all")) cmd_landmarks_all(nlhs, plhs, nrhs, prhs);

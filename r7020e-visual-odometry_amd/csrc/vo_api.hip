@@ -163,6 +163,7 @@ struct vo_ctx {
     MatchExBuffers mx;               // vo_match_ex / vo_match_f32_ex (allocated on first use)
     MatchRadiusBuffers mr;           // vo_match_radius / vo_match_radius_f32 (allocated on first use)
     FundBuffers fund;                // vo_est_fundamental / vo_est_fundamental_batch (allocated on first use)
+    KltBuffers klt;                  // vo_track_points / vo_track_points_batch (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
@@ -244,6 +245,11 @@ void vo_default_refine_params(vo_refine_params* p)
 void vo_default_fund_params(vo_fund_params* p)
 {
     p->method = VO_FUND_MSAC; p->num_trials = 500; p->distance_threshold = 0.01; p->confidence = 99.0; p->seed = 0x5EED;
+}
+void vo_default_klt_params(vo_klt_params* p)
+{
+    p->num_pyramid_levels = 3; p->block_size[0] = 31; p->block_size[1] = 31; p->max_iterations = 30;
+    p->max_bidirectional_error = vo_u32_as_f32(0x7f800000u);
 }
 
 const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -2155,6 +2161,111 @@ int vo_est_fundamental(vo_ctx* c, const float* x1, const float* x2, int n, const
     if (st == VO_ERR_TOO_FEW_POINTS) return fail(c, st, "estimateFundamentalMatrix: need at least 8 points, got %d", n);
     if (st == VO_ERR_NO_CONSENSUS) return fail(c, st, "estimateFundamentalMatrix: no consensus (no model with >= 8 inliers)");
     return st;
+}
+
+// ---- vision.PointTracker (vo.h: "pyramidal Lucas-Kanade point tracking") -----------------------
+// -> nullptr when the block is inside the ranges of include/vo.h, else the offending field
+static const char* klt_params_refusal(const vo_klt_params& p)
+{
+    if (p.num_pyramid_levels < 1 || p.num_pyramid_levels > VO_KLT_MAX_LEVELS) return "num_pyramid_levels (1 .. 6)";
+    for (int k = 0; k < 2; ++k)
+        if (p.block_size[k] < VO_KLT_MIN_WIN || p.block_size[k] > VO_KLT_MAX_WIN || !(p.block_size[k] & 1))
+            return k ? "block_size[1] (odd, 5 .. 31)" : "block_size[0] (odd, 5 .. 31)";
+    if (p.max_iterations < 1 || p.max_iterations > VO_KLT_MAX_ITER) return "max_iterations (1 .. 50)";
+    if (!(p.max_bidirectional_error > 0.0f)) return "max_bidirectional_error (> 0 or +inf)";
+    return nullptr;
+}
+
+int vo_track_points_batch(vo_ctx* c, const uint8_t* imgs0, const uint8_t* imgs1, int ld, int col_major, int n_pairs,
+                          const float* pts0, const float* guess, const int32_t* n_pts, int pts_stride,
+                          const vo_klt_params* params, float* pts1, uint8_t* valid, float* scores, vo_klt_info* info)
+{
+    const char* who = "vo_track_points";
+    if (!c || !imgs0 || !imgs1 || !n_pts || n_pairs < 1 || pts_stride < 0 || (col_major != 0 && col_major != 1) ||
+        ld < (col_major ? c->rows : c->cols))
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    // every refusal before anything is enqueued
+    if (n_pairs > c->max_batch) return fail(c, VO_ERR_CAPACITY, "%s: %d pairs exceed max_batch %d", who, n_pairs, c->max_batch);
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    const int K = c->set[0].sb.kp_cap;
+    vo_klt_params p;
+    if (params) p = *params; else vo_default_klt_params(&p);
+    if (const char* field = klt_params_refusal(p)) return fail(c, VO_ERR_ARG, "%s: parameter out of range: %s", who, field);
+    int max_n = 0;
+    for (int f = 0; f < n_pairs; ++f) {
+        const int n = n_pts[f];
+        if (n < 0 || n > pts_stride) return fail(c, VO_ERR_ARG, "%s: n_pts[%d] = %d is outside 0 .. pts_stride = %d", who, f, n, pts_stride);
+        if (n > K) return fail(c, VO_ERR_CAPACITY, "%s: pair %d has %d points, more than max_keypoints %d", who, f, n, K);
+        max_n = std::max(max_n, n);
+    }
+    if (max_n > 0 && (!pts0 || !pts1 || !valid)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    for (int f = 0; f < n_pairs; ++f)
+        for (int which = 0; which < (guess ? 2 : 1); ++which) {
+            const float* x = (which ? guess : pts0) + (size_t)f * pts_stride * 2;
+            for (long e = 0; e < 2L * n_pts[f]; ++e)
+                if (!std::isfinite(x[e]) || !(std::fabs(x[e]) < 1048576.0f))
+                    return fail(c, VO_ERR_ARG, "%s: %s(%ld, %ld) of pair %d must be finite and below 2^20 in magnitude (point index %ld)",
+                                who, which ? "guess" : "points", e / 2 + 1, e % 2 + 1, f, e / 2);
+        }
+    if (max_n == 0) return VO_OK;                            // nothing to track: nothing is launched
+    CallScope call(c); if (call.status) return call.status;
+    KltBuffers& kb = c->klt;
+    {
+        const hipError_t e = klt_reserve(c->pool, kb, c->rows, c->cols, n_pairs, pts_stride);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t fs = (size_t)c->rows * c->cols, pts = (size_t)n_pairs * pts_stride;
+    for (int which = 0; which < 2; ++which) {                // level 0: the images themselves, img0s then img1s
+        const uint8_t* src = which ? imgs1 : imgs0;
+        uint8_t* dst = kb.planes + (size_t)which * n_pairs * fs;
+        if (!col_major && ld == c->cols) HIPC(c, hipMemcpyAsync(dst, src, fs * n_pairs, hipMemcpyHostToDevice, c->stream));
+        else { int rc = stage_images(c, src, ld, col_major, n_pairs, dst); if (rc) return rc; }
+    }
+    HIPC(c, hipMemcpyAsync(kb.pts0, pts0, sizeof(float) * 2 * pts, hipMemcpyHostToDevice, c->stream));
+    if (guess) HIPC(c, hipMemcpyAsync(kb.guess, guess, sizeof(float) * 2 * pts, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(kb.n, n_pts, sizeof(int) * n_pairs, hipMemcpyHostToDevice, c->stream));
+    klt_pyr_launch(kb, c->rows, c->cols, n_pairs, p.num_pyramid_levels, c->stream);
+    klt_track_launch(kb, c->rows, c->cols, n_pairs, pts_stride, max_n, guess != nullptr, p, c->stream);
+    kb.last_pairs = n_pairs; kb.last_levels = p.num_pyramid_levels;
+    // rows beyond n_pts[f] stay as the caller has them: pair by pair
+    for (int f = 0; f < n_pairs; ++f) {
+        const size_t o = (size_t)f * pts_stride, n = (size_t)n_pts[f];
+        if (!n) continue;
+        HIPC(c, hipMemcpyAsync(pts1 + 2 * o, kb.pts1 + 2 * o, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(valid + o, kb.valid + o, n, hipMemcpyDeviceToHost, c->stream));
+        if (scores) HIPC(c, hipMemcpyAsync(scores + o, kb.scores + o, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        if (info) HIPC(c, hipMemcpyAsync(info + o, kb.info + o, sizeof(vo_klt_info) * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    return finish(c);
+}
+
+int vo_track_points(vo_ctx* c, const uint8_t* img0, const uint8_t* img1, int rows, int cols, int ld, int col_major,
+                    const float* pts0, const float* guess, int n, const vo_klt_params* params, float* pts1, uint8_t* valid,
+                    float* scores, vo_klt_info* info)
+{
+    if (!c || rows != c->rows || cols != c->cols || n < 0) return fail(c, VO_ERR_ARG, "vo_track_points: bad arguments");
+    if (n > c->set[0].sb.kp_cap) return fail(c, VO_ERR_CAPACITY, "vo_track_points: %d points exceed max_keypoints", n);
+    const int32_t cnt = n;
+    return vo_track_points_batch(c, img0, img1, ld, col_major, 1, pts0, guess, &cnt, n, params, pts1, valid, scores, info);
+}
+
+int vo_fetch_klt_level(vo_ctx* c, int image, int level, uint8_t* out, int capacity, int* rows, int* cols)
+{
+    if (!c || image < 0 || level < 0) return fail(c, VO_ERR_ARG, "vo_fetch_klt_level: bad arguments");
+    const KltBuffers& kb = c->klt;
+    if (kb.last_pairs == 0) return fail(c, VO_ERR_STATE, "vo_fetch_klt_level: no vo_track_points call has launched yet");
+    if (image >= 2 * kb.last_pairs || level >= kb.last_levels)
+        return fail(c, VO_ERR_ARG, "vo_fetch_klt_level: image %d, level %d outside the last call's %d images, %d levels", image, level,
+                    2 * kb.last_pairs, kb.last_levels);
+    const int r = vo_klt_level_dim(c->rows, level), q = vo_klt_level_dim(c->cols, level);
+    if (rows) *rows = r;
+    if (cols) *cols = q;
+    if (!out || capacity < r * q) return fail(c, VO_ERR_CAPACITY, "vo_fetch_klt_level: %d bytes needed", r * q);
+    CallScope call(c); if (call.status) return call.status;
+    const size_t i = (size_t)(image & 1) * kb.last_pairs + (image >> 1);
+    HIPC(c, hipMemcpyAsync(out, kb.planes + klt_level_offset(c->rows, c->cols, kb.last_pairs, level) + i * r * q, (size_t)r * q,
+                           hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
 }
 
 int vo_landmarks(vo_ctx* c, const float* l_pos, const float* r_pos, int S, const float* old_l, const float* old_r, int Kn,

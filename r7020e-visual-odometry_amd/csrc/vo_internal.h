@@ -320,4 +320,25 @@ void pack_f32_desc_launch(const float* F, int n, int ld, int col_major, uint8_t*
 void match_f32_launch(const float* F1, int n1, int ld1, const float* F2, int n2, int ld2, int col_major, float* A, float* BT,
                       int* res, const vo_match_params& p, hipStream_t s);
 
+// ---- vision.PointTracker (klt.hip): vo_track_points / vo_track_points_batch ----
+// Buffers of their own, allocated by klt_reserve at the first launching call and grown to the
+// largest batch seen, so the loop's buffer sets are never touched.  planes is level-major: level l
+// of image i (i = which * n_pairs + pair) at klt_level_offset(l) + i * rows_l * cols_l, level 0 the
+// staged images themselves.
+struct KltBuffers {
+    int cap_pairs = 0; size_t cap_pts = 0;
+    int last_pairs = 0, last_levels = 0;          // of the last launching call (vo_fetch_klt_level)
+    uint8_t* planes = nullptr;                    // [6 levels][2 n_pairs][rows_l][cols_l]
+    int* n = nullptr;                             // [n_pairs]
+    float* pts0 = nullptr; float* guess = nullptr; float* pts1 = nullptr;   // [n_pairs][pts_stride][2]
+    uint8_t* valid = nullptr; float* scores = nullptr; vo_klt_info* info = nullptr;   // [n_pairs][pts_stride]
+};
+hipError_t klt_reserve(DevPool& pool, KltBuffers& kb, int rows, int cols, int n_pairs, int pts_stride);   // all or nothing per group
+size_t klt_level_offset(int rows, int cols, int n_pairs, int level);
+// k_klt_pyr: levels 1 .. levels - 1 of all 2 n_pairs images, one launch per level
+void klt_pyr_launch(KltBuffers& kb, int rows, int cols, int n_pairs, int levels, hipStream_t s);
+// k_klt_track: one wave per point and pair over kb.pts0 / kb.guess / kb.n -> kb.pts1, valid, scores, info
+void klt_track_launch(KltBuffers& kb, int rows, int cols, int n_pairs, int pts_stride, int max_n, bool has_guess,
+                      const vo_klt_params& p, hipStream_t s);
+
 }  // namespace vo

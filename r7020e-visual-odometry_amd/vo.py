@@ -13,6 +13,7 @@ running on the MI355X through libvo.so:
     estworldpose                           VO.m:123-127
     bundleAdjustmentMotion                 after VO.m:123-127 (refine_pose, set_pose_refinement)
     estimateFundamentalMatrix              after matchFeatures (est_fundamental, est_fundamental_batch)
+    vision.PointTracker                    pyramidal KLT between frames or cameras (track_points, PointTracker)
     CreateLandmarksFromFeatures           CreateLandmarksFromFeatures.m:1-21
     VisualOdometry.step                    the VO.m loop body (VO.m:70-161)
 
@@ -80,6 +81,18 @@ class FundParams(C.Structure):
                 ("confidence", C.c_double), ("seed", C.c_uint32)]
 
 
+class KltParams(C.Structure):
+    """vo_klt_params: vision.PointTracker's NumPyramidLevels, BlockSize ({height, width}), MaxIterations and
+    MaxBidirectionalError (+inf: off)."""
+    _fields_ = [("num_pyramid_levels", C.c_int32), ("block_size", C.c_int32 * 2), ("max_iterations", C.c_int32),
+                ("max_bidirectional_error", C.c_float)]
+
+
+class KltInfo(C.Structure):
+    _fields_ = [("status", C.c_uint8), ("stop", C.c_uint8), ("iterations", C.c_uint8), ("levels_skipped", C.c_uint8),
+                ("bidir_error", C.c_float)]
+
+
 class RefineStats(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("passes", C.c_int32), ("accepted", C.c_int32),
                 ("cost_initial", C.c_double), ("cost_final", C.c_double)]
@@ -126,6 +139,13 @@ VO_FUND_NORM8, VO_FUND_MSAC = 0, 1
 FUND_METHODS = {"Norm8Point": VO_FUND_NORM8, "MSAC": VO_FUND_MSAC}
 FUND_MAX_TRIALS = 100000
 
+# vo_klt_info.status / .stop
+VO_KLT_OK, VO_KLT_TEMPLATE_OUT, VO_KLT_LOST, VO_KLT_FLAT, VO_KLT_BIDIR = 0, 1, 2, 3, 4
+VO_KLT_STOP_NONE, VO_KLT_STOP_EPS, VO_KLT_STOP_OSC, VO_KLT_STOP_MAXIT = 0, 1, 2, 3
+KLT_INFO_DTYPE = np.dtype([("status", "u1"), ("stop", "u1"), ("iterations", "u1"), ("levels_skipped", "u1"),
+                           ("bidir_error", "<f4")])
+KLT_MAX_COORD = 1048576.0
+
 # exported symbols (tests check the library exports every one)
 EXPORTS = [
     "vo_default_sift_params", "vo_default_match_params", "vo_default_ransac_params", "vo_create", "vo_destroy",
@@ -144,6 +164,7 @@ EXPORTS = [
     "vo_default_refine_params", "vo_refine_pose", "vo_set_pose_refinement", "vo_fetch_pose_refinement",
     "vo_match_radius", "vo_match_radius_f32",
     "vo_default_fund_params", "vo_est_fundamental", "vo_est_fundamental_batch",
+    "vo_default_klt_params", "vo_track_points", "vo_track_points_batch", "vo_fetch_klt_level",
 ]
 
 _libs: dict = {}
@@ -230,6 +251,15 @@ def load_library(path: str | os.PathLike | None = None):
                                          P(C.c_uint8), P(C.c_int)]
         L.vo_est_fundamental_batch.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_int32), C.c_int, P(FundParams),
                                                C.c_uint32, P(C.c_double), P(C.c_uint8), P(C.c_int32), P(C.c_int32)]
+    if hasattr(L, "vo_track_points"):        # (absent from an older library timed beside this one)
+        L.vo_default_klt_params.argtypes = [P(KltParams)]
+        L.vo_default_klt_params.restype = None
+        L.vo_track_points.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float),
+                                      C.c_int, P(KltParams), P(C.c_float), P(C.c_uint8), P(C.c_float), P(KltInfo)]
+        L.vo_track_points_batch.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float),
+                                            P(C.c_int32), C.c_int, P(KltParams), P(C.c_float), P(C.c_uint8), P(C.c_float),
+                                            P(KltInfo)]
+        L.vo_fetch_klt_level.argtypes = [vp, C.c_int, C.c_int, P(C.c_uint8), C.c_int, P(C.c_int), P(C.c_int)]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
                                P(C.c_double), P(C.c_double), C.c_int, P(C.c_int)]
     L.vo_step.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(StepOut)]
@@ -380,6 +410,53 @@ def fund_points(matchedPoints1, matchedPoints2, who: str = "est_fundamental"):
     if len(out[0]) != len(out[1]):
         raise VOError(VO_ERR_ARG, f"{who}: matchedPoints1 and matchedPoints2 differ in length")
     return out[0], out[1]
+
+
+def default_klt_params(**overrides) -> KltParams:
+    """vo_default_klt_params (3 levels, BlockSize [31 31], 30 iterations, MaxBidirectionalError inf), with
+    any field overridden by keyword (block_size: (height, width)).  Host only: no library, no device."""
+    p = KltParams(3, (C.c_int32 * 2)(31, 31), 30, float("inf"))
+    for k, v in overrides.items():
+        if k not in dict(KltParams._fields_):
+            raise VOError(VO_ERR_ARG, f"default_klt_params: no field {k}")
+        if k == "block_size":
+            v = (C.c_int32 * 2)(int(v[0]), int(v[1]))
+        setattr(p, k, v)
+    return p
+
+
+def check_klt_params(p: KltParams) -> None:
+    """vo_track_points' parameter ranges (include/vo.h), checked on the host: VOError(VO_ERR_ARG) naming
+    the offending field."""
+    bad = None
+    if not 1 <= p.num_pyramid_levels <= 6:
+        bad = "num_pyramid_levels (1 .. 6)"
+    elif any(not (5 <= b <= 31 and b % 2 == 1) for b in p.block_size):
+        bad = "block_size (odd, 5 .. 31)"
+    elif not 1 <= p.max_iterations <= 50:
+        bad = "max_iterations (1 .. 50)"
+    elif not p.max_bidirectional_error > 0.0:
+        bad = "max_bidirectional_error (> 0 or inf)"
+    if bad:
+        raise VOError(VO_ERR_ARG, f"track_points: parameter out of range: {bad}")
+
+
+def klt_points(points, who: str = "track_points", name: str = "points") -> np.ndarray:
+    """A point list as [n][2] float32 (an n x 2 array, or a keypoint array with fields x, y), checked on the
+    host by vo_check_points' finiteness rule (finite, |x|, |y| < 2^20): VOError(VO_ERR_ARG) naming the first
+    offending row."""
+    a = np.asarray(points)
+    if a.dtype.names and "x" in a.dtype.names:
+        a = np.stack([a["x"], a["y"]], 1)
+    if a.size == 0:
+        a = np.zeros((0, 2), np.float32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise VOError(VO_ERR_ARG, f"{who}: {name} must be n x 2")
+    a = np.ascontiguousarray(a, np.float32)
+    bad = np.flatnonzero(~(np.isfinite(a) & (np.abs(a) < KLT_MAX_COORD)).all(1))
+    if len(bad):
+        raise VOError(VO_ERR_ARG, f"{who}: {name} row {int(bad[0])} must be finite and below 2^20 in magnitude")
+    return a
 
 
 def _refine_stats(s: RefineStats) -> np.ndarray:
@@ -889,6 +966,83 @@ class Context:
                                                       _p(nin, C.c_int32), _p(st, C.c_int32)))
         return st[:B], F[:B].reshape(B, 3, 3), inl[:B, :stride].astype(bool), nin[:B]
 
+    # ---- vision.PointTracker ----
+    def track_points(self, img0: np.ndarray, img1: np.ndarray, points, guess=None, params: KltParams | None = None):
+        """Pyramidal Lucas-Kanade from img0 to img1 (vo_track_points): points [n][2] 1-based pixels, guess
+        [n][2] or None -> (points1 [n][2] float32, valid [n] bool, scores [n] float32, info [n] KLT_INFO_DTYPE).
+        A point that is not valid keeps its input position.  Images of one storage (both Fortran-ordered,
+        or both row-major with one row stride) go through as they lie."""
+        a, b = np.asarray(img0, np.uint8), np.asarray(img1, np.uint8)
+        if a.ndim != 2 or a.shape != b.shape:
+            raise VOError(VO_ERR_ARG, "track_points: two 2-D uint8 images of one size")
+        rows, cols = a.shape
+        if rows > 1 and a.strides == b.strides and a.strides[0] == 1 and a.strides[1] >= rows:
+            col_major, ld = 1, a.strides[1]
+        elif a.strides == b.strides and a.strides[1] == 1 and a.strides[0] >= cols:
+            col_major, ld = 0, a.strides[0]
+        else:
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+            col_major, ld = 0, cols
+        pts = klt_points(points)
+        g = None if guess is None else klt_points(guess, name="guess")
+        if g is not None and len(g) != len(pts):
+            raise VOError(VO_ERR_ARG, "track_points: guess and points differ in length")
+        p = params if params is not None else default_klt_params()
+        check_klt_params(p)
+        n = len(pts)
+        out = np.zeros((max(n, 1), 2), np.float32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        scores = np.zeros(max(n, 1), np.float32)
+        info = np.zeros(max(n, 1), KLT_INFO_DTYPE)
+        self._check(self.lib.vo_track_points(self.h, _p(a, C.c_uint8), _p(b, C.c_uint8), rows, cols, ld, col_major, _p(pts, C.c_float),
+                                             _p(g, C.c_float) if g is not None else None, n, C.byref(p), _p(out, C.c_float),
+                                             _p(valid, C.c_uint8), _p(scores, C.c_float), info.ctypes.data_as(C.POINTER(KltInfo))))
+        return out[:n], valid[:n].astype(bool), scores[:n], info[:n]
+
+    def track_points_batch(self, imgs0: np.ndarray, imgs1: np.ndarray, points_list, guess_list=None,
+                           params: KltParams | None = None) -> list:
+        """vo_track_points_batch: imgs0, imgs1 [n_pairs, rows, cols], one point set per pair (their counts may
+        differ, 0 included), guess_list None or one guess set per pair -> a list of track_points' tuples."""
+        imgs0, imgs1 = np.ascontiguousarray(imgs0, np.uint8), np.ascontiguousarray(imgs1, np.uint8)
+        if imgs0.ndim != 3 or imgs0.shape != imgs1.shape or len(points_list) != imgs0.shape[0]:
+            raise VOError(VO_ERR_ARG, "track_points_batch: imgs0, imgs1 [n_pairs, rows, cols] and one point set per pair")
+        B = imgs0.shape[0]
+        sets = [klt_points(q, f"track_points_batch: pair {f}") for f, q in enumerate(points_list)]
+        counts = np.array([len(q) for q in sets], np.int32)
+        stride = int(counts.max()) if B else 0
+        pts = np.zeros((B, max(stride, 1), 2), np.float32)
+        g = None
+        if guess_list is not None:
+            if len(guess_list) != B:
+                raise VOError(VO_ERR_ARG, "track_points_batch: one guess set per pair")
+            g = np.zeros_like(pts)
+        for f, q in enumerate(sets):
+            pts[f, : len(q)] = q
+            if g is not None:
+                gq = klt_points(guess_list[f], f"track_points_batch: pair {f}", "guess")
+                if len(gq) != len(q):
+                    raise VOError(VO_ERR_ARG, f"track_points_batch: pair {f}: guess and points differ in length")
+                g[f, : len(q)] = gq
+        p = params if params is not None else default_klt_params()
+        check_klt_params(p)
+        out = np.zeros_like(pts)
+        valid = np.zeros((B, max(stride, 1)), np.uint8)
+        scores = np.zeros((B, max(stride, 1)), np.float32)
+        info = np.zeros((B, max(stride, 1)), KLT_INFO_DTYPE)
+        self._check(self.lib.vo_track_points_batch(self.h, _p(imgs0, C.c_uint8), _p(imgs1, C.c_uint8), imgs0.shape[2], 0, B,
+                                                   _p(pts, C.c_float), _p(g, C.c_float) if g is not None else None,
+                                                   _p(counts, C.c_int32), stride, C.byref(p), _p(out, C.c_float), _p(valid, C.c_uint8),
+                                                   _p(scores, C.c_float), info.ctypes.data_as(C.POINTER(KltInfo))))
+        return [(out[f, : counts[f]].copy(), valid[f, : counts[f]].astype(bool), scores[f, : counts[f]].copy(),
+                 info[f, : counts[f]].copy()) for f in range(B)]
+
+    def fetch_klt_level(self, image: int, level: int) -> np.ndarray:
+        """Diagnostic (vo_fetch_klt_level): pyramid level `level` of image 2 * pair + which of the last track call."""
+        r, q = C.c_int(0), C.c_int(0)
+        out = np.zeros(self.rows * self.cols, np.uint8)
+        self._check(self.lib.vo_fetch_klt_level(self.h, image, level, _p(out, C.c_uint8), out.size, C.byref(r), C.byref(q)))
+        return out[: r.value * q.value].reshape(r.value, q.value).copy()
+
     # ---- new-landmark filter + CreateLandmarksFromFeatures ----
     def landmarks(self, l_pos, r_pos, old_l, old_r, pose) -> np.ndarray:
         a = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (l_pos, r_pos, old_l, old_r)]
@@ -1184,3 +1338,46 @@ def estimateFundamentalMatrix(matchedPoints1, matchedPoints2, Method: str = "MSA
     check_fund_params(p)
     rc, F, inl, _ = _default_ctx(375, 1242).est_fundamental(x1, x2, p, key)
     return F, inl, {VO_OK: 0, VO_ERR_TOO_FEW_POINTS: 1, VO_ERR_NO_CONSENSUS: 2}[rc]
+
+
+class PointTracker:
+    """vision.PointTracker's shape on a Context: initialize(points, I), then step(I) -> (points, validity,
+    scores) carries the points from the previous image to I; set_points replaces them (and their
+    validity).  Points that were lost stay where they were last seen and stay invalid, as the toolbox
+    keeps them, until set_points."""
+
+    def __init__(self, ctx: "Context", NumPyramidLevels: int = 3, BlockSize=(31, 31), MaxIterations: int = 30,
+                 MaxBidirectionalError: float = float("inf")):
+        self.ctx = ctx
+        self.params = default_klt_params(num_pyramid_levels=int(NumPyramidLevels), block_size=BlockSize,
+                                         max_iterations=int(MaxIterations), max_bidirectional_error=float(MaxBidirectionalError))
+        check_klt_params(self.params)
+        self.image = None
+        self.points = np.zeros((0, 2), np.float32)
+        self.validity = np.zeros(0, bool)
+
+    def initialize(self, points, I) -> None:
+        I = np.asarray(I, np.uint8)
+        if I.shape != (self.ctx.rows, self.ctx.cols):
+            raise VOError(VO_ERR_ARG, "PointTracker.initialize: a 2-D uint8 image of the context's size")
+        self.image = I.copy()
+        self.set_points(points)
+
+    def set_points(self, points, validity=None) -> None:
+        self.points = klt_points(points, "PointTracker.set_points").copy()
+        self.validity = np.ones(len(self.points), bool) if validity is None else np.asarray(validity, bool).copy()
+        if len(self.validity) != len(self.points):
+            raise VOError(VO_ERR_ARG, "PointTracker.set_points: validity and points differ in length")
+
+    def step(self, I):
+        if self.image is None:
+            raise VOError(VO_ERR_STATE, "PointTracker.step: initialize first")
+        I = np.asarray(I, np.uint8)
+        idx = np.flatnonzero(self.validity)
+        pts, ok, sc, _ = self.ctx.track_points(self.image, I, self.points[idx], params=self.params)
+        scores = np.zeros(len(self.points), np.float32)
+        self.points[idx] = pts
+        self.validity[idx] = ok
+        scores[idx] = sc
+        self.image = I.copy()
+        return self.points.copy(), self.validity.copy(), scores
