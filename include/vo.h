@@ -41,6 +41,8 @@
  *   vo_est_fundamental_batch "Norm8Point"): the epipolar check of 2-D/2-D matches after matchFeatures
  *   vo_track_points /      vision.PointTracker (initialize on one image, step on the next): pyramidal
  *   vo_track_points_batch  Lucas-Kanade with MaxBidirectionalError, between frames or between the cameras
+ *   vo_detect_corners /    detectMinEigenFeatures / detectHarrisFeatures(I, MinQuality, FilterSize, ROI):
+ *   vo_detect_corners_batch cornerPoints for the tracker, without a scale space
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
  *                          CreateLandmarksFromFeatures.m:1-21
  *   vo_step / vo_step_batch the whole loop body VO.m:70-161 (features stay
@@ -644,6 +646,60 @@ int vo_track_points_batch(vo_ctx* ctx, const uint8_t* imgs0, const uint8_t* imgs
  * track call -> out (tightly packed rows), *rows, *cols.  VO_ERR_STATE before such a call,
  * VO_ERR_CAPACITY (with *rows, *cols set) when capacity < rows * cols. */
 int vo_fetch_klt_level(vo_ctx* ctx, int image, int level, uint8_t* out, int capacity, int* rows, int* cols);
+
+/* ---- detectMinEigenFeatures / detectHarrisFeatures: cornerPoints ---- */
+/* points = detectMinEigenFeatures(I, MinQuality = , FilterSize = , ROI = ) (Shi-Tomasi, the detector the
+ * toolbox pairs with vision.PointTracker) and detectHarrisFeatures(...).  The toolbox's implementation is
+ * closed; the spec chosen here (vo_spec.h vo_corner_*, DESIGN 3.5.4, shared by the device and the CPU
+ * reference, so both give the same bytes):
+ *  - central differences of the u8 image under replicate, their three products smoothed by the
+ *    separable filter_size x filter_size Gaussian (sigma = filter_size / 3) in 12-bit integer weights:
+ *    exact integers up to the response;
+ *  - metric (f32, in the units of a [0, 1] image): the smaller eigenvalue of the smoothed matrix, or
+ *    det - 0.04 trace^2 (Harris), in f64;
+ *  - a corner is a pixel of the ROI with metric > min_quality * (the ROI's maximum metric) that is a
+ *    local maximum of its 8 neighbours inside the image, the first of an equal pair winning [EXT: the
+ *    toolbox uses imregionalmax]; a maximum that is not positive gives no corners;
+ *  - Location = the pixel, 1-based (x = column), plus a per-axis parabolic offset in [-0.5, 0.5] (0 beside
+ *    the image border); Metric = the pixel's metric [EXT: the toolbox reports the fitted peak];
+ *  - corners come ascending in (row, column); with strongest = N > 0 the N strongest, metric descending,
+ *    raster order ascending among equals (cornerPoints.selectStrongest(N)). */
+#define VO_CORNER_MINEIG 0
+#define VO_CORNER_HARRIS 1
+
+typedef struct {
+    int32_t method;        /* VO_CORNER_MINEIG (default) | VO_CORNER_HARRIS */
+    int32_t filter_size;   /* odd, 3 .. 15, default 5 (FilterSize) */
+    float   min_quality;   /* [0, 1], default 0.01 (MinQuality) */
+    int32_t strongest;     /* 0 = all, else 1 .. max_keypoints */
+    int32_t roi[4];        /* x y w h, 1-based (ROI); w = 0: whole image */
+} vo_corner_params;
+
+void vo_default_corner_params(vo_corner_params* p);
+
+/* img: a host image taken as vo_sift_ex takes it (rows x cols the context's; row-major with row stride
+ * ld >= cols, or col_major with column stride ld >= rows); params NULL = the defaults -> loc [capacity][2]
+ * (x, y), metric [capacity], *n_out.  VO_ERR_ARG, decided on the host before anything is enqueued and
+ * naming the field: a parameter outside the ranges above, an ROI with w or h < 1 or not inside the image.
+ * VO_ERR_STATE while step batches are pending.  VO_ERR_CAPACITY with *n_out the true count and nothing
+ * written: more corners than the device list holds (4 x max_keypoints), or more to return than
+ * capacity.  The first call that launches allocates the call's own buffers (images, metric planes,
+ * lists, maxima; they grow to the largest batch seen); a context that never calls allocates and launches
+ * nothing.  The loop state, have_features and every other entry are untouched. */
+int vo_detect_corners(vo_ctx* ctx, const uint8_t* img, int rows, int cols, int ld, int col_major, const vo_corner_params* params,
+                      float* loc, float* metric, int capacity, int* n_out);
+
+/* n_img (1 .. 2 x max_batch) consecutive images (as vo_describe_batch takes them) in one launch per kernel;
+ * image i's results at loc + i * stride * 2, metric + i * stride, its count in n_out[i] and VO_OK or
+ * VO_ERR_CAPACITY (as above, capacity = stride) in status[i]; rows beyond the count are untouched.  The
+ * return value is VO_OK when the call ran, whatever the images' statuses.  Image i equals the single call,
+ * by bytes. */
+int vo_detect_corners_batch(vo_ctx* ctx, const uint8_t* imgs, int ld, int col_major, int n_img, const vo_corner_params* params,
+                            float* loc, float* metric, int stride, int32_t* n_out, int32_t* status);
+
+/* diagnostic: the metric plane of image `image` of the last launching call -> out [rows][cols].
+ * VO_ERR_STATE before such a call, VO_ERR_CAPACITY when capacity < rows * cols. */
+int vo_fetch_corner_metric(vo_ctx* ctx, int image, float* out, int capacity);
 
 /* new-landmark filter (VO.m:145-158) + CreateLandmarksFromFeatures.
  * l_pos/r_pos [S][2] current stereo-matched locations; old_l/old_r [K][2]

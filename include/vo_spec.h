@@ -1276,4 +1276,108 @@ VO_HD float vo_klt_bidir_error(float x, float y, float x0, float y0)
     return sqrtf(dx * dx + dy * dy);
 }
 
+/* ------------------------------------------------------------------------ */
+/* detectMinEigenFeatures / detectHarrisFeatures: cornerPoints. */
+/* Shared by k_corner_metric / k_corner_count / k_corner_emit / k_corner_rank */
+/* and the CPU reference (tests/corner_ref).  Integers up to the response,    */
+/* then f64 basic operations and sqrt in the order written.                   */
+/*                                                                           */
+/* Image u8, every read clamped to the image.  Ix(r, c) = p(r, c + 1) -       */
+/* p(r, c - 1), Iy(r, c) = p(r + 1, c) - p(r - 1, c), both in [-255, 255]; the */
+/* products Ix^2, Iy^2, Ix Iy have magnitude <= 255^2 = 65025.  A product at   */
+/* an index outside the image is the product at the clamped index.            */
+/*                                                                           */
+/* Window: f x f (odd, 3 .. 15), separable, integer weights q_k >= 0 of       */
+/* vo_corner_weights that add to 4096 exactly.                                */
+/*  - horizontal pass h = sum_j q_j prod: |h| <= (sum_j q_j) 65025 =          */
+/*    4096 * 65025 = 266342400 < 2^31 = 2147483648: int32 holds it and every  */
+/*    partial sum (all q_j >= 0, so partial sums of |q_j prod| only grow);    */
+/*  - vertical pass v = sum_i q_i h: |v| <= 4096 * 266342400 = 1090938470400 */
+/*    < 2^41 = 2199023255552: int64, and exact as a double (< 2^53).          */
+/* A, B, C = v of Ix^2, Iy^2, Ix Iy: the exact 2-D sums scaled by 2^24, so the */
+/* order of either sum is free.                                               */
+/* ------------------------------------------------------------------------ */
+#define VO_CORNER_MINEIG 0
+#define VO_CORNER_HARRIS 1
+#define VO_CORNER_MIN_FILTER 3
+#define VO_CORNER_MAX_FILTER 15
+#define VO_CORNER_W_ONE 4096
+#define VO_CORNER_HARRIS_K 0.04
+#define VO_CORNER_S (5.9604644775390625e-08 / 65025.0)   /* 2^-24 / 255^2: the units of a [0, 1] image */
+
+/* the f 1-D weights: q_k = rint(4096 w_k / sum w), w_k = exp(-k^2 / (2 sigma^2)), sigma = f / 3, in
+ * host double, then the centre takes what is missing from 4096.  Host only (libvo's entry and the
+ * reference call it; the kernels get the integers). */
+static inline void vo_corner_weights(int f, int* q)
+{
+    const int R = (f - 1) / 2;
+    const double sigma = (double)f / 3.0;
+    double w[VO_CORNER_MAX_FILTER], sum = 0.0;
+    int total = 0;
+    for (int k = -R; k <= R; ++k) { w[k + R] = exp(-(double)(k * k) / (2.0 * sigma * sigma)); sum += w[k + R]; }
+    for (int k = 0; k < f; ++k) { q[k] = (int)rint(4096.0 * w[k] / sum); total += q[k]; }
+    q[R] += VO_CORNER_W_ONE - total;
+}
+
+VO_HD int vo_corner_clamp(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+/* the response of the smoothed matrix [A C; C B] (scaled by 2^24 * 65025) */
+VO_HD float vo_corner_response(int method, int64_t A, int64_t B, int64_t C)
+{
+    const double a = (double)A, b = (double)B, c = (double)C, S = VO_CORNER_S;
+    if (method == VO_CORNER_HARRIS) {
+        const double tr = a + b;
+        return (float)((((a * b) - (c * c)) - VO_CORNER_HARRIS_K * (tr * tr)) * (S * S));
+    }
+    const double d = a - b;
+    return (float)((0.5 * ((a + b) - sqrt(d * d + 4.0 * (c * c)))) * S);
+}
+
+/* the ROI's maximum is taken from 0: a metric that is not positive does not count */
+VO_HD uint32_t vo_corner_max_bits(float m) { return m > 0.0f ? vo_f32_as_u32(m) : 0u; }
+
+/* pixel (r, c) of the tightly packed metric plane m: above the threshold (thr = min_quality * mmax, mmax
+ * > 0 checked by the caller) and a local maximum of its 8 neighbours inside the image -- strictly above
+ * those that precede it in row-major order, not below those that follow, so the first pixel of an equal
+ * pair wins */
+VO_HD int vo_corner_is_corner(const float* m, int rows, int cols, int r, int c, float thr)
+{
+    const float z = m[(long)r * cols + c];
+    if (!(z > thr)) return 0;
+    for (int dr = -1; dr <= 1; ++dr)
+        for (int dc = -1; dc <= 1; ++dc) {
+            const int rr = r + dr, cc = c + dc;
+            if ((dr == 0 && dc == 0) || rr < 0 || rr >= rows || cc < 0 || cc >= cols) continue;
+            const float n = m[(long)rr * cols + cc];
+            const int before = dr < 0 || (dr == 0 && dc < 0);
+            if (before ? !(z > n) : !(z >= n)) return 0;
+        }
+    return 1;
+}
+
+/* sub-pixel offset along one axis from the metrics at -1, 0, +1 (f32, in this order) */
+VO_HD float vo_corner_offset(float l, float z, float g)
+{
+    const float den = (l - z) + (g - z);
+    float d = den < 0.0f ? 0.5f * (l - g) / den : 0.0f;
+    if (d < -0.5f) d = -0.5f;
+    if (d > 0.5f) d = 0.5f;
+    return d;
+}
+
+/* Location (x, y), 1-based, of the corner at pixel (r, c); the offset of an axis with a neighbour
+ * outside the image is 0 */
+VO_HD void vo_corner_location(const float* m, int rows, int cols, int r, int c, float* x, float* y)
+{
+    const float z = m[(long)r * cols + c];
+    const float dx = (c > 0 && c < cols - 1) ? vo_corner_offset(m[(long)r * cols + c - 1], z, m[(long)r * cols + c + 1]) : 0.0f;
+    const float dy = (r > 0 && r < rows - 1) ? vo_corner_offset(m[(long)(r - 1) * cols + c], z, m[(long)(r + 1) * cols + c]) : 0.0f;
+    *x = (float)(c + 1) + dx;
+    *y = (float)(r + 1) + dy;
+}
+
+/* selectStrongest's key (vo_set_strongest's order): metric descending, then position in the raster-ordered
+ * list ascending.  A corner's metric is positive, so its bits order as a u32. */
+VO_HD uint64_t vo_corner_key(float metric, uint32_t index) { return (uint64_t)vo_f32_as_u32(metric) << 32 | (uint64_t)(~index); }
+
 #endif /* VO_SPEC_H */

@@ -48,6 +48,9 @@
  *   [points, validity, scores] = vo_mex('trackpoints', I0, I1, points, opts)
  *        one step of a vision.PointTracker initialised with points on I0 and stepped to I1 (pyramidal
  *        Lucas-Kanade): vo_track_points; M x 2 single, M x 1 logical, M x 1 single (matlab/voPointTracker.m)
+ *   [Location, Metric] = vo_mex('corners', I, opts)
+ *        detectMinEigenFeatures / detectHarrisFeatures(I, MinQuality = , FilterSize = , ROI = ): vo_detect_corners;
+ *        N x 2 single [x y] 1-based, N x 1 single (matlab/detectMinEigenFeatures.m, matlab/detectHarrisFeatures.m)
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
  *        CreateLandmarksFromFeatures.m:2-18 (the rows before the :20 append)
  *   [rel_A, A, status, nLandmarks] = vo_mex('step', Il, Ir, P1, P2)
@@ -853,6 +856,56 @@ static void cmd_trackpoints(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     mxFree(out); mxFree(sc); mxFree(ok);
 }
 
+/* vo_detect_corners through a weak reference: with a libvo that lacks it 'corners' raises
+ * vo:cornerPoints:unavailable and every other command runs as before */
+extern __typeof__(vo_detect_corners) vo_detect_corners __attribute__((weak));
+extern __typeof__(vo_default_corner_params) vo_default_corner_params __attribute__((weak));
+#define VO_MEX_CORNER_CAP 65536     /* the device list of the session's context: 4 x the default max_keypoints */
+
+/* [Location, Metric] = vo_mex('corners', I, opts)
+ * I uint8 image; opts (optional) = [method FilterSize MinQuality strongest x y w h] double, method 0 = MinEigen,
+ * 1 = Harris, strongest 0 = all, w = 0 = the whole image (ROI 1-based, as MATLAB gives it).  Corners come
+ * ascending in (row, column), or the `strongest` strongest. */
+static void cmd_corners(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs != 2 && nrhs != 3) need_args(nrhs, 2, "corners");
+    if (nlhs > 2) mexErrMsgIdAndTxt("vo:badArgument", "corners returns at most [Location, Metric]");
+    if (!vo_detect_corners || !vo_default_corner_params)
+        mexErrMsgIdAndTxt("vo:cornerPoints:unavailable", "this libvo has no vo_detect_corners: use the toolbox's "
+                          "detectMinEigenFeatures / detectHarrisFeatures, or link a newer libvo");
+    const mxArray* I = prhs[1];
+    need_real(I, mxUINT8_CLASS, -1, -1, "I");
+    vo_corner_params cp;
+    vo_default_corner_params(&cp);
+    if (nrhs == 3) {
+        need_real(prhs[2], mxDOUBLE_CLASS, 1, 8, "opts");
+        const double* o = mxGetDoubles(prhs[2]);
+        int32_t* f[7] = {&cp.method, &cp.filter_size, &cp.strongest, &cp.roi[0], &cp.roi[1], &cp.roi[2], &cp.roi[3]};
+        const int at[7] = {0, 1, 3, 4, 5, 6, 7};
+        for (int k = 0; k < 7; ++k) {                                 /* not an integer in 0 .. 2^20: -1, refused by libvo */
+            const double v = o[at[k]];
+            *f[k] = (v >= 0.0 && v <= 1048576.0 && v == (double)(int32_t)v) ? (int32_t)v : -1;
+        }
+        cp.min_quality = (float)o[2];
+    }
+    const int rows = (int)mxGetM(I), cols = (int)mxGetN(I);
+    float* loc = (float*)mxMalloc(sizeof(float) * 2 * VO_MEX_CORNER_CAP);
+    float* met = (float*)mxMalloc(sizeof(float) * VO_MEX_CORNER_CAP);
+    int n = 0;
+    need_ctx(rows, cols);
+    const int rc = vo_detect_corners(g_ctx, mxGetUint8s(I), rows, cols, rows, 1, &cp, loc, met, VO_MEX_CORNER_CAP, &n);
+    if (rc != VO_OK) { mxFree(loc); mxFree(met); check(rc); }
+    plhs[0] = mxCreateNumericMatrix(n, 2, mxSINGLE_CLASS, mxREAL);
+    float* P = n ? mxGetSingles(plhs[0]) : NULL;
+    for (int i = 0; i < n; ++i) { P[i] = loc[2 * i]; P[(size_t)n + i] = loc[2 * i + 1]; }
+    if (nlhs > 1) {
+        plhs[1] = mxCreateNumericMatrix(n, 1, mxSINGLE_CLASS, mxREAL);
+        float* M = n ? mxGetSingles(plhs[1]) : NULL;
+        for (int i = 0; i < n; ++i) M[i] = met[i];
+    }
+    mxFree(loc); mxFree(met);
+}
+
 /* CreateLandmarksFromFeatures(features_l, features_r, P1, P2, pose, ~) rows (:2-18): VO.m:145-158
  * has already filtered the points, so libvo's own filter runs against no old points (K = 0). */
 static void cmd_landmarks(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
@@ -930,6 +983,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "refinepose")) cmd_refinepose(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fundamental")) cmd_fundamental(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "trackpoints")) cmd_trackpoints(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "corners")) cmd_corners(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks")) cmd_landmarks(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step")) cmd_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks_all")) cmd_landmarks_all(nlhs, plhs, nrhs, prhs);

@@ -164,6 +164,7 @@ struct vo_ctx {
     MatchRadiusBuffers mr;           // vo_match_radius / vo_match_radius_f32 (allocated on first use)
     FundBuffers fund;                // vo_est_fundamental / vo_est_fundamental_batch (allocated on first use)
     KltBuffers klt;                  // vo_track_points / vo_track_points_batch (allocated on first use)
+    CornerBuffers corner;            // vo_detect_corners / vo_detect_corners_batch (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
@@ -250,6 +251,11 @@ void vo_default_klt_params(vo_klt_params* p)
 {
     p->num_pyramid_levels = 3; p->block_size[0] = 31; p->block_size[1] = 31; p->max_iterations = 30;
     p->max_bidirectional_error = vo_u32_as_f32(0x7f800000u);
+}
+void vo_default_corner_params(vo_corner_params* p)
+{
+    p->method = VO_CORNER_MINEIG; p->filter_size = 5; p->min_quality = 0.01f; p->strongest = 0;
+    for (int k = 0; k < 4; ++k) p->roi[k] = 0;
 }
 
 const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -2265,6 +2271,100 @@ int vo_fetch_klt_level(vo_ctx* c, int image, int level, uint8_t* out, int capaci
     const size_t i = (size_t)(image & 1) * kb.last_pairs + (image >> 1);
     HIPC(c, hipMemcpyAsync(out, kb.planes + klt_level_offset(c->rows, c->cols, kb.last_pairs, level) + i * r * q, (size_t)r * q,
                            hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+// ---- detectMinEigenFeatures / detectHarrisFeatures (vo.h: "cornerPoints") ------------------------
+// -> nullptr when the block is inside the ranges of include/vo.h, else the offending field; roi0 = the
+// ROI 0-based (the whole image for w = 0)
+static const char* corner_params_refusal(const vo_corner_params& p, int rows, int cols, int max_keypoints, int* roi0)
+{
+    if (p.method != VO_CORNER_MINEIG && p.method != VO_CORNER_HARRIS) return "method (VO_CORNER_MINEIG | VO_CORNER_HARRIS)";
+    if (p.filter_size < VO_CORNER_MIN_FILTER || p.filter_size > VO_CORNER_MAX_FILTER || !(p.filter_size & 1))
+        return "filter_size (odd, 3 .. 15)";
+    if (!(p.min_quality >= 0.0f && p.min_quality <= 1.0f)) return "min_quality (0 .. 1)";
+    if (p.strongest < 0 || p.strongest > max_keypoints) return "strongest (0, or 1 .. max_keypoints)";
+    if (p.roi[2] == 0) { roi0[0] = 0; roi0[1] = 0; roi0[2] = cols; roi0[3] = rows; return nullptr; }
+    if (p.roi[2] < 1 || p.roi[3] < 1) return "roi (w, h >= 1)";
+    if (p.roi[0] < 1 || p.roi[1] < 1 || p.roi[0] > cols || p.roi[1] > rows || p.roi[2] > cols - (p.roi[0] - 1) ||
+        p.roi[3] > rows - (p.roi[1] - 1))
+        return "roi (x y w h, 1-based, inside the image)";
+    roi0[0] = p.roi[0] - 1; roi0[1] = p.roi[1] - 1; roi0[2] = p.roi[2]; roi0[3] = p.roi[3];
+    return nullptr;
+}
+
+int vo_detect_corners_batch(vo_ctx* c, const uint8_t* imgs, int ld, int col_major, int n_img, const vo_corner_params* params,
+                            float* loc, float* metric, int stride, int32_t* n_out, int32_t* status)
+{
+    const char* who = "vo_detect_corners";
+    if (!c || !imgs || !n_out || !status || n_img < 1 || n_img > 2 * c->max_batch || stride < 0 || (stride > 0 && (!loc || !metric)) ||
+        (col_major != 0 && col_major != 1) || ld < (col_major ? c->rows : c->cols))
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    // every refusal before anything is enqueued
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    const int K = c->set[0].sb.kp_cap;
+    vo_corner_params p;
+    if (params) p = *params; else vo_default_corner_params(&p);
+    int roi0[4];
+    if (const char* field = corner_params_refusal(p, c->rows, c->cols, K, roi0))
+        return fail(c, VO_ERR_ARG, "%s: parameter out of range: %s", who, field);
+    CallScope call(c); if (call.status) return call.status;
+    CornerBuffers& cb = c->corner;
+    {
+        const hipError_t e = corner_reserve(c->pool, cb, c->rows, c->cols, n_img, 4 * K);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t fs = (size_t)c->rows * c->cols;
+    if (!col_major && ld == c->cols) HIPC(c, hipMemcpyAsync(cb.img, imgs, fs * n_img, hipMemcpyHostToDevice, c->stream));
+    else { int rc = stage_images(c, imgs, ld, col_major, n_img, cb.img); if (rc) return rc; }
+    HIPC(c, corner_launch(cb, c->rows, c->cols, n_img, p, roi0, c->stream));
+    cb.last_img = n_img;
+    std::vector<int> total((size_t)n_img);
+    HIPC(c, hipMemcpyAsync(total.data(), cb.total, sizeof(int) * n_img, hipMemcpyDeviceToHost, c->stream));
+    int rc = finish(c);
+    if (rc) return rc;
+    const float* d_loc = p.strongest > 0 ? cb.sloc : cb.loc;
+    const float* d_met = p.strongest > 0 ? cb.smet : cb.met;
+    for (int i = 0; i < n_img; ++i) {
+        const int count = total[i];
+        const int n_ret = p.strongest > 0 ? std::min(count, p.strongest) : count;
+        if (count > cb.list_cap || n_ret > stride) {
+            n_out[i] = count > cb.list_cap ? count : n_ret;
+            status[i] = VO_ERR_CAPACITY;
+            continue;
+        }
+        n_out[i] = n_ret; status[i] = VO_OK;
+        if (!n_ret) continue;
+        HIPC(c, hipMemcpy(loc + (size_t)i * stride * 2, d_loc + (size_t)i * cb.list_cap * 2, sizeof(float) * 2 * n_ret, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(metric + (size_t)i * stride, d_met + (size_t)i * cb.list_cap, sizeof(float) * n_ret, hipMemcpyDeviceToHost));
+    }
+    return VO_OK;
+}
+
+int vo_detect_corners(vo_ctx* c, const uint8_t* img, int rows, int cols, int ld, int col_major, const vo_corner_params* params,
+                      float* loc, float* metric, int capacity, int* n_out)
+{
+    if (!c || rows != c->rows || cols != c->cols || capacity < 0 || !n_out) return fail(c, VO_ERR_ARG, "vo_detect_corners: bad arguments");
+    int32_t n = 0, st = VO_OK;
+    const int rc = vo_detect_corners_batch(c, img, ld, col_major, 1, params, loc, metric, capacity, &n, &st);
+    if (rc) return rc;
+    *n_out = n;
+    if (st == VO_ERR_CAPACITY)
+        return fail(c, VO_ERR_CAPACITY, "vo_detect_corners: %d corners exceed the device list (%d = 4 x max_keypoints) or the capacity %d", n,
+                    c->corner.list_cap, capacity);
+    return st;
+}
+
+int vo_fetch_corner_metric(vo_ctx* c, int image, float* out, int capacity)
+{
+    if (!c || image < 0) return fail(c, VO_ERR_ARG, "vo_fetch_corner_metric: bad arguments");
+    const CornerBuffers& cb = c->corner;
+    if (cb.last_img == 0) return fail(c, VO_ERR_STATE, "vo_fetch_corner_metric: no vo_detect_corners call has launched yet");
+    if (image >= cb.last_img) return fail(c, VO_ERR_ARG, "vo_fetch_corner_metric: image %d outside the last call's %d images", image, cb.last_img);
+    const size_t fs = (size_t)c->rows * c->cols;
+    if (!out || capacity < 0 || (size_t)capacity < fs) return fail(c, VO_ERR_CAPACITY, "vo_fetch_corner_metric: %zu floats needed", fs);
+    CallScope call(c); if (call.status) return call.status;
+    HIPC(c, hipMemcpyAsync(out, cb.metric + (size_t)image * fs, sizeof(float) * fs, hipMemcpyDeviceToHost, c->stream));
     return finish(c);
 }
 

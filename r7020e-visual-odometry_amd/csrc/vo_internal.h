@@ -341,4 +341,23 @@ void klt_pyr_launch(KltBuffers& kb, int rows, int cols, int n_pairs, int levels,
 void klt_track_launch(KltBuffers& kb, int rows, int cols, int n_pairs, int pts_stride, int max_n, bool has_guess,
                       const vo_klt_params& p, hipStream_t s);
 
+// ---- detectMinEigenFeatures / detectHarrisFeatures (corner.hip): vo_detect_corners[_batch] ----
+// Buffers of their own, allocated by corner_reserve at the first launching call and grown to the
+// largest batch seen, so the loop's buffer sets are never touched.  list_cap = 4 x max_keypoints.
+struct CornerBuffers {
+    int cap_img = 0, list_cap = 0;
+    int last_img = 0;                             // of the last launching call (vo_fetch_corner_metric)
+    uint8_t* img = nullptr;                       // [n_img][rows][cols]
+    float* metric = nullptr;                      // [n_img][rows][cols]
+    uint32_t* mmax = nullptr;                     // [n_img] the ROI's maximum, as the bits of a float >= 0
+    int* cnt = nullptr;                           // [n_img][chunks of the whole image]
+    int* total = nullptr;                         // [n_img] the true count
+    float* loc = nullptr; float* met = nullptr;   // [n_img][list_cap][2], [n_img][list_cap]: raster order
+    float* sloc = nullptr; float* smet = nullptr; // the same, ranked (strongest > 0)
+};
+hipError_t corner_reserve(DevPool& pool, CornerBuffers& cb, int rows, int cols, int n_img, int list_cap);   // all or nothing
+// k_corner_metric, k_corner_count, k_corner_emit and, with p.strongest > 0, k_corner_rank over cb.img;
+// roi0 = x y w h, 0-based, inside the image
+hipError_t corner_launch(CornerBuffers& cb, int rows, int cols, int n_img, const vo_corner_params& p, const int* roi0, hipStream_t s);
+
 }  // namespace vo

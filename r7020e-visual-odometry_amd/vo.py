@@ -14,6 +14,7 @@ running on the MI355X through libvo.so:
     bundleAdjustmentMotion                 after VO.m:123-127 (refine_pose, set_pose_refinement)
     estimateFundamentalMatrix              after matchFeatures (est_fundamental, est_fundamental_batch)
     vision.PointTracker                    pyramidal KLT between frames or cameras (track_points, PointTracker)
+    detectMinEigenFeatures / detectHarrisFeatures   cornerPoints for the tracker (detect_corners, detect_corners_batch)
     CreateLandmarksFromFeatures           CreateLandmarksFromFeatures.m:1-21
     VisualOdometry.step                    the VO.m loop body (VO.m:70-161)
 
@@ -93,6 +94,13 @@ class KltInfo(C.Structure):
                 ("bidir_error", C.c_float)]
 
 
+class CornerParams(C.Structure):
+    """vo_corner_params: method (VO_CORNER_MINEIG | VO_CORNER_HARRIS), FilterSize, MinQuality, strongest (0: all)
+    and ROI (x y w h, 1-based; w = 0: the whole image)."""
+    _fields_ = [("method", C.c_int32), ("filter_size", C.c_int32), ("min_quality", C.c_float), ("strongest", C.c_int32),
+                ("roi", C.c_int32 * 4)]
+
+
 class RefineStats(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("passes", C.c_int32), ("accepted", C.c_int32),
                 ("cost_initial", C.c_double), ("cost_final", C.c_double)]
@@ -146,6 +154,8 @@ KLT_INFO_DTYPE = np.dtype([("status", "u1"), ("stop", "u1"), ("iterations", "u1"
                            ("bidir_error", "<f4")])
 KLT_MAX_COORD = 1048576.0
 
+VO_CORNER_MINEIG, VO_CORNER_HARRIS = 0, 1
+
 # exported symbols (tests check the library exports every one)
 EXPORTS = [
     "vo_default_sift_params", "vo_default_match_params", "vo_default_ransac_params", "vo_create", "vo_destroy",
@@ -165,6 +175,7 @@ EXPORTS = [
     "vo_match_radius", "vo_match_radius_f32",
     "vo_default_fund_params", "vo_est_fundamental", "vo_est_fundamental_batch",
     "vo_default_klt_params", "vo_track_points", "vo_track_points_batch", "vo_fetch_klt_level",
+    "vo_default_corner_params", "vo_detect_corners", "vo_detect_corners_batch", "vo_fetch_corner_metric",
 ]
 
 _libs: dict = {}
@@ -260,6 +271,14 @@ def load_library(path: str | os.PathLike | None = None):
                                             P(C.c_int32), C.c_int, P(KltParams), P(C.c_float), P(C.c_uint8), P(C.c_float),
                                             P(KltInfo)]
         L.vo_fetch_klt_level.argtypes = [vp, C.c_int, C.c_int, P(C.c_uint8), C.c_int, P(C.c_int), P(C.c_int)]
+    if hasattr(L, "vo_detect_corners"):      # (absent from an older library timed beside this one)
+        L.vo_default_corner_params.argtypes = [P(CornerParams)]
+        L.vo_default_corner_params.restype = None
+        L.vo_detect_corners.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(CornerParams), P(C.c_float),
+                                        P(C.c_float), C.c_int, P(C.c_int)]
+        L.vo_detect_corners_batch.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(CornerParams), P(C.c_float),
+                                              P(C.c_float), C.c_int, P(C.c_int32), P(C.c_int32)]
+        L.vo_fetch_corner_metric.argtypes = [vp, C.c_int, P(C.c_float), C.c_int]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
                                P(C.c_double), P(C.c_double), C.c_int, P(C.c_int)]
     L.vo_step.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(StepOut)]
@@ -457,6 +476,40 @@ def klt_points(points, who: str = "track_points", name: str = "points") -> np.nd
     if len(bad):
         raise VOError(VO_ERR_ARG, f"{who}: {name} row {int(bad[0])} must be finite and below 2^20 in magnitude")
     return a
+
+
+def default_corner_params(**overrides) -> CornerParams:
+    """vo_default_corner_params (VO_CORNER_MINEIG, FilterSize 5, MinQuality 0.01, all corners, the whole image),
+    with any field overridden by keyword (roi: (x, y, w, h), 1-based, or None).  Host only: no library, no device."""
+    p = CornerParams(VO_CORNER_MINEIG, 5, 0.01, 0, (C.c_int32 * 4)(0, 0, 0, 0))
+    for k, v in overrides.items():
+        if k not in dict(CornerParams._fields_):
+            raise VOError(VO_ERR_ARG, f"default_corner_params: no field {k}")
+        if k == "roi":
+            v = (C.c_int32 * 4)(0, 0, 0, 0) if v is None else (C.c_int32 * 4)(*(int(e) for e in v))
+        setattr(p, k, v)
+    return p
+
+
+def check_corner_params(p: CornerParams, rows: int, cols: int, max_keypoints: int) -> None:
+    """vo_detect_corners' parameter ranges (include/vo.h), checked on the host: VOError(VO_ERR_ARG) naming the
+    offending field."""
+    bad = None
+    x, y, w, h = p.roi
+    if p.method not in (VO_CORNER_MINEIG, VO_CORNER_HARRIS):
+        bad = "method (VO_CORNER_MINEIG | VO_CORNER_HARRIS)"
+    elif not (3 <= p.filter_size <= 15 and p.filter_size % 2 == 1):
+        bad = "filter_size (odd, 3 .. 15)"
+    elif not 0.0 <= p.min_quality <= 1.0:
+        bad = "min_quality (0 .. 1)"
+    elif not 0 <= p.strongest <= max_keypoints:
+        bad = "strongest (0, or 1 .. max_keypoints)"
+    elif w != 0 and (w < 1 or h < 1):
+        bad = "roi (w, h >= 1)"
+    elif w != 0 and (x < 1 or y < 1 or x > cols or y > rows or w > cols - (x - 1) or h > rows - (y - 1)):
+        bad = "roi (x y w h, 1-based, inside the image)"
+    if bad:
+        raise VOError(VO_ERR_ARG, f"detect_corners: parameter out of range: {bad}")
 
 
 def _refine_stats(s: RefineStats) -> np.ndarray:
@@ -1043,6 +1096,63 @@ class Context:
         self._check(self.lib.vo_fetch_klt_level(self.h, image, level, _p(out, C.c_uint8), out.size, C.byref(r), C.byref(q)))
         return out[: r.value * q.value].reshape(r.value, q.value).copy()
 
+    # ---- detectMinEigenFeatures / detectHarrisFeatures ----
+    def detect_corners(self, img: np.ndarray, params: CornerParams | None = None, capacity: int | None = None):
+        """cornerPoints of one image (vo_detect_corners) -> (Location [n][2] float32 = (x, y) 1-based, Metric [n]
+        float32), ascending in (row, column), or the params.strongest strongest.  capacity: rows the call may
+        return (default: the device list's 4 x max_keypoints).  More corners than that: VOError(VO_ERR_CAPACITY)
+        whose .count is the true count.  The image goes through as it lies (see sift)."""
+        img = np.asarray(img, np.uint8)
+        if img.ndim != 2:
+            raise VOError(VO_ERR_ARG, "detect_corners: a 2-D uint8 image")
+        rows, cols = img.shape
+        if rows > 1 and img.strides[0] == 1 and img.strides[1] >= rows:
+            col_major, ld = 1, img.strides[1]
+        elif img.strides[1] == 1 and img.strides[0] >= cols:
+            col_major, ld = 0, img.strides[0]
+        else:
+            img = np.ascontiguousarray(img)
+            col_major, ld = 0, cols
+        p = params if params is not None else default_corner_params()
+        check_corner_params(p, self.rows, self.cols, self.sift_params.max_keypoints)
+        cap = 4 * self.sift_params.max_keypoints if capacity is None else int(capacity)
+        loc = np.zeros((max(cap, 1), 2), np.float32)
+        met = np.zeros(max(cap, 1), np.float32)
+        n = C.c_int(0)
+        rc = self.lib.vo_detect_corners(self.h, _p(img, C.c_uint8), rows, cols, ld, col_major, C.byref(p), _p(loc, C.c_float),
+                                        _p(met, C.c_float), cap, C.byref(n))
+        if rc == VO_ERR_CAPACITY:
+            e = VOError(rc, self.lib.vo_last_error(self.h).decode())
+            e.count = n.value
+            raise e
+        self._check(rc)
+        return loc[: n.value].copy(), met[: n.value].copy()
+
+    def detect_corners_batch(self, imgs: np.ndarray, params: CornerParams | None = None, capacity: int | None = None) -> list:
+        """vo_detect_corners_batch: imgs [n_img, rows, cols] -> one (Location, Metric, status, count) per image;
+        status VO_OK, or VO_ERR_CAPACITY with empty arrays and the true count."""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        if imgs.ndim != 3:
+            raise VOError(VO_ERR_ARG, "detect_corners_batch: imgs [n_img, rows, cols]")
+        B = imgs.shape[0]
+        p = params if params is not None else default_corner_params()
+        check_corner_params(p, self.rows, self.cols, self.sift_params.max_keypoints)
+        cap = 4 * self.sift_params.max_keypoints if capacity is None else int(capacity)
+        loc = np.zeros((max(B, 1), max(cap, 1), 2), np.float32)
+        met = np.zeros((max(B, 1), max(cap, 1)), np.float32)
+        n, st = np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int32)
+        self._check(self.lib.vo_detect_corners_batch(self.h, _p(imgs, C.c_uint8), imgs.shape[2], 0, B, C.byref(p), _p(loc, C.c_float),
+                                                     _p(met, C.c_float), cap, _p(n, C.c_int32), _p(st, C.c_int32)))
+        return [(loc[i, : n[i]].copy(), met[i, : n[i]].copy(), VO_OK, int(n[i])) if st[i] == VO_OK else
+                (np.zeros((0, 2), np.float32), np.zeros(0, np.float32), int(st[i]), int(n[i])) for i in range(B)]
+
+    def fetch_corner_metric(self, image: int = 0) -> np.ndarray:
+        """Diagnostic (vo_fetch_corner_metric): the metric plane [rows, cols] float32 of image `image` of the last
+        detect_corners call."""
+        out = np.zeros((self.rows, self.cols), np.float32)
+        self._check(self.lib.vo_fetch_corner_metric(self.h, image, _p(out, C.c_float), out.size))
+        return out
+
     # ---- new-landmark filter + CreateLandmarksFromFeatures ----
     def landmarks(self, l_pos, r_pos, old_l, old_r, pose) -> np.ndarray:
         a = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (l_pos, r_pos, old_l, old_r)]
@@ -1381,3 +1491,23 @@ class PointTracker:
         scores[idx] = sc
         self.image = I.copy()
         return self.points.copy(), self.validity.copy(), scores
+
+
+def _detect_corners(I, method: int, MinQuality: float, FilterSize: int, ROI):
+    I = np.asarray(I)
+    if I.ndim != 2 or I.dtype != np.uint8:
+        raise VOError(VO_ERR_ARG, "a 2-D uint8 image")
+    p = default_corner_params(method=method, min_quality=float(MinQuality), filter_size=int(FilterSize), roi=ROI)
+    return _default_ctx(*I.shape).detect_corners(I, p)
+
+
+def detectMinEigenFeatures(I, MinQuality: float = 0.01, FilterSize: int = 5, ROI=None):
+    """detectMinEigenFeatures(I, MinQuality = , FilterSize = , ROI = ) -> (Location [n][2] (x, y) 1-based, Metric [n]):
+    Shi-Tomasi corners, the points vision.PointTracker is initialised with."""
+    return _detect_corners(I, VO_CORNER_MINEIG, MinQuality, FilterSize, ROI)
+
+
+def detectHarrisFeatures(I, MinQuality: float = 0.01, FilterSize: int = 5, ROI=None):
+    """detectHarrisFeatures(I, MinQuality = , FilterSize = , ROI = ) -> (Location, Metric): Harris-Stephens corners,
+    det - 0.04 trace^2 of the same smoothed gradient matrix."""
+    return _detect_corners(I, VO_CORNER_HARRIS, MinQuality, FilterSize, ROI)
