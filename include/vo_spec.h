@@ -29,9 +29,11 @@
 
 #if defined(__HIPCC__)
 #define VO_HD __host__ __device__ __forceinline__
+#define VO_UNROLL _Pragma("unroll")
 #else
 #include <math.h>
 #define VO_HD static inline
+#define VO_UNROLL
 #endif
 
 /* ------------------------------------------------------------------------ */
@@ -460,6 +462,288 @@ VO_HD uint8_t vo_undistort_u8(double t00, double t01, double t10, double t11, do
 }
 
 /* ------------------------------------------------------------------------ */
+/* triangulate and estworldpose: the DLT point, Grunert's   */
+/* P3P on either side of its root finder, and the pose MSAC's sample, trial  */
+/* bound, replay and camera pose.  One definition for the kernels            */
+/* (k_gather_tri, k_tri_list, k_lm_tri, k_msac; geom.hip) and the oracle     */
+/* (oracle/vo_ref.c), equal by bytes: f64 + - * / and sqrt in the order      */
+/* written, no contraction, vo_log_d the only transcendental.  The float64   */
+/* numpy references of tests/geom_ref.py are the independent check.          */
+/* ------------------------------------------------------------------------ */
+/* One point from two views: the null vector of the 4x4 DLT system by one-sided Jacobi (Hestenes),
+ * at most 30 sweeps, rotations skipped at |g| <= 1e-15 sqrt(a b); the column of the smallest norm
+ * (the first of equals), dehomogenised and rounded through single as MATLAB returns single for
+ * single inputs.  P1 / P2 3x4 row-major.  Every index is a compile-time constant once unrolled,
+ * which keeps A and V in registers on the device. */
+VO_HD void vo_dlt_point(float u1f, float v1f, float u2f, float v2f, const double* P1, const double* P2, double* X)
+{
+    double u1 = u1f, v1 = v1f, u2 = u2f, v2 = v2f;
+    double A[4][4];   /* A[row][col] */
+    VO_UNROLL
+    for (int c = 0; c < 4; ++c) {
+        A[0][c] = u1 * P1[8 + c] - P1[c];
+        A[1][c] = v1 * P1[8 + c] - P1[4 + c];
+        A[2][c] = u2 * P2[8 + c] - P2[c];
+        A[3][c] = v2 * P2[8 + c] - P2[4 + c];
+    }
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        int rotated = 0;
+        VO_UNROLL
+        for (int p = 0; p < 3; ++p)
+            VO_UNROLL
+            for (int q = p + 1; q < 4; ++q) {
+                double al = 0, be = 0, ga = 0;
+                VO_UNROLL
+                for (int i = 0; i < 4; ++i) {
+                    al = al + A[i][p] * A[i][p];
+                    be = be + A[i][q] * A[i][q];
+                    ga = ga + A[i][p] * A[i][q];
+                }
+                if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
+                rotated = 1;
+                double zeta = (be - al) / (2.0 * ga);
+                double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                double c = 1.0 / sqrt(1.0 + t * t);
+                double s = c * t;
+                VO_UNROLL
+                for (int i = 0; i < 4; ++i) {
+                    double ap = A[i][p], aq = A[i][q];
+                    A[i][p] = c * ap - s * aq;
+                    A[i][q] = s * ap + c * aq;
+                    double vp = V[i][p], vq = V[i][q];
+                    V[i][p] = c * vp - s * vq;
+                    V[i][q] = s * vp + c * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    int jmin = 0;
+    double nmin = 0;
+    VO_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        double nj = 0;
+        VO_UNROLL
+        for (int i = 0; i < 4; ++i) nj = nj + A[i][j] * A[i][j];
+        if (j == 0 || nj < nmin) { nmin = nj; jmin = j; }
+    }
+    double x = 0, y = 0, z = 0, w = 1;   /* column jmin, selected without a runtime index */
+    VO_UNROLL
+    for (int j = 0; j < 4; ++j)
+        if (j == jmin) { x = V[0][j]; y = V[1][j]; z = V[2][j]; w = V[3][j]; }
+    X[0] = (double)(float)(x / w);
+    X[1] = (double)(float)(y / w);
+    X[2] = (double)(float)(z / w);
+}
+
+/* Squared pixel error of X under Xc = R X + t (R 3x3 row-major) and the intrinsics K (fx = K[0],
+ * s = K[1], cx = K[2], fy = K[4], cy = K[5]); +inf for a point not in front of the camera. */
+VO_HD double vo_pose_reproj_err2(const double* R, const double* t, const double* K, const double* X, const double* uv)
+{
+    double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
+    double yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
+    double zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
+    if (!(zc > 0)) return INFINITY;
+    double xn = xc / zc, yn = yc / zc;
+    double u = K[0] * xn + K[1] * yn + K[2];
+    double v = K[4] * yn + K[5];
+    double du = u - uv[0], dv = v - uv[1];
+    return du * du + dv * dv;
+}
+
+/* P3P: Grunert's quartic in v = s3 / s1 (Haralick et al. 1994), coefficients by polynomial algebra.
+ * vo_p3p_setup builds the quartic P of three correspondences, the caller finds its real roots in
+ * ascending order with its own root finder (the oracle's recursive real_roots, the kernel's
+ * register-resident templates), and vo_p3p_pose turns one root into a pose.  The caller owns the
+ * loop over the roots and stops at the fourth pose. */
+VO_HD void vo_p3p_pmul(const double* a, int da, const double* b, int db, double* out)
+{
+    for (int i = 0; i <= da + db; ++i) out[i] = 0.0;
+    for (int i = 0; i <= da; ++i)
+        for (int j = 0; j <= db; ++j) out[i + j] = out[i + j] + a[i] * b[j];
+}
+
+VO_HD void vo_p3p_bearing(const double* K, double u, double v, double* f)
+{
+    double yn = (v - K[5]) / K[4];
+    double xn = (u - K[2] - K[1] * yn) / K[0];
+    double n = sqrt(xn * xn + yn * yn + 1.0);
+    f[0] = xn / n; f[1] = yn / n; f[2] = 1.0 / n;
+}
+
+VO_HD void vo_p3p_cross3(const double* a, const double* b, double* c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+VO_HD int vo_p3p_normalize3(double* a)
+{
+    double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (!(n > 0)) return 0;
+    a[0] = a[0] / n; a[1] = a[1] / n; a[2] = a[2] / n;
+    return 1;
+}
+
+/* rotation R (row-major) and t with Pc = R Pw + t from 3 congruent points */
+VO_HD int vo_p3p_align3(const double Pw[3][3], const double Pc[3][3], double* R, double* t)
+{
+    double ew[3][3], ec[3][3];   /* ew[k] = k-th basis vector */
+    double d1[3], d2[3];
+    for (int i = 0; i < 3; ++i) { ew[0][i] = Pw[1][i] - Pw[0][i]; d1[i] = Pw[2][i] - Pw[0][i]; }
+    if (!vo_p3p_normalize3(ew[0])) return 0;
+    vo_p3p_cross3(ew[0], d1, ew[2]);
+    if (!vo_p3p_normalize3(ew[2])) return 0;
+    vo_p3p_cross3(ew[2], ew[0], ew[1]);
+    for (int i = 0; i < 3; ++i) { ec[0][i] = Pc[1][i] - Pc[0][i]; d2[i] = Pc[2][i] - Pc[0][i]; }
+    if (!vo_p3p_normalize3(ec[0])) return 0;
+    vo_p3p_cross3(ec[0], d2, ec[2]);
+    if (!vo_p3p_normalize3(ec[2])) return 0;
+    vo_p3p_cross3(ec[2], ec[0], ec[1]);
+    /* R = Ec * Ew^T : R[i][j] = sum_k ec[k][i] * ew[k][j] */
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = ec[0][i] * ew[0][j] + ec[1][i] * ew[1][j] + ec[2][i] * ew[2][j];
+    double mw[3], mc[3];
+    for (int i = 0; i < 3; ++i) {
+        mw[i] = (Pw[0][i] + Pw[1][i] + Pw[2][i]) / 3.0;
+        mc[i] = (Pc[0][i] + Pc[1][i] + Pc[2][i]) / 3.0;
+    }
+    for (int i = 0; i < 3; ++i) t[i] = mc[i] - (R[3 * i] * mw[0] + R[3 * i + 1] * mw[1] + R[3 * i + 2] * mw[2]);
+    return 1;
+}
+
+/* j: unit bearings of the image points; u = N(v) / D(v), s1 = sqrt(b2 / Q(v));
+ * P = D^2 + N^2 - 2 cg N D - (c2 / b2) Q D^2, coefficient i at x^i */
+typedef struct { double j[3][3], b2, N[3], D[2], Q[3], P[5]; } vo_p3p;
+
+/* returns 0 for a degenerate world triangle (two points coincide, or a NaN) */
+VO_HD int vo_p3p_setup(const double img[3][2], const double world[3][3], const double* K, vo_p3p* s)
+{
+    for (int i = 0; i < 3; ++i) vo_p3p_bearing(K, img[i][0], img[i][1], s->j[i]);
+    double dv[3];
+    for (int i = 0; i < 3; ++i) dv[i] = world[1][i] - world[2][i];
+    double a2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+    for (int i = 0; i < 3; ++i) dv[i] = world[0][i] - world[2][i];
+    double b2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+    for (int i = 0; i < 3; ++i) dv[i] = world[0][i] - world[1][i];
+    double c2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+    if (!(a2 > 0 && b2 > 0 && c2 > 0)) return 0;
+    double ca = s->j[1][0] * s->j[2][0] + s->j[1][1] * s->j[2][1] + s->j[1][2] * s->j[2][2];  /* cos alpha: rays 2,3 */
+    double cb = s->j[0][0] * s->j[2][0] + s->j[0][1] * s->j[2][1] + s->j[0][2] * s->j[2][2];  /* cos beta:  rays 1,3 */
+    double cg = s->j[0][0] * s->j[1][0] + s->j[0][1] * s->j[1][1] + s->j[0][2] * s->j[1][2];  /* cos gamma: rays 1,2 */
+    double Kq = (a2 - c2) / b2, cb2 = c2 / b2;
+    s->b2 = b2;
+    s->N[0] = 1.0 + Kq; s->N[1] = -2.0 * Kq * cb; s->N[2] = Kq - 1.0;
+    s->D[0] = 2.0 * cg; s->D[1] = -2.0 * ca;
+    s->Q[0] = 1.0; s->Q[1] = -2.0 * cb; s->Q[2] = 1.0;
+    double DD[3], NN[5], ND[4], QDD[5];
+    vo_p3p_pmul(s->D, 1, s->D, 1, DD);
+    vo_p3p_pmul(s->N, 2, s->N, 2, NN);
+    vo_p3p_pmul(s->N, 2, s->D, 1, ND);
+    vo_p3p_pmul(s->Q, 2, DD, 2, QDD);
+    for (int i = 0; i < 5; ++i) {
+        double v = NN[i] - cb2 * QDD[i];
+        if (i < 3) v = v + DD[i];
+        if (i < 4) v = v - 2.0 * cg * ND[i];
+        s->P[i] = v;
+    }
+    return 1;
+}
+
+/* The pose of root v: 1 and (R, t) with Xc = R Xw + t when v > 0, D(v) != 0, u > 0, Q(v) > 0 and
+ * the two triangles align; world is the triangle given to vo_p3p_setup. */
+VO_HD int vo_p3p_pose(const vo_p3p* s, const double world[3][3], double v, double* R, double* t)
+{
+    if (!(v > 0)) return 0;
+    double Dv = s->D[0] + s->D[1] * v;
+    if (Dv == 0.0) return 0;
+    double u = (s->N[0] + s->N[1] * v + s->N[2] * v * v) / Dv;
+    if (!(u > 0)) return 0;
+    double Qv = s->Q[0] + s->Q[1] * v + s->Q[2] * v * v;
+    if (!(Qv > 0)) return 0;
+    double s1 = sqrt(s->b2 / Qv), s2 = u * s1, s3 = v * s1;
+    double Pc[3][3];
+    for (int i = 0; i < 3; ++i) { Pc[0][i] = s1 * s->j[0][i]; Pc[1][i] = s2 * s->j[1][i]; Pc[2][i] = s3 * s->j[2][i]; }
+    return vo_p3p_align3(world, Pc, R, t);
+}
+
+/* Slot `slot` of the frame with key `key`: up to 16 attempts, each 4 indices from one Philox call
+ * (counter {slot, attempt, key, 0x5EED}, key words {seed, 0x9E3779B9}); the first attempt whose 4
+ * indices are distinct is the sample.  Returns 0 when all 16 fail (n < 4 always does). */
+VO_HD int vo_pose_sample(uint32_t seed, uint32_t key, uint32_t slot, uint32_t n, uint32_t* idx)
+{
+    for (uint32_t att = 0; att < 16; ++att) {
+        vo_u32x4 c = {{slot, att, key, 0x5EEDu}};
+        vo_u32x4 r = vo_philox4x32_10(c, seed, 0x9E3779B9u);
+        for (int q = 0; q < 4; ++q) idx[q] = vo_rand_index(r.v[q], n);
+        if (idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] && idx[2] != idx[3])
+            return 1;
+    }
+    return 0;
+}
+
+/* Trials after which a sample of 4 inliers was drawn with probability conf (a fraction), at the
+ * inlier ratio w = n_in / n: ceil(log(1 - conf) / log(1 - w^4)) clamped to [1, INT_MAX], w^4 =
+ * ((w w) w) w.  w^4 <= 1e-300 (or NaN) gives INT_MAX: no bound.  At w = 1 the logarithm is -inf, the
+ * quotient +0 and the result 1.  A logarithm that is not negative -- the 0 of a w^4 below half an ulp
+ * of 1 -- gives 1.  This is not vo_fund_trials_needed with another exponent and stays apart from it:
+ * that one tests w^8 >= 1 first and answers a zero logarithm with "no bound" (DESIGN 3.5.2). */
+VO_HD int vo_pose_trials_needed(int n_in, int n, double conf)
+{
+    double w = (double)n_in / (double)n;
+    double w4 = w * w * w * w;
+    if (!(w4 > 1e-300)) return 0x7fffffff;
+    double den = vo_log_d(1.0 - w4);
+    if (!(den < 0)) return 1;
+    double num = vo_log_d(1.0 - conf);
+    double N = ceil(num / den);
+    if (N > 2147483647.0) return 0x7fffffff;
+    if (N < 1.0) return 1;
+    return (int)N;
+}
+
+/* The sequential MSAC loop, replayed slot by slot in slot order over (valid, score, n_in):
+ *     vo_pose_replay_begin(&r, max_num_trials);
+ *     for slot = 0 .. max_num_trials - 1, while !vo_pose_replay_done(&r):  vo_pose_replay_slot(...)
+ * An invalid slot (no 4 distinct indices, or a sample without a pose) counts as no trial.  A valid
+ * one counts, and replaces the best iff its score is strictly smaller; the bound is then
+ * min(bound, vo_pose_trials_needed).  Done once trials >= bound.  Returns 1 when the slot became
+ * the best (a caller that does not keep every slot keeps its R, t). */
+typedef struct { int bound, trials, best, best_in; double best_score; } vo_pose_replay;
+
+VO_HD void vo_pose_replay_begin(vo_pose_replay* r, int max_num_trials)
+{
+    r->bound = max_num_trials; r->trials = 0; r->best = -1; r->best_in = 0;
+    r->best_score = INFINITY;
+}
+
+VO_HD int vo_pose_replay_done(const vo_pose_replay* r) { return r->trials >= r->bound; }
+
+VO_HD int vo_pose_replay_slot(vo_pose_replay* r, int slot, int valid, double score, int n_in, int n, double conf)
+{
+    if (!valid) return 0;
+    r->trials = r->trials + 1;
+    if (!(score < r->best_score)) return 0;
+    r->best_score = score; r->best = slot; r->best_in = n_in;
+    int need = vo_pose_trials_needed(n_in, n, conf);
+    if (need < r->bound) r->bound = need;
+    return 1;
+}
+
+/* The camera pose in the world, rigidtform3d.A row-major, of the extrinsics Xc = R X + t:
+ * [R^T, -R^T t; 0 0 0 1]. */
+VO_HD void vo_pose_to_T(const double* R, const double* t, double* T)
+{
+    VO_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        T[4 * i] = R[i]; T[4 * i + 1] = R[3 + i]; T[4 * i + 2] = R[6 + i];
+        T[4 * i + 3] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
+    }
+    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+}
+
+/* ------------------------------------------------------------------------ */
 /* triangulate's second and third outputs (reprojectionErrors, validIndex)   */
 /* of one point.  X is the point as vo_triangulate returns it -- the doubles */
 /* already rounded through single, not the unrounded null vector -- so a     */
@@ -505,7 +789,7 @@ VO_HD int vo_tri_quality(const double* X, float u1, float v1, float u2, float v2
 /*                                                                           */
 /* State: extrinsics R (3x3 row-major), t with Xc = R X + t -- MsacHyp's     */
 /* convention.  A pose given as rigidtform3d.A converts with                 */
-/* vo_refine_from_T and back with vo_refine_to_T (msac_final's expressions). */
+/* vo_refine_from_T and back with vo_refine_to_T (vo_pose_to_T by name).    */
 /* Used set U = { k : use[k] != 0 and zc_k > 0 at the initial pose }, fixed  */
 /* for the call: every pass re-evaluates zc_k at the initial pose from its   */
 /* third row (z0 = R0[6..8], t0[2]) instead of storing a mask.               */
@@ -520,12 +804,6 @@ VO_HD int vo_tri_quality(const double* X, float u1, float v1, float u2, float v2
 #define VO_REFINE_NSUM 28           /* 21 of H's upper triangle row-major, 6 of g, the cost */
 #define VO_REFINE_LANES 64          /* partial sums: partial l adds the points k = l (mod 64), ascending */
 
-#if defined(__HIPCC__)
-#define VO_UNROLL _Pragma("unroll")
-#else
-#define VO_UNROLL
-#endif
-
 VO_HD void vo_refine_from_T(const double* T, double* R, double* t)
 {
     VO_UNROLL
@@ -536,19 +814,11 @@ VO_HD void vo_refine_from_T(const double* T, double* R, double* t)
     for (int i = 0; i < 3; ++i) t[i] = -(R[3 * i] * T[3] + R[3 * i + 1] * T[7] + R[3 * i + 2] * T[11]);
 }
 
-VO_HD void vo_refine_to_T(const double* R, const double* t, double* T)
-{
-    VO_UNROLL
-    for (int i = 0; i < 3; ++i) {
-        T[4 * i] = R[i]; T[4 * i + 1] = R[3 + i]; T[4 * i + 2] = R[6 + i];
-        T[4 * i + 3] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
-    }
-    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
-}
+VO_HD void vo_refine_to_T(const double* R, const double* t, double* T) { vo_pose_to_T(R, t, T); }
 
 /* One point of one pass at the pose (R, t).  Returns 1 when the point is in U (0: it adds nothing).
  * A point of U with !(zc > 0) at this pose adds nothing and sets *behind.  Otherwise, with K read as
- * reproj_err2_dev reads it (fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5]):
+ * vo_pose_reproj_err2 reads it (fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5]):
  *   residual  ru = (fx xn + s yn + cx) - u,  rv = (fy yn + cy) - v,   xn = xc / zc, yn = yc / zc
  *   rows of the Jacobian for the left perturbation Xc' = Xc + w x Xc + v:  (Xc x a, a), (Xc x b, b)
  *   with a = (fx / zc, s / zc, -(fx xn + s yn) / zc),  b = (0, fy / zc, -(fy yn) / zc)

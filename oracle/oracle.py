@@ -130,6 +130,7 @@ def lib(cv: bool = False):
         L.oracle_spec_check_expf_nonpos.restype = C.c_long
         L.oracle_philox.restype = None
         L.oracle_gauss_radius.argtypes = [C.c_double]
+        L.oracle_pose_trials_needed.argtypes = [C.c_int, C.c_int, C.c_double]
         L.oracle_run_sequence.restype = C.c_long
         L.oracle_sift_match_pair.argtypes = [P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, P(SiftParams), P(MatchParams),
                                              P(C.c_int), P(C.c_int)]
@@ -364,6 +365,11 @@ def spec_eval(fn: str, x) -> np.ndarray:
     out = np.zeros(n)
     lib().oracle_spec_eval(SPEC_FN[fn], _p(x, C.c_double), _p(out, C.c_double), n)
     return out
+
+
+def pose_trials_needed(n_in: int, n: int, conf: float) -> int:
+    """vo_spec.h's vo_pose_trials_needed (conf as a fraction)."""
+    return int(lib().oracle_pose_trials_needed(int(n_in), int(n), float(conf)))
 
 
 def philox(ctr, key) -> np.ndarray:

@@ -31,6 +31,8 @@ void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
     for (int i = 0; i < 4; ++i) out[i] = r.v[i];
 }
 
+int oracle_pose_trials_needed(int n_in, int n, double conf) { return vo_pose_trials_needed(n_in, n, conf); }
+
 int oracle_gauss_radius(double sigma)
 {
     float k[VO_SIFT_MAX_RADIUS + 1];

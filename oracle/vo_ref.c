@@ -219,64 +219,12 @@ int oracle_track(const uint8_t* old_l, const uint8_t* old_r, int n_old,
 }
 
 /* ======================================================================= */
-/* triangulate: DLT, null vector by one-sided Jacobi SVD (Hestenes)         */
+/* triangulate: vo_spec.h's vo_dlt_point per row                            */
 /* ======================================================================= */
-static void dlt_point(float u1f, float v1f, float u2f, float v2f, const double* P1, const double* P2, double X[3])
-{
-    double u1 = u1f, v1 = v1f, u2 = u2f, v2 = v2f;
-    double A[4][4];   /* A[row][col] */
-    for (int c = 0; c < 4; ++c) {
-        A[0][c] = u1 * P1[8 + c] - P1[c];
-        A[1][c] = v1 * P1[8 + c] - P1[4 + c];
-        A[2][c] = u2 * P2[8 + c] - P2[c];
-        A[3][c] = v2 * P2[8 + c] - P2[4 + c];
-    }
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        int rotated = 0;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                double al = 0, be = 0, ga = 0;
-                for (int i = 0; i < 4; ++i) {
-                    al = al + A[i][p] * A[i][p];
-                    be = be + A[i][q] * A[i][q];
-                    ga = ga + A[i][p] * A[i][q];
-                }
-                if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
-                rotated = 1;
-                double zeta = (be - al) / (2.0 * ga);
-                double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                double c = 1.0 / sqrt(1.0 + t * t);
-                double s = c * t;
-                for (int i = 0; i < 4; ++i) {
-                    double ap = A[i][p], aq = A[i][q];
-                    A[i][p] = c * ap - s * aq;
-                    A[i][q] = s * ap + c * aq;
-                    double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = c * vp - s * vq;
-                    V[i][q] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    int jmin = 0;
-    double nmin = 0;
-    for (int j = 0; j < 4; ++j) {
-        double nj = 0;
-        for (int i = 0; i < 4; ++i) nj = nj + A[i][j] * A[i][j];
-        if (j == 0 || nj < nmin) { nmin = nj; jmin = j; }
-    }
-    double w = V[3][jmin];
-    /* MATLAB returns single for single inputs: round through float */
-    X[0] = (double)(float)(V[0][jmin] / w);
-    X[1] = (double)(float)(V[1][jmin] / w);
-    X[2] = (double)(float)(V[2][jmin] / w);
-}
-
 void oracle_triangulate(const float* x1, const float* x2, int n, const double P1[12],
                         const double P2[12], double* X)
 {
-    for (int i = 0; i < n; ++i) dlt_point(x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], P1, P2, X + 3 * i);
+    for (int i = 0; i < n; ++i) vo_dlt_point(x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1], P1, P2, X + 3 * i);
 }
 
 /* ======================================================================= */
@@ -342,152 +290,28 @@ static int real_roots(const double* a_in, int deg, double* roots)
     return nr;
 }
 
-static void pmul(const double* a, int da, const double* b, int db, double* out)
-{
-    for (int i = 0; i <= da + db; ++i) out[i] = 0.0;
-    for (int i = 0; i <= da; ++i)
-        for (int j = 0; j <= db; ++j) out[i + j] = out[i + j] + a[i] * b[j];
-}
-
-static void bearing(const double K[9], double u, double v, double f[3])
-{
-    double yn = (v - K[5]) / K[4];
-    double xn = (u - K[2] - K[1] * yn) / K[0];
-    double n = sqrt(xn * xn + yn * yn + 1.0);
-    f[0] = xn / n; f[1] = yn / n; f[2] = 1.0 / n;
-}
-
-static void cross3(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-static int normalize3(double* a)
-{
-    double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (!(n > 0)) return 0;
-    a[0] = a[0] / n; a[1] = a[1] / n; a[2] = a[2] / n;
-    return 1;
-}
-
-/* rotation R (row-major) and t with Pc = R Pw + t from 3 congruent points */
-static int align3(const double Pw[3][3], const double Pc[3][3], double R[9], double t[3])
-{
-    double ew[3][3], ec[3][3];   /* ew[k] = k-th basis vector */
-    double d1[3], d2[3];
-    for (int i = 0; i < 3; ++i) { ew[0][i] = Pw[1][i] - Pw[0][i]; d1[i] = Pw[2][i] - Pw[0][i]; }
-    if (!normalize3(ew[0])) return 0;
-    cross3(ew[0], d1, ew[2]);
-    if (!normalize3(ew[2])) return 0;
-    cross3(ew[2], ew[0], ew[1]);
-    for (int i = 0; i < 3; ++i) { ec[0][i] = Pc[1][i] - Pc[0][i]; d2[i] = Pc[2][i] - Pc[0][i]; }
-    if (!normalize3(ec[0])) return 0;
-    cross3(ec[0], d2, ec[2]);
-    if (!normalize3(ec[2])) return 0;
-    cross3(ec[2], ec[0], ec[1]);
-    /* R = Ec * Ew^T : R[i][j] = sum_k ec[k][i] * ew[k][j] */
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = ec[0][i] * ew[0][j] + ec[1][i] * ew[1][j] + ec[2][i] * ew[2][j];
-    double mw[3], mc[3];
-    for (int i = 0; i < 3; ++i) {
-        mw[i] = (Pw[0][i] + Pw[1][i] + Pw[2][i]) / 3.0;
-        mc[i] = (Pc[0][i] + Pc[1][i] + Pc[2][i]) / 3.0;
-    }
-    for (int i = 0; i < 3; ++i) t[i] = mc[i] - (R[3 * i] * mw[0] + R[3 * i + 1] * mw[1] + R[3 * i + 2] * mw[2]);
-    return 1;
-}
-
 int oracle_p3p(const double img[3][2], const double world[3][3], const double K[9],
                double Rs[4][9], double ts[4][3])
 {
-    double j[3][3];
-    for (int i = 0; i < 3; ++i) bearing(K, img[i][0], img[i][1], j[i]);
-    double dv[3];
-    for (int i = 0; i < 3; ++i) dv[i] = world[1][i] - world[2][i];
-    double a2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    for (int i = 0; i < 3; ++i) dv[i] = world[0][i] - world[2][i];
-    double b2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    for (int i = 0; i < 3; ++i) dv[i] = world[0][i] - world[1][i];
-    double c2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    if (!(a2 > 0 && b2 > 0 && c2 > 0)) return 0;
-    double ca = j[1][0] * j[2][0] + j[1][1] * j[2][1] + j[1][2] * j[2][2];  /* cos alpha: rays 2,3 */
-    double cb = j[0][0] * j[2][0] + j[0][1] * j[2][1] + j[0][2] * j[2][2];  /* cos beta:  rays 1,3 */
-    double cg = j[0][0] * j[1][0] + j[0][1] * j[1][1] + j[0][2] * j[1][2];  /* cos gamma: rays 1,2 */
-    double Kq = (a2 - c2) / b2, cb2 = c2 / b2;
-    /* u = N(v)/D(v); quartic = D^2 + N^2 - 2 cg N D - (c2/b2) Q D^2 */
-    double N[3] = {1.0 + Kq, -2.0 * Kq * cb, Kq - 1.0};
-    double D[2] = {2.0 * cg, -2.0 * ca};
-    double Q[3] = {1.0, -2.0 * cb, 1.0};
-    double DD[3], NN[5], ND[4], QDD[5];
-    pmul(D, 1, D, 1, DD);
-    pmul(N, 2, N, 2, NN);
-    pmul(N, 2, D, 1, ND);
-    pmul(Q, 2, DD, 2, QDD);
-    double P[5];
-    for (int i = 0; i < 5; ++i) {
-        double v = NN[i] - cb2 * QDD[i];
-        if (i < 3) v = v + DD[i];
-        if (i < 4) v = v - 2.0 * cg * ND[i];
-        P[i] = v;
-    }
+    vo_p3p p;
+    if (!vo_p3p_setup(img, world, K, &p)) return 0;
     double roots[4];
-    int nr = real_roots(P, 4, roots);
+    int nr = real_roots(p.P, 4, roots);
     int ns = 0;
-    for (int k = 0; k < nr; ++k) {
-        double v = roots[k];
-        if (!(v > 0)) continue;
-        double Dv = D[0] + D[1] * v;
-        if (Dv == 0.0) continue;
-        double u = (N[0] + N[1] * v + N[2] * v * v) / Dv;
-        if (!(u > 0)) continue;
-        double Qv = Q[0] + Q[1] * v + Q[2] * v * v;
-        if (!(Qv > 0)) continue;
-        double s1 = sqrt(b2 / Qv), s2 = u * s1, s3 = v * s1;
-        double Pc[3][3];
-        for (int i = 0; i < 3; ++i) { Pc[0][i] = s1 * j[0][i]; Pc[1][i] = s2 * j[1][i]; Pc[2][i] = s3 * j[2][i]; }
-        if (align3(world, Pc, Rs[ns], ts[ns])) ns++;
-        if (ns == 4) break;
-    }
+    for (int k = 0; k < nr && ns < 4; ++k)
+        if (vo_p3p_pose(&p, world, roots[k], Rs[ns], ts[ns])) ns++;
     return ns;
 }
 
 /* ======================================================================= */
 /* estworldpose: P3P + MSAC                                 */
 /* ======================================================================= */
-static double reproj_err2(const double R[9], const double t[3], const double K[9], const double* X, const double* uv)
-{
-    double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
-    double yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
-    double zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
-    if (!(zc > 0)) return INFINITY;
-    double xn = xc / zc, yn = yc / zc;
-    double u = K[0] * xn + K[1] * yn + K[2];
-    double v = K[4] * yn + K[5];
-    double du = u - uv[0], dv = v - uv[1];
-    return du * du + dv * dv;
-}
-
-/* sample 4 distinct indices for slot s; returns 0 if none found */
-static int msac_sample(uint32_t seed, uint32_t frame_key, uint32_t s, uint32_t n, uint32_t idx[4])
-{
-    for (uint32_t att = 0; att < 16; ++att) {
-        vo_u32x4 c = {{s, att, frame_key, 0x5EEDu}};
-        vo_u32x4 r = vo_philox4x32_10(c, seed, 0x9E3779B9u);
-        for (int q = 0; q < 4; ++q) idx[q] = vo_rand_index(r.v[q], n);
-        if (idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] && idx[2] != idx[3])
-            return 1;
-    }
-    return 0;
-}
-
 /* one hypothesis slot: returns 1 if valid (R,t filled) */
 static int msac_hypothesis(const double* img, const double* world, int n, const double K[9], uint32_t seed,
                            uint32_t frame_key, uint32_t s, double R[9], double t[3])
 {
     uint32_t idx[4];
-    if (!msac_sample(seed, frame_key, s, (uint32_t)n, idx)) return 0;
+    if (!vo_pose_sample(seed, frame_key, s, (uint32_t)n, idx)) return 0;
     double im3[3][2], w3[3][3];
     for (int q = 0; q < 3; ++q) {
         im3[q][0] = img[2 * idx[q]]; im3[q][1] = img[2 * idx[q] + 1];
@@ -498,7 +322,7 @@ static int msac_hypothesis(const double* img, const double* world, int n, const 
     int best = -1;
     double be = INFINITY;
     for (int k = 0; k < ns; ++k) {
-        double e = reproj_err2(Rs[k], ts[k], K, world + 3 * idx[3], img + 2 * idx[3]);
+        double e = vo_pose_reproj_err2(Rs[k], ts[k], K, world + 3 * idx[3], img + 2 * idx[3]);
         if (e < be) { be = e; best = k; }
     }
     if (best < 0) return 0;
@@ -515,7 +339,7 @@ static double msac_score(const double R[9], const double t[3], const double* img
     int cnt = 0;
     for (int l = 0; l < 64; ++l) part[l] = 0.0;
     for (int k = 0; k < n; ++k) {
-        double e = reproj_err2(R, t, K, world + 3 * k, img + 2 * k);
+        double e = vo_pose_reproj_err2(R, t, K, world + 3 * k, img + 2 * k);
         if (e < thr) cnt++;
         part[k & 63] = part[k & 63] + (e < thr ? e : thr);
     }
@@ -523,20 +347,6 @@ static double msac_score(const double R[9], const double t[3], const double* img
         for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
     *n_in = cnt;
     return part[0];
-}
-
-int msac_trials_needed(int n_in, int n, double conf)
-{
-    double w = (double)n_in / (double)n;
-    double w4 = w * w * w * w;
-    if (!(w4 > 1e-300)) return 0x7fffffff;
-    double den = vo_log_d(1.0 - w4);
-    if (!(den < 0)) return 1;
-    double num = vo_log_d(1.0 - conf);
-    double N = ceil(num / den);
-    if (N > 2147483647.0) return 0x7fffffff;
-    if (N < 1.0) return 1;
-    return (int)N;
 }
 
 int oracle_estworldpose(const double* img, const double* world, int n, const double K[9],
@@ -547,38 +357,28 @@ int oracle_estworldpose(const double* img, const double* world, int n, const dou
     if (n < 4) return VO_ERR_TOO_FEW_POINTS;
     const double thr = p->max_reprojection_error * p->max_reprojection_error;
     const double conf = p->confidence / 100.0;
-    int num_trials = p->max_num_trials;
-    int trials = 0;
-    double best_score = INFINITY, bR[9], bt[3];
-    int have = 0, best_in = 0;
-    for (int s = 0; s < p->max_num_trials && trials < num_trials; ++s) {
-        double R[9], t[3];
-        if (!msac_hypothesis(img, world, n, K, p->seed, frame_key, (uint32_t)s, R, t)) continue;
-        trials++;
-        int nin;
-        double sc = msac_score(R, t, img, world, n, K, thr, &nin);
-        if (sc < best_score) {
-            best_score = sc; have = 1; best_in = nin;
+    vo_pose_replay r;
+    vo_pose_replay_begin(&r, p->max_num_trials);
+    double bR[9], bt[3];
+    for (int s = 0; s < p->max_num_trials && !vo_pose_replay_done(&r); ++s) {
+        double R[9], t[3], sc = 0;
+        int nin = 0;
+        const int valid = msac_hypothesis(img, world, n, K, p->seed, frame_key, (uint32_t)s, R, t);
+        if (valid) sc = msac_score(R, t, img, world, n, K, thr, &nin);
+        if (vo_pose_replay_slot(&r, s, valid, sc, nin, n, conf)) {
             memcpy(bR, R, sizeof(bR)); memcpy(bt, t, sizeof(bt));
-            int need = msac_trials_needed(nin, n, conf);
-            if (need < num_trials) num_trials = need;
         }
     }
-    if (!have || best_in < 4) return VO_ERR_NO_CONSENSUS;
+    if (r.best < 0 || r.best_in < 4) return VO_ERR_NO_CONSENSUS;
     int cnt = 0;
     for (int k = 0; k < n; ++k) {
-        double e = reproj_err2(bR, bt, K, world + 3 * k, img + 2 * k);
+        double e = vo_pose_reproj_err2(bR, bt, K, world + 3 * k, img + 2 * k);
         int in = e < thr;
         if (inliers) inliers[k] = (uint8_t)in;
         cnt += in;
     }
     if (n_inliers) *n_inliers = cnt;
-    /* camera pose in world: [R^T, -R^T t; 0 0 0 1] */
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) T[4 * i + j] = bR[3 * j + i];
-        T[4 * i + 3] = -(bR[i] * bt[0] + bR[3 + i] * bt[1] + bR[6 + i] * bt[2]);
-    }
-    T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+    vo_pose_to_T(bR, bt, T);   /* camera pose in world */
     return VO_OK;
 }
 
@@ -586,7 +386,7 @@ int oracle_estworldpose(const double* img, const double* world, int n, const dou
 /* landmarks: VO.m:145-160 + CreateLandmarksFromFeatures.m                  */
 /* ======================================================================= */
 /* CreateLandmarksFromFeatures.m:1-16 in the camera frame: X[rows][3] (the triangulated
- * point, single-rounded as dlt_point returns it) and keep[rows] (0 = zero row).  Returns
+ * point, single-rounded as vo_dlt_point returns it) and keep[rows] (0 = zero row).  Returns
  * rows; only min(rows, capacity) are written. */
 int oracle_landmark_rows(const float* l_pos, const float* r_pos, int S, const float* old_l,
                          const float* old_r, int K, const double P1[12], const double P2[12],
@@ -607,7 +407,7 @@ int oracle_landmark_rows(const float* l_pos, const float* r_pos, int S, const fl
     for (int r = 0; r < 2 && r < capacity; ++r) { keep[r] = 0; X_out[3 * r] = X_out[3 * r + 1] = X_out[3 * r + 2] = 0.0f; }
     for (int i = 0; i < M; i += 2) {   /* 1-based odd i <-> 0-based even */
         double X[3];
-        dlt_point(l_pos[2 * idx[i]], l_pos[2 * idx[i] + 1], r_pos[2 * idx[i]], r_pos[2 * idx[i] + 1], P1, P2, X);
+        vo_dlt_point(l_pos[2 * idx[i]], l_pos[2 * idx[i] + 1], r_pos[2 * idx[i]], r_pos[2 * idx[i] + 1], P1, P2, X);
         if (X[2] < 0) continue;
         if (X[2] > 80) continue;
         for (int r = rows; r < i + 1 && r < capacity; ++r) { keep[r] = 0; X_out[3 * r] = X_out[3 * r + 1] = X_out[3 * r + 2] = 0.0f; }

@@ -5,7 +5,7 @@
 //       match.hip) composes its (i, j) pairs into the next step's lists, so no
 //       descriptor is ever copied.
 //   triangulate (VO.m:113-116)            k_gather_tri: one lane per tracked
-//       point, linear DLT + one-sided Jacobi SVD in f64 (oracle dlt_point).
+//       point, linear DLT + one-sided Jacobi SVD in f64 (vo_dlt_point).
 //   estworldpose (VO.m:123-127)           k_msac: one block per frame walks the
 //       hypothesis slots in chunks of 64 -- a lane per slot (Philox sample,
 //       Grunert P3P, 4th-point disambiguation), a wave per slot score
@@ -24,7 +24,9 @@
 //       k_lm_tri (odd rows, z gates).  (One fused block per frame measured
 //       3.5x slower: 0.27 vs 0.075 ms per batch for positions + filter.)  The world transform needs the chained pose and runs
 //       on the host after the 4x4 chain.
-// Float/double expressions mirror oracle/vo_ref.c operation for operation.
+// The arithmetic of triangulate and estworldpose (DLT, P3P, the MSAC sample, bound, replay and pose)
+// is vo_spec.h's, compiled here and by oracle/vo_ref.c; only the quartic's root finder exists in two
+// forms (real_roots_trim below, real_roots there), operation for operation.
 #include "vo_geom.h"
 #include <cstring>
 #include <cstdlib>
@@ -92,69 +94,8 @@ void geom_fill_track_jobs(const GeomBuffers& g, MatchJob* jobs, int M, int first
 }
 
 // ---------------------------------------------------------------------------
-// DLT triangulation (oracle dlt_point)
+// DLT triangulation (vo_spec.h vo_dlt_point)
 // ---------------------------------------------------------------------------
-__device__ void dlt_point_dev(float u1f, float v1f, float u2f, float v2f, const double* P1, const double* P2, double X[3])
-{
-    double u1 = u1f, v1 = v1f, u2 = u2f, v2 = v2f;
-    double A[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        A[0][c] = u1 * P1[8 + c] - P1[c];
-        A[1][c] = v1 * P1[8 + c] - P1[4 + c];
-        A[2][c] = u2 * P2[8 + c] - P2[c];
-        A[3][c] = v2 * P2[8 + c] - P2[4 + c];
-    }
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        int rotated = 0;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                double al = 0, be = 0, ga = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    al = al + A[i][p] * A[i][p];
-                    be = be + A[i][q] * A[i][q];
-                    ga = ga + A[i][p] * A[i][q];
-                }
-                if (ga == 0.0 || fabs(ga) <= 1e-15 * sqrt(al * be)) continue;
-                rotated = 1;
-                double zeta = (be - al) / (2.0 * ga);
-                double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                double c = 1.0 / sqrt(1.0 + t * t);
-                double s = c * t;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    double ap = A[i][p], aq = A[i][q];
-                    A[i][p] = c * ap - s * aq;
-                    A[i][q] = s * ap + c * aq;
-                    double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = c * vp - s * vq;
-                    V[i][q] = s * vp + c * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    int jmin = 0;
-    double nmin = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double nj = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) nj = nj + A[i][j] * A[i][j];
-        if (j == 0 || nj < nmin) { nmin = nj; jmin = j; }
-    }
-    double v0 = 0, v1_ = 0, v2_ = 0, w = 1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j == jmin) { v0 = V[0][j]; v1_ = V[1][j]; v2_ = V[2][j]; w = V[3][j]; }
-    X[0] = (double)(float)(v0 / w);
-    X[1] = (double)(float)(v1_ / w);
-    X[2] = (double)(float)(v2_ / w);
-}
-
 struct CalibDev { double P1[12], P2[12], K[9]; };
 
 // gather tracked positions and triangulate the old stereo pair. grid (blocks, B)
@@ -176,7 +117,7 @@ __global__ void k_gather_tri(const vo_keypoint* __restrict__ kp, int kp_cap, con
         double* ip = imgpt + ((size_t)f * K + k) * 2;
         ip[0] = cu.x; ip[1] = cu.y;
         double X[3];
-        dlt_point_dev(ol.x, ol.y, orr.x, orr.y, cal.P1, cal.P2, X);
+        vo_dlt_point(ol.x, ol.y, orr.x, orr.y, cal.P1, cal.P2, X);
         double* w = world + ((size_t)f * K + k) * 3;
         w[0] = X[0]; w[1] = X[1]; w[2] = X[2];
     }
@@ -187,7 +128,7 @@ __global__ void k_tri_list(const float* __restrict__ pos, int n, CalibDev cal, d
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
         double Y[3];
-        dlt_point_dev(pos[4 * k], pos[4 * k + 1], pos[4 * k + 2], pos[4 * k + 3], cal.P1, cal.P2, Y);
+        vo_dlt_point(pos[4 * k], pos[4 * k + 1], pos[4 * k + 2], pos[4 * k + 3], cal.P1, cal.P2, Y);
         X[3 * k] = Y[0]; X[3 * k + 1] = Y[1]; X[3 * k + 2] = Y[2];
     }
 }
@@ -216,14 +157,14 @@ __global__ void k_tri_quality(const float* __restrict__ pos, const double* __res
 }
 
 // ---------------------------------------------------------------------------
-// P3P (oracle_p3p) — Grunert's quartic by polynomial algebra, deterministic
-// bracketing/bisection root finder (template recursion = the oracle's).
+// P3P (vo_spec.h vo_p3p_setup / vo_p3p_pose) — the deterministic bracketing/bisection
+// root finder that runs between the two (template recursion = the oracle's real_roots).
 // ---------------------------------------------------------------------------
 // Register-resident form: every array index is a compile-time constant (fixed-degree solvers
 // selected by a switch on the trimmed degree, roots appended through select chains), so the
 // coefficients, critical points and roots stay in VGPRs -- the dynamically indexed form
 // lived in scratch and its bisection loop waited on scratch loads every iteration.  Same
-// operations in the same order as the oracle (real_roots, oracle/vo_ref.c:294): the trim
+// operations in the same order as the oracle (real_roots in oracle/vo_ref.c): the trim
 // keeps the largest i >= 1 with !(|a_i| <= 1e-14 amax), Horner as r = r*x + a_i.
 template <int D>
 __device__ __forceinline__ double peval_fixed(const double* a, double x)
@@ -324,141 +265,6 @@ __device__ int real_roots_trim(const double* a, double* roots)
     return 0;
 }
 
-__device__ __forceinline__ void pmul_dev(const double* a, int da, const double* b, int db, double* out)
-{
-    for (int i = 0; i <= da + db; ++i) out[i] = 0.0;
-    for (int i = 0; i <= da; ++i)
-        for (int j = 0; j <= db; ++j) out[i + j] = out[i + j] + a[i] * b[j];
-}
-
-__device__ __forceinline__ void bearing_dev(const double* K, double u, double v, double f[3])
-{
-    double yn = (v - K[5]) / K[4];
-    double xn = (u - K[2] - K[1] * yn) / K[0];
-    double n = sqrt(xn * xn + yn * yn + 1.0);
-    f[0] = xn / n; f[1] = yn / n; f[2] = 1.0 / n;
-}
-
-__device__ __forceinline__ void cross3_dev(const double* a, const double* b, double* c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ int normalize3_dev(double* a)
-{
-    double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    if (!(n > 0)) return 0;
-    a[0] = a[0] / n; a[1] = a[1] / n; a[2] = a[2] / n;
-    return 1;
-}
-
-__device__ int align3_dev(const double Pw[3][3], const double Pc[3][3], double R[9], double t[3])
-{
-    double ew[3][3], ec[3][3];
-    double d1[3], d2[3];
-    for (int i = 0; i < 3; ++i) { ew[0][i] = Pw[1][i] - Pw[0][i]; d1[i] = Pw[2][i] - Pw[0][i]; }
-    if (!normalize3_dev(ew[0])) return 0;
-    cross3_dev(ew[0], d1, ew[2]);
-    if (!normalize3_dev(ew[2])) return 0;
-    cross3_dev(ew[2], ew[0], ew[1]);
-    for (int i = 0; i < 3; ++i) { ec[0][i] = Pc[1][i] - Pc[0][i]; d2[i] = Pc[2][i] - Pc[0][i]; }
-    if (!normalize3_dev(ec[0])) return 0;
-    cross3_dev(ec[0], d2, ec[2]);
-    if (!normalize3_dev(ec[2])) return 0;
-    cross3_dev(ec[2], ec[0], ec[1]);
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = ec[0][i] * ew[0][j] + ec[1][i] * ew[1][j] + ec[2][i] * ew[2][j];
-    double mw[3], mc[3];
-    for (int i = 0; i < 3; ++i) {
-        mw[i] = (Pw[0][i] + Pw[1][i] + Pw[2][i]) / 3.0;
-        mc[i] = (Pc[0][i] + Pc[1][i] + Pc[2][i]) / 3.0;
-    }
-    for (int i = 0; i < 3; ++i) t[i] = mc[i] - (R[3 * i] * mw[0] + R[3 * i + 1] * mw[1] + R[3 * i + 2] * mw[2]);
-    return 1;
-}
-
-__device__ __forceinline__ double reproj_err2_dev(const double R[9], const double t[3], const double* K, const double* X,
-                                                  const double* uv)
-{
-    double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
-    double yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
-    double zc = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
-    if (!(zc > 0)) return INFINITY;
-    double xn = xc / zc, yn = yc / zc;
-    double u = K[0] * xn + K[1] * yn + K[2];
-    double v = K[4] * yn + K[5];
-    double du = u - uv[0], dv = v - uv[1];
-    return du * du + dv * dv;
-}
-
-// one P3P + 4th-point selection; returns 1 if valid
-__device__ int p3p_hyp_dev(const double im3[3][2], const double w3[3][3], const double* w4, const double* im4,
-                           const double* K, double Rb[9], double tb[3])
-{
-    double j[3][3];
-    for (int i = 0; i < 3; ++i) bearing_dev(K, im3[i][0], im3[i][1], j[i]);
-    double dv[3];
-    for (int i = 0; i < 3; ++i) dv[i] = w3[1][i] - w3[2][i];
-    double a2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    for (int i = 0; i < 3; ++i) dv[i] = w3[0][i] - w3[2][i];
-    double b2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    for (int i = 0; i < 3; ++i) dv[i] = w3[0][i] - w3[1][i];
-    double c2 = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-    if (!(a2 > 0 && b2 > 0 && c2 > 0)) return 0;
-    double ca = j[1][0] * j[2][0] + j[1][1] * j[2][1] + j[1][2] * j[2][2];
-    double cb = j[0][0] * j[2][0] + j[0][1] * j[2][1] + j[0][2] * j[2][2];
-    double cg = j[0][0] * j[1][0] + j[0][1] * j[1][1] + j[0][2] * j[1][2];
-    double Kq = (a2 - c2) / b2, cb2 = c2 / b2;
-    double N[3] = {1.0 + Kq, -2.0 * Kq * cb, Kq - 1.0};
-    double D[2] = {2.0 * cg, -2.0 * ca};
-    double Q[3] = {1.0, -2.0 * cb, 1.0};
-    double DD[3], NN[5], ND[4], QDD[5];
-    pmul_dev(D, 1, D, 1, DD);
-    pmul_dev(N, 2, N, 2, NN);
-    pmul_dev(N, 2, D, 1, ND);
-    pmul_dev(Q, 2, DD, 2, QDD);
-    double P[5];
-    for (int i = 0; i < 5; ++i) {
-        double v = NN[i] - cb2 * QDD[i];
-        if (i < 3) v = v + DD[i];
-        if (i < 4) v = v - 2.0 * cg * ND[i];
-        P[i] = v;
-    }
-    double roots[4];
-    const int nr = real_roots_trim<4>(P, roots);
-    int ns = 0, best = -1;
-    double be = INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k >= nr) break;
-        double v = roots[k];
-        if (!(v > 0)) continue;
-        double Dv = D[0] + D[1] * v;
-        if (Dv == 0.0) continue;
-        double u = (N[0] + N[1] * v + N[2] * v * v) / Dv;
-        if (!(u > 0)) continue;
-        double Qv = Q[0] + Q[1] * v + Q[2] * v * v;
-        if (!(Qv > 0)) continue;
-        double s1 = sqrt(b2 / Qv), s2 = u * s1, s3 = v * s1;
-        double Pc[3][3];
-        for (int i = 0; i < 3; ++i) { Pc[0][i] = s1 * j[0][i]; Pc[1][i] = s2 * j[1][i]; Pc[2][i] = s3 * j[2][i]; }
-        double R[9], t[3];
-        if (align3_dev(w3, Pc, R, t)) {
-            double e = reproj_err2_dev(R, t, K, w4, im4);
-            if (e < be) {
-                be = e; best = ns;
-                for (int q = 0; q < 9; ++q) Rb[q] = R[q];
-                for (int q = 0; q < 3; ++q) tb[q] = t[q];
-            }
-            ns++;
-        }
-        if (ns == 4) break;
-    }
-    return best >= 0;
-}
-
 struct MsacArgs {
     const double* img; const double* world; const int* n; int n_stride;   // n[f * n_stride]
     MsacHyp* hyp; FrameGeom* fg; uint8_t* inliers;
@@ -484,22 +290,33 @@ __device__ void msac_hyp_slot(const MsacArgs& a, int f, int s, int n)
     const double* img = a.img + (size_t)f * a.kp_cap * 2;
     const double* world = a.world + (size_t)f * a.kp_cap * 3;
     uint32_t idx[4];
-    bool ok = false;
-    for (uint32_t att = 0; att < 16 && !ok; ++att) {
-        vo_u32x4 c = {{(uint32_t)s, att, a.key0 + (uint32_t)f, 0x5EEDu}};
-        vo_u32x4 r = vo_philox4x32_10(c, a.seed, 0x9E3779B9u);
-        for (int q = 0; q < 4; ++q) idx[q] = vo_rand_index(r.v[q], (uint32_t)n);
-        ok = idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] &&
-             idx[2] != idx[3];
-    }
-    if (!ok) return;
+    if (!vo_pose_sample(a.seed, a.key0 + (uint32_t)f, (uint32_t)s, (uint32_t)n, idx)) return;
     double im3[3][2], w3[3][3];
     for (int q = 0; q < 3; ++q) {
         im3[q][0] = img[2 * idx[q]]; im3[q][1] = img[2 * idx[q] + 1];
         for (int i = 0; i < 3; ++i) w3[q][i] = world[3 * idx[q] + i];
     }
-    double R[9], t[3];
-    if (!p3p_hyp_dev(im3, w3, world + 3 * idx[3], img + 2 * idx[3], a.K, R, t)) return;
+    vo_p3p p;
+    if (!vo_p3p_setup(im3, w3, a.K, &p)) return;
+    double roots[4];
+    const int nr = real_roots_trim<4>(p.P, roots);
+    // of at most four poses, the one with the smallest error at the 4th point (the first of equals)
+    double R[9], t[3], be = INFINITY;
+    int ns = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k >= nr) break;
+        double Rk[9], tk[3];
+        if (!vo_p3p_pose(&p, w3, roots[k], Rk, tk)) continue;
+        const double e = vo_pose_reproj_err2(Rk, tk, a.K, world + 3 * idx[3], img + 2 * idx[3]);
+        if (e < be) {
+            be = e;
+            for (int q = 0; q < 9; ++q) R[q] = Rk[q];
+            for (int q = 0; q < 3; ++q) t[q] = tk[q];
+        }
+        if (++ns == 4) break;
+    }
+    if (!(be < INFINITY)) return;
     for (int q = 0; q < 9; ++q) h->R[q] = R[q];
     for (int q = 0; q < 3; ++q) h->t[q] = t[q];
     h->valid = 1;
@@ -517,7 +334,7 @@ __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s,
     double part = 0.0;
     int cnt = 0;
     for (int k = lane; k < n; k += 64) {
-        double e = reproj_err2_dev(R, tt, a.K, world + 3 * k, img + 2 * k);
+        double e = vo_pose_reproj_err2(R, tt, a.K, world + 3 * k, img + 2 * k);
         if (e < a.thr) cnt++;
         part = part + (e < a.thr ? e : a.thr);
     }
@@ -527,20 +344,6 @@ __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s,
         cnt += __shfl_xor(cnt, off);
     }
     if (lane == 0) { h->score = part; h->n_in = cnt; }
-}
-
-__device__ int msac_trials_needed_dev(int n_in, int n, double conf)
-{
-    double w = (double)n_in / (double)n;
-    double w4 = w * w * w * w;
-    if (!(w4 > 1e-300)) return 0x7fffffff;
-    double den = vo_log_d(1.0 - w4);
-    if (!(den < 0)) return 1;
-    double num = vo_log_d(1.0 - conf);
-    double N = ceil(num / den);
-    if (N > 2147483647.0) return 0x7fffffff;
-    if (N < 1.0) return 1;
-    return (int)N;
 }
 
 // inlier mask + camera pose of the chosen slot (one wave)
@@ -562,7 +365,7 @@ __device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status
     const double* world = a.world + (size_t)f * a.kp_cap * 3;
     int cnt = 0;
     for (int k = lane; k < n; k += 64) {
-        const int in = reproj_err2_dev(R, t, a.K, world + 3 * k, img + 2 * k) < a.thr;
+        const int in = vo_pose_reproj_err2(R, t, a.K, world + 3 * k, img + 2 * k) < a.thr;
         a.inliers[(size_t)f * a.kp_cap + k] = (uint8_t)in;
         cnt += in;
     }
@@ -570,11 +373,7 @@ __device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status
     for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
     if (lane == 0) {
         g->n_inliers = cnt;
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) g->T[4 * i + j] = R[3 * j + i];
-            g->T[4 * i + 3] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
-        }
-        g->T[12] = 0; g->T[13] = 0; g->T[14] = 0; g->T[15] = 1;
+        vo_pose_to_T(R, t, g->T);
     }
 }
 
@@ -601,9 +400,8 @@ __global__ __launch_bounds__(VO_MSAC_T) void k_msac(MsacArgs a)
     const int n = msac_n(a, f);
     const int limit = a.max_trials < a.n_hyp ? a.max_trials : a.n_hyp;
     FrameGeom* g = a.fg + f;
-    // replay state (thread 0)
-    int num_trials = a.max_trials, trials = 0, best_in = 0, best = -1;
-    double best_score = INFINITY;
+    vo_pose_replay r;                                       // thread 0's
+    vo_pose_replay_begin(&r, a.max_trials);
     if (tid == 0) s_done = n < 4;
     __syncthreads();
     for (int c0 = 0, c1 = min(VO_MSAC_FIRST, limit); !s_done && c0 < limit;
@@ -614,29 +412,22 @@ __global__ __launch_bounds__(VO_MSAC_T) void k_msac(MsacArgs a)
             if (a.hyp[(size_t)f * a.n_hyp + s].valid) msac_score_slot(a, f, s, n, lane);
         __syncthreads();                                    // ... and scored
         if (tid == 0) {
-            int s = c0;
-            for (; s < c1 && trials < num_trials; ++s) {
+            for (int s = c0; s < c1 && !vo_pose_replay_done(&r); ++s) {
                 const MsacHyp* h = a.hyp + (size_t)f * a.n_hyp + s;
-                if (!h->valid) continue;
-                trials++;
-                if (h->score < best_score) {
-                    best_score = h->score; best = s; best_in = h->n_in;
-                    int need = msac_trials_needed_dev(h->n_in, n, a.conf);
-                    if (need < num_trials) num_trials = need;
-                }
+                vo_pose_replay_slot(&r, s, h->valid, h->score, h->n_in, n, a.conf);
             }
-            s_done = trials >= num_trials || s >= limit;
+            s_done = vo_pose_replay_done(&r);               // (the last chunk ends the loop by c0 < limit)
         }
         __syncthreads();
     }
     if (tid == 0) {
         int status = VO_OK;
         if (n < 4) status = VO_ERR_TOO_FEW_POINTS;
-        else if (best < 0 || best_in < 4) status = VO_ERR_NO_CONSENSUS;
-        s_best = best;
+        else if (r.best < 0 || r.best_in < 4) status = VO_ERR_NO_CONSENSUS;
+        s_best = r.best;
         s_status = status;
         g->status = status;
-        g->best = best;
+        g->best = r.best;
         g->n_tracked = n;
     }
     __syncthreads();
@@ -1159,7 +950,7 @@ __global__ void k_lm_tri(const float* __restrict__ spos, const int* __restrict__
         if ((m & 1) == 0 && m < M) {
             const int j = lm_new[(size_t)f * K + m];
             const float* p = spos + ((size_t)f * K + j) * 4;
-            dlt_point_dev(p[0], p[1], p[2], p[3], cal.P1, cal.P2, X);
+            vo_dlt_point(p[0], p[1], p[2], p[3], cal.P1, cal.P2, X);
             keep = !(X[2] < 0) && !(X[2] > 80);
             if (keep) atomicMax(lm_rows + f, m + 1);
         }

@@ -118,3 +118,35 @@ def test_gauss_kernel_matches_formula(oracle):
         g /= g.sum()
         assert np.allclose(k, g[r:], rtol=1e-6, atol=1e-9)
         assert abs(k[0] + 2 * k[1:].sum() - 1) < 1e-6
+
+
+def test_pose_trials_needed_branches(oracle):
+    """vo_pose_trials_needed(n_in, n, conf) = ceil(log(1 - conf) / log(1 - w^4)), w = n_in / n,
+    clamped to [1, INT_MAX], at each of its branches.  The expected values are the formula in
+    Python float64 (libm log); every case sits far from an integer boundary of the quotient, so
+    vo_log_d's 4e-13 cannot move the ceiling."""
+    INT_MAX = 0x7FFFFFFF
+    # no inlier: w^4 = 0 <= 1e-300, no bound
+    assert oracle.pose_trials_needed(0, 100, 0.99) == INT_MAX
+    # every point an inlier: log(1 - 1) = -inf, the quotient is +0, its ceiling 0 -> 1
+    assert math.log(0.01) / -math.inf == 0.0
+    assert oracle.pose_trials_needed(100, 100, 0.99) == 1
+    # an ordinary ratio at conf 0.99: w = 1/2, log(0.01) / log(0.9375) = 71.36 -> 72
+    q = math.log(1.0 - 0.99) / math.log(1.0 - 0.5 ** 4)
+    assert 71.3 < q < 71.4
+    assert oracle.pose_trials_needed(50, 100, 0.99) == math.ceil(q) == 72
+    # and one more, w = 0.9: log(0.01) / log(0.3439) = 4.31 -> 5
+    q = math.log(1.0 - 0.99) / math.log(1.0 - (90 / 100) ** 4)
+    assert 4.3 < q < 4.4
+    assert oracle.pose_trials_needed(90, 100, 0.99) == math.ceil(q) == 5
+    # a ratio so small that N exceeds INT_MAX: w = 1e-3, N ~ 4.6e12
+    q = math.log(1.0 - 0.99) / math.log(1.0 - (1 / 1000) ** 4)
+    assert q > 1e12
+    assert oracle.pose_trials_needed(1, 1000, 0.99) == INT_MAX
+    # conf so small that N < 1: log(1 - 0) = 0, the quotient is -0 -> 1
+    assert math.ceil(math.log(1.0 - 0.0) / math.log(1.0 - 0.5 ** 4)) == 0
+    assert oracle.pose_trials_needed(50, 100, 0.0) == 1
+    # 1e-300 < w^4 < 2^-53: 1 - w^4 rounds to 1 and its logarithm is 0, not negative.  The spec
+    # answers 1 there (DESIGN 3.5.2 tells why the fundamental-matrix bound does not).
+    assert 1.0 - (1 / 100000) ** 4 == 1.0 and (1 / 100000) ** 4 > 1e-300
+    assert oracle.pose_trials_needed(1, 100000, 0.99) == 1
