@@ -703,6 +703,19 @@ VO_HD int vo_pose_trials_needed(int n_in, int n, double conf)
     return (int)N;
 }
 
+/* The sum of an MSAC score, of a refinement pass and of a masked Norm8 fit: 64 lane-strided partials
+ * (partial l adds the items k = l (mod 64), ascending) joined by the pairwise tree
+ *     p[i] = p[i] + p[i + off]  for i < off,  off = 32, 16, .. 1,
+ * each a single IEEE addition; the sum is p[0].  m values per partial are summed side by side;
+ * partial l is at p + l * stride, the result in p[0 .. m).  VO_REFINE_LANES and VO_FUND_LANES name
+ * the 64.  On the device this function is wave_sum (csrc/wave.h), one partial per lane. */
+VO_HD void vo_tree_sum(double* p, int stride, int m)
+{
+    for (int off = 32; off >= 1; off >>= 1)
+        for (int i = 0; i < off; ++i)
+            for (int q = 0; q < m; ++q) p[i * stride + q] = p[i * stride + q] + p[(i + off) * stride + q];
+}
+
 /* The sequential MSAC loop, replayed slot by slot in slot order over (valid, score, n_in):
  *     vo_pose_replay_begin(&r, max_num_trials);
  *     for slot = 0 .. max_num_trials - 1, while !vo_pose_replay_done(&r):  vo_pose_replay_slot(...)
@@ -802,7 +815,7 @@ VO_HD int vo_tri_quality(const double* X, float u1, float v1, float u2, float v2
 #define VO_REFINE_LAMBDA_MIN 1e-12
 #define VO_REFINE_LAMBDA_MAX 1e12
 #define VO_REFINE_NSUM 28           /* 21 of H's upper triangle row-major, 6 of g, the cost */
-#define VO_REFINE_LANES 64          /* partial sums: partial l adds the points k = l (mod 64), ascending */
+#define VO_REFINE_LANES 64          /* partial sums: partial l adds the points k = l (mod 64), ascending; joined by vo_tree_sum */
 
 VO_HD void vo_refine_from_T(const double* T, double* R, double* t)
 {
@@ -1084,7 +1097,7 @@ VO_HD float vo_radius_box_lb(float xmin, float xmax, float ymin, float ymax, flo
 #define VO_FUND_ATTEMPTS 16          /* draws of 8 indices before a slot is invalid */
 #define VO_FUND_NSUM 45              /* upper triangle of A'A, row-major */
 #define VO_FUND_NWORK (45 + 81)      /* ... and the eigenvector matrix */
-#define VO_FUND_LANES 64             /* partial sums of a masked fit: partial l adds the used points k = l (mod 64) */
+#define VO_FUND_LANES 64             /* partial sums of a masked fit: partial l adds the used points k = l (mod 64); joined by vo_tree_sum */
 #define VO_FUND_SWEEP_CAP 30         /* cyclic Jacobi sweeps, at most */
 #define VO_FUND_SKIP_EPS 1.1102230246251565e-16   /* 2^-53: a_pq is negligible beside |a_pp| + |a_qq| */
 #define VO_FUND_SQRT2 1.4142135623730951

@@ -118,6 +118,7 @@ long oracle_run_sequence(const uint8_t* lefts, const uint8_t* rights, int F, int
 
 /* spec primitive evaluation for KATs (spec_eval.c) */
 void oracle_spec_eval(int fn, const double* in, double* out, int n);
+void oracle_tree_sum(double* p, int stride, int m);   /* vo_spec.h vo_tree_sum, in place */
 void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out);
 int oracle_gauss_radius(double sigma);
 

@@ -131,6 +131,8 @@ def lib(cv: bool = False):
         L.oracle_philox.restype = None
         L.oracle_gauss_radius.argtypes = [C.c_double]
         L.oracle_pose_trials_needed.argtypes = [C.c_int, C.c_int, C.c_double]
+        L.oracle_tree_sum.argtypes = [P(C.c_double), C.c_int, C.c_int]
+        L.oracle_tree_sum.restype = None
         L.oracle_run_sequence.restype = C.c_long
         L.oracle_sift_match_pair.argtypes = [P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, P(SiftParams), P(MatchParams),
                                              P(C.c_int), P(C.c_int)]
@@ -370,6 +372,14 @@ def spec_eval(fn: str, x) -> np.ndarray:
 def pose_trials_needed(n_in: int, n: int, conf: float) -> int:
     """vo_spec.h's vo_pose_trials_needed (conf as a fraction)."""
     return int(lib().oracle_pose_trials_needed(int(n_in), int(n), float(conf)))
+
+
+def tree_sum(p, m: int) -> np.ndarray:
+    """vo_spec.h's vo_tree_sum over p [64][stride >= m] float64 -> the m sums (p is not changed)."""
+    p = np.array(p, np.float64, order="C")
+    assert p.ndim == 2 and p.shape[0] == 64 and p.shape[1] >= m
+    lib().oracle_tree_sum(_p(p, C.c_double), p.shape[1], int(m))
+    return p[0, :m].copy()
 
 
 def philox(ctr, key) -> np.ndarray:

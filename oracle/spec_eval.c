@@ -33,6 +33,8 @@ void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
 
 int oracle_pose_trials_needed(int n_in, int n, double conf) { return vo_pose_trials_needed(n_in, n, conf); }
 
+void oracle_tree_sum(double* p, int stride, int m) { vo_tree_sum(p, stride, m); }
+
 int oracle_gauss_radius(double sigma)
 {
     float k[VO_SIFT_MAX_RADIUS + 1];

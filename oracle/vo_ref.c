@@ -331,7 +331,7 @@ static int msac_hypothesis(const double* img, const double* world, int n, const 
     return 1;
 }
 
-/* MSAC score: 64 lane-strided partial sums + pairwise tree */
+/* MSAC score: 64 lane-strided partial sums + vo_tree_sum */
 static double msac_score(const double R[9], const double t[3], const double* img, const double* world, int n,
                          const double K[9], double thr, int* n_in)
 {
@@ -343,8 +343,7 @@ static double msac_score(const double R[9], const double t[3], const double* img
         if (e < thr) cnt++;
         part[k & 63] = part[k & 63] + (e < thr ? e : thr);
     }
-    for (int off = 32; off >= 1; off >>= 1)
-        for (int l = 0; l < off; ++l) part[l] = part[l] + part[l + off];
+    vo_tree_sum(part, 1, 1);
     *n_in = cnt;
     return part[0];
 }

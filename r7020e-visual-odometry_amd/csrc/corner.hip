@@ -17,6 +17,7 @@
 // the image's, keys staged through LDS in tiles of 256 -- a corner's rank is the number of larger keys,
 // and ranks below N are written to the ranked list.
 #include "vo_internal.h"
+#include "wave.h"
 
 namespace vo {
 
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_corner_metric(CornerArgs a)
         a.metric[plane + (size_t)r * cols + c] = m;
         if (r >= a.y0 && r < a.y0 + a.h && c >= a.x0 && c < a.x0 + a.w) best = max(best, vo_corner_max_bits(m));
     }
-    for (int off = 32; off >= 1; off >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, off));
+    best = wave_max(best);
     if ((tid & 63) == 0) wmax[tid >> 6] = best;
     __syncthreads();
     if (tid == 0) {
@@ -131,10 +132,8 @@ __global__ __launch_bounds__(256) void k_corner_count(CornerSelArgs a)
             int r, c;
             n += corner_test(a, m, blockIdx.x * CORNER_CHUNK + k * 256 + tid, thr, r, c) ? 1 : 0;
         }
-    for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off);
-    if ((tid & 63) == 0) wc[tid >> 6] = n;
-    __syncthreads();
-    if (tid == 0) a.cnt[(size_t)img * a.n_chunks + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+    n = block_sum<4>(n, wc);
+    if (tid == 0) a.cnt[(size_t)img * a.n_chunks + blockIdx.x] = n;
 }
 
 __global__ __launch_bounds__(256) void k_corner_emit(CornerSelArgs a)
@@ -148,20 +147,17 @@ __global__ __launch_bounds__(256) void k_corner_emit(CornerSelArgs a)
     // corners in the chunks before this one
     int before = 0;
     for (int b = tid; b < (int)blockIdx.x; b += 256) before += cnt[b];
-    for (int off = 32; off >= 1; off >>= 1) before += __shfl_xor(before, off);
-    if (lane == 0) wc[wave] = before;
-    __syncthreads();
-    int base = wc[0] + wc[1] + wc[2] + wc[3];
+    int base = block_sum<4>(before, wc);
     if ((int)blockIdx.x == a.n_chunks - 1 && tid == 0) a.total[img] = base + cnt[blockIdx.x];
     if (!(mmax > 0.0f) || cnt[blockIdx.x] == 0) return;       // block-uniform
     for (int k = 0; k < CORNER_CHUNK / 256; ++k) {
         int r = 0, c = 0;
         const bool is = corner_test(a, m, blockIdx.x * CORNER_CHUNK + k * 256 + tid, thr, r, c);
-        const unsigned long long mask = __ballot(is);
+        int n_wave;
+        int pos = base + wave_rank(is, &n_wave);
         __syncthreads();                                      // the previous round's readers are done
-        if (lane == 0) wc[wave] = __popcll(mask);
+        if (lane == 0) wc[wave] = n_wave;
         __syncthreads();
-        int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
         for (int v = 0; v < wave; ++v) pos += wc[v];
         if (is && pos < a.cap) {
             float x, y;

@@ -28,6 +28,7 @@
 // is vo_spec.h's, compiled here and by oracle/vo_ref.c; only the quartic's root finder exists in two
 // forms (real_roots_trim below, real_roots there), operation for operation.
 #include "vo_geom.h"
+#include "wave.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -322,7 +323,7 @@ __device__ void msac_hyp_slot(const MsacArgs& a, int f, int s, int n)
     h->valid = 1;
 }
 
-// MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed shuffle tree
+// MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed tree (wave_sum)
 __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s, int n, int lane)
 {
     MsacHyp* h = a.hyp + (size_t)f * a.n_hyp + s;
@@ -338,11 +339,8 @@ __device__ __forceinline__ void msac_score_slot(const MsacArgs& a, int f, int s,
         if (e < a.thr) cnt++;
         part = part + (e < a.thr ? e : a.thr);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        part = part + __shfl_down(part, off);
-        cnt += __shfl_xor(cnt, off);
-    }
+    part = wave_sum(part);
+    cnt = wave_sum_xor(cnt);
     if (lane == 0) { h->score = part; h->n_in = cnt; }
 }
 
@@ -369,8 +367,7 @@ __device__ void msac_final(const MsacArgs& a, int f, int n, int best, int status
         a.inliers[(size_t)f * a.kp_cap + k] = (uint8_t)in;
         cnt += in;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+    cnt = wave_sum(cnt);
     if (lane == 0) {
         g->n_inliers = cnt;
         vo_pose_to_T(R, t, g->T);
@@ -447,9 +444,8 @@ struct RefineArgs {
 };
 
 // One pass of the wave over the frame's points: lane l sums the points k = l (mod 64) in ascending
-// k, then the xor butterfly -- the fixed tree of msac_score_slot; every level adds the same two
-// values in both partner lanes, so all 64 lanes end with the bits of the tree's p[0] and every
-// decision taken on the sums is wave-uniform.
+// k, then wave_sum -- the fixed tree of msac_score_slot; all 64 lanes end with the bits of the
+// tree's p[0], so every decision taken on the sums is wave-uniform.
 __device__ __forceinline__ void refine_pass(const double* K, const double* img, const double* world, const uint8_t* use, int n,
                                             int lane, const double* R, const double* t, const double* z0, double* sums,
                                             int& n_used, int& behind)
@@ -459,15 +455,9 @@ __device__ __forceinline__ void refine_pass(const double* K, const double* img, 
     int cnt = 0, bh = 0;
     for (int k = lane; k < n; k += VO_REFINE_LANES)
         cnt += vo_refine_point(R, t, z0, K, world + 3 * k, img + 2 * k, use[k], sums, &bh);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int q = 0; q < VO_REFINE_NSUM; ++q) sums[q] = sums[q] + __shfl_xor(sums[q], off);
-        cnt += __shfl_xor(cnt, off);
-        bh |= __shfl_xor(bh, off);
-    }
-    n_used = cnt;
-    behind = bh;
+    wave_sum_xor<VO_REFINE_NSUM>(sums);
+    n_used = wave_sum_xor(cnt);
+    behind = wave_sum_xor(bh) != 0;                         // bh is 0 or 1 per lane: any lane's
 }
 
 // Wave-uniform doubles moved, not computed (the bits stay): into scalar registers, and parked
@@ -658,7 +648,7 @@ __device__ __forceinline__ void fund_hyp_slot(const FundArgs& a, const float* x1
     }
 }
 
-// MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed shuffle tree (msac_score_slot)
+// MSAC score of one valid slot by one wave: 64 lane-strided partials + the fixed tree (msac_score_slot)
 __device__ __forceinline__ void fund_score_slot(FundHyp* h, const float* x1, const float* x2, int n, double thr, int lane)
 {
     double F[9];
@@ -672,19 +662,9 @@ __device__ __forceinline__ void fund_score_slot(FundHyp* h, const float* x1, con
         if (e < thr) cnt++;
         part = part + (e < thr ? e : thr);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        part = part + __shfl_down(part, off);
-        cnt += __shfl_xor(cnt, off);
-    }
+    part = wave_sum(part);
+    cnt = wave_sum(cnt);
     if (lane == 0) { h->score = part; h->n_in = cnt; }
-}
-
-__device__ __forceinline__ double fund_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);      // the tree's p[0] in every lane (refine_pass)
-    return v;
 }
 
 // The masked Norm8 fit by one wave: lane l is partial l of the three passes; the 45 sums of the last
@@ -700,9 +680,8 @@ __device__ __forceinline__ int fund_refit(const float* x1, const float* x2, cons
         ++m;
         s0 = s0 + (double)p1.x; s1 = s1 + (double)p1.y; s2 = s2 + (double)p2.x; s3 = s3 + (double)p2.y;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m += __shfl_xor(m, off);
-    s0 = fund_wave_sum(s0); s1 = fund_wave_sum(s1); s2 = fund_wave_sum(s2); s3 = fund_wave_sum(s3);
+    m = wave_sum(m);
+    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
     double N1[3], N2[3];
     N1[1] = s0 / (double)m; N1[2] = s1 / (double)m; N2[1] = s2 / (double)m; N2[2] = s3 / (double)m;
     double d1 = 0.0, d2 = 0.0;
@@ -712,7 +691,7 @@ __device__ __forceinline__ int fund_refit(const float* x1, const float* x2, cons
         d1 = d1 + vo_fund_dist((double)p1.x, (double)p1.y, N1[1], N1[2]);
         d2 = d2 + vo_fund_dist((double)p2.x, (double)p2.y, N2[1], N2[2]);
     }
-    d1 = fund_wave_sum(d1); d2 = fund_wave_sum(d2);
+    d1 = wave_sum(d1); d2 = wave_sum(d2);
     N1[0] = VO_FUND_SQRT2 / (d1 / (double)m);
     N2[0] = VO_FUND_SQRT2 / (d2 / (double)m);
     if (!vo_fund_finite(N1[0]) || !vo_fund_finite(N2[0])) return 0;            // wave-uniform: the sums are
@@ -723,7 +702,7 @@ __device__ __forceinline__ int fund_refit(const float* x1, const float* x2, cons
         vo_fund_row(N1, N2, (double)p1.x, (double)p1.y, (double)p2.x, (double)p2.y, W + lane, VO_FUND_CHUNK);
     }
     for (int q = 0; q < VO_FUND_NSUM; ++q) {
-        const double v = fund_wave_sum(W[q * VO_FUND_CHUNK + lane]);
+        const double v = wave_sum(W[q * VO_FUND_CHUNK + lane]);
         if (lane == 0) W[q * VO_FUND_CHUNK] = v;
     }
     const int ok = fund_solve_group(W, lane & (VO_FUND_GROUP - 1), lane < VO_FUND_GROUP, 1, N1, N2, F);   // lanes 0 .. 7 on column 0
@@ -802,8 +781,7 @@ __global__ __launch_bounds__(VO_FUND_T) void k_fund_msac(FundArgs a)
     int cnt = 0;
     if (status == VO_OK) {
         for (int k = lane; k < n; k += VO_FUND_LANES) cnt += mask[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+        cnt = wave_sum(cnt);
         if (!fund_refit(x1, x2, mask, n, lane, s_w, F)) status = VO_ERR_NO_CONSENSUS;
     }
     if (status != VO_OK) {
@@ -839,33 +817,6 @@ __global__ void k_stereo_pos(const vo_keypoint* __restrict__ kp, int kp_cap, con
     if (blockIdx.x == 0 && threadIdx.x == 0) s_n[f] = n;
 }
 
-__device__ __forceinline__ uint32_t block_exscan_1024_g(uint32_t v, uint32_t* sh, uint32_t* total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        uint32_t s = lane < 16 ? sh[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            uint32_t y = __shfl_up(s, o);
-            if (lane >= o) s += y;
-        }
-        if (lane < 16) sh[16 + lane] = s;
-    }
-    __syncthreads();
-    uint32_t before = wid ? sh[16 + wid - 1] : 0;
-    *total = sh[16 + 15];
-    __syncthreads();
-    return before + x - v;
-}
-
 // new-landmark filter (VO.m:147-154) + compaction.  one block (1024) per frame.
 // old positions: oldpos[f][k] (x1, y1, x2, y2) for k < *kn (kn[f * kn_stride]).
 // flags: per-frame byte scratch (lm_keep, rewritten later by k_lm_tri).
@@ -880,7 +831,7 @@ __global__ __launch_bounds__(1024) void k_lm_filter(const float* __restrict__ sp
     // through LDS 1024 at a time and every thread compares its match against all of
     // them (broadcast reads).  hit = any old left x == lx or any old left y == ly, or
     // likewise on the right (VO.m:150-151, exact float equality).
-    __shared__ uint32_t sh[32];
+    __shared__ uint32_t sh[16];
     __shared__ float4 so[1024];
     const int f = blockIdx.x, tid = threadIdx.x, K = kp_cap;
     int S = s_n[f];
@@ -921,7 +872,7 @@ __global__ __launch_bounds__(1024) void k_lm_filter(const float* __restrict__ sp
         const uint32_t isnew = (valid && !hit) ? 1u : 0u;
         if (valid) fl[j] = (uint8_t)isnew;
         uint32_t total;
-        const uint32_t pos = block_exscan_1024_g(isnew, sh, &total);
+        const uint32_t pos = block_excl_scan<16>(isnew, sh, &total);
         if (isnew) lm_new[(size_t)f * K + done + pos] = j;
         done += total;
     }
@@ -1029,8 +980,7 @@ __global__ __launch_bounds__(256) void k_lm_pack(const float* __restrict__ lm_X,
     if (tid < 64) {
         int v = 0;
         for (int g2 = tid; g2 < f; g2 += 64) v += min(lm_rows[g2], kp_cap);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        v = wave_sum(v);
         if (tid == 0) off = v;
     }
     __syncthreads();

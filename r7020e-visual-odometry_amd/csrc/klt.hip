@@ -12,9 +12,10 @@
 // taps of a sample of the second image are read straight from L1 / L2 with clamped indices: staging
 // the (bw + 1) x (bh + 1) patch through the same LDS slice was measured 17 - 20 % slower (DESIGN.md
 // 9p); the score pass, which runs once, still stages.  Lane partials are int32 (bounds: vo_spec.h),
-// the window sums int64 through a __shfl_xor tree, so every lane holds the same sums and takes the
+// the window sums int64 through wave_sum, so every lane holds the same sums and takes the
 // same f32 step: control flow is wave-uniform.
 #include "vo_internal.h"
+#include "wave.h"
 
 namespace vo {
 
@@ -64,12 +65,6 @@ static __device__ __forceinline__ void klt_stage(uint8_t* P, const uint8_t* __re
         if (x >= pw) { x -= pw; ++y; }
     }
     klt_wave_sync();
-}
-
-static __device__ __forceinline__ int64_t klt_wave_sum(int64_t v)
-{
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor((long long)v, off);
-    return v;
 }
 
 __global__ __launch_bounds__(KLT_WAVES * 64) void k_klt_track(KltArgs a)
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(KLT_WAVES * 64) void k_klt_track(KltArgs a)
                     x += rm; y += qd;
                     if (x >= bw) { x -= bw; ++y; }
                 }
-                const int64_t txx = klt_wave_sum(sxx), txy = klt_wave_sum(sxy), tyy = klt_wave_sum(syy);
+                const int64_t txx = wave_sum(sxx), txy = wave_sum(sxy), tyy = wave_sum(syy);
                 if (!vo_klt_gradient_matrix(txx, txy, tyy, bw, bh, Am)) why = VO_KLT_FLAT;
             }
             int stop = VO_KLT_STOP_NONE, j = 0;
@@ -175,7 +170,7 @@ __global__ __launch_bounds__(KLT_WAVES * 64) void k_klt_track(KltArgs a)
                         if (x >= bw) { x -= bw; ++y; }
                     }
                     float dx, dy;
-                    vo_klt_delta(Am, klt_wave_sum(s1), klt_wave_sum(s2), &dx, &dy);
+                    vo_klt_delta(Am, wave_sum(s1), wave_sum(s2), &dx, &dy);
                     qx = qx + dx; qy = qy + dy;
                     mx = qx + hx; my = qy + hy;
                     stop = vo_klt_stop(j, dx, dy, pdx, pdy, &mx, &my);
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(KLT_WAVES * 64) void k_klt_track(KltArgs a)
                     x += rm; y += qd;
                     if (x >= bw) { x -= bw; ++y; }
                 }
-                score = vo_klt_score(klt_wave_sum(s2), bw, bh);
+                score = vo_klt_score(wave_sum(s2), bw, bh);
             }
             if (!a.bidir) break;
         } else {

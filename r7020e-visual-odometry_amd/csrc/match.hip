@@ -15,6 +15,7 @@
 // ascending F1 order.
 #include "vo_internal.h"
 #include "vo_geom.h"
+#include "wave.h"
 
 namespace vo {
 
@@ -38,6 +39,27 @@ __device__ __forceinline__ void top2c_merge(float& b, int& i, float& s, float b2
     const float ns = fmaxf(fmaxf(s, s2), fminf(b, b2));
     if (b2 > b || (b2 == b && i2 < i)) { b = b2; i = i2; }
     s = ns;
+}
+// top2c_merge with the lane at xor distance off (whole wave, converged)
+__device__ __forceinline__ void top2c_merge_lanes(float& b, int& i, float& s, int off)
+{
+    const float b2 = __shfl_xor(b, off), s2 = __shfl_xor(s, off);
+    const int i2 = __shfl_xor(i, off);
+    top2c_merge(b, i, s, b2, i2, s2);
+}
+// The f32 kernels rank by SSD and a lane may hold no column yet (idx < 0, best = inf): the wave's 64
+// (best, idx, second) joined by lexicographic min on (value, index) over the lanes that hold one, and
+// the second smallest value of the union multiset; the result in every lane (whole wave, converged)
+__device__ __forceinline__ void top2s_merge_wave(float& best, int& bidx, float& second)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float b2 = __shfl_xor(best, off), s2 = __shfl_xor(second, off);
+        const int i2 = __shfl_xor(bidx, off);
+        const float ns = fminf(fminf(second, s2), fmaxf(best, b2));
+        if (i2 >= 0 && (bidx < 0 || b2 < best || (b2 == best && i2 < bidx))) { best = b2; bidx = i2; }
+        second = ns;
+    }
 }
 
 // Pointers read from the job table are generic to the compiler, so loads through them became
@@ -122,7 +144,7 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
     // task table: job j owns tasks [tstart[j], tstart[j+1]); job sizes are read on device
     // (counts of earlier kernels), one thread per job, then a block prefix sum
     __shared__ int tstart[VO_MP_MAX_JOBS + 1], jn1[VO_MP_MAX_JOBS], jnch[VO_MP_MAX_JOBS];
-    __shared__ int wsum[4];
+    __shared__ uint32_t wsum[4];
     {
         int my = 0;
         if (tid < n_jobs) {
@@ -131,15 +153,10 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
             jn1[tid] = n1; jnch[tid] = nch;
             my = ((n1 + ROWS - 1) / ROWS) * nch;
         }
-        int inc = my;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (tid < n_jobs) tstart[tid] = before + inc - my;
-        if (tid == 255) tstart[min(n_jobs, VO_MP_MAX_JOBS)] = before + inc;
+        uint32_t all;
+        const uint32_t first = block_excl_scan<4>((uint32_t)my, wsum, &all);
+        if (tid < n_jobs) tstart[tid] = (int)first;
+        if (tid == 255) tstart[min(n_jobs, VO_MP_MAX_JOBS)] = (int)all;
         __syncthreads();
     }
     const int total = tstart[n_jobs];
@@ -281,9 +298,7 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
         }
 #pragma unroll
         for (int sb = 0; sb < NB; ++sb) {
-            const float ob = __shfl_xor(best1[sb], 32), os = __shfl_xor(second1[sb], 32);
-            const int oi = __shfl_xor(bidx1[sb], 32);
-            top2c_merge(best1[sb], bidx1[sb], second1[sb], ob, oi, os);
+            top2c_merge_lanes(best1[sb], bidx1[sb], second1[sb], 32);
             const int row = i0 + 32 * sb + l31;
             if (h == 0 && row < n1) {
                 MatchTop2 mt;
@@ -302,12 +317,28 @@ __global__ __launch_bounds__(256, NB == 1 ? VO_MP_BLOCKS : 2) void k_match_parti
 // `compose` (a tracking step of find_remaining_points), the workgroup then applies that step's
 // index composition to its frame's lists (VO.m:287-333) -- so a tracking step is two launches
 // (partial, finish); as separate merge, compact and compose kernels it was four.
+// A tile's accepted rows in thread order after the `base` rows of the earlier tiles: this thread's
+// position if it holds one (ok), and base moves past the tile.  Whole 256-thread block; wsum is free
+// again at return.
+__device__ __forceinline__ uint32_t match_place(bool ok, uint32_t* wsum, uint32_t& base)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int cnt;
+    uint32_t pos = base + (uint32_t)wave_rank(ok, &cnt);
+    if (lane == 0) wsum[wid] = (uint32_t)cnt;
+    __syncthreads();
+    for (int w = 0; w < wid; ++w) pos += wsum[w];
+    base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    return pos;
+}
+
 __global__ __launch_bounds__(256) void k_match_finish(const MatchJob* __restrict__ jobs, const MatchTop2* __restrict__ partial,
                                                       int row_cap, int n_chunks_cap, float T, float max_ratio,
                                                       MatchCompose cp, int with_compose)
 {
     __shared__ uint32_t wsum[4];
-    const int jb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int jb = blockIdx.x, tid = threadIdx.x;
     const MatchJob J = jobs[jb];
     const int n1 = job_rows(J.n1, row_cap), n2 = job_rows(J.n2, row_cap);
     const int nch = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
@@ -326,15 +357,8 @@ __global__ __launch_bounds__(256) void k_match_finish(const MatchJob* __restrict
             const float bs = 2.0f - 2.0f * b, ss = 2.0f - 2.0f * s;      // SSD of best / second best
             acc = (i >= 0 && bs <= T && (bs / ss) <= max_ratio) ? i : -1;
         }
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(acc >= 0);
-        if (lane == 0) wsum[wid] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = base;
-        for (int w = 0; w < wid; ++w) before += wsum[w];
-        const uint32_t pos = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t pos = match_place(acc >= 0, wsum, base);
         if (acc >= 0 && pos < (uint32_t)J.cap) { gst(J.out_i + pos, r); gst(J.out_j + pos, acc); }
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();                                          // wsum reused by the next tile
     }
     const int n_out = (int)(base < (uint32_t)J.cap ? base : (uint32_t)J.cap);
     if (tid == 0) gst(J.out_n, n_out);
@@ -380,7 +404,7 @@ __global__ __launch_bounds__(256) void k_match_finish_unique(const MatchJob* __r
                                                              float T, float max_ratio, int unique, float* __restrict__ metric)
 {
     __shared__ uint32_t wsum[4];
-    const int jb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int jb = blockIdx.x, tid = threadIdx.x;
     const MatchJob J = jobs[jb];
     const int n1 = job_rows(J.n1, row_cap), n2 = job_rows(J.n2, row_cap);
     const int nch = (n2 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK, nchb = (n1 + VO_MATCH_CHUNK - 1) / VO_MATCH_CHUNK;
@@ -412,15 +436,8 @@ __global__ __launch_bounds__(256) void k_match_finish_unique(const MatchJob* __r
                 if (bi != r) acc = -1;
             }
         }
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(acc >= 0);
-        if (lane == 0) wsum[wid] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = base;
-        for (int w = 0; w < wid; ++w) before += wsum[w];
-        const uint32_t pos = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t pos = match_place(acc >= 0, wsum, base);
         if (acc >= 0 && pos < (uint32_t)J.cap) { gst(J.out_i + pos, r); gst(J.out_j + pos, acc); gst(M + pos, bs); }
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();                                          // wsum reused by the next tile
     }
     if (tid == 0) gst(J.out_n, (int)(base < (uint32_t)J.cap ? base : (uint32_t)J.cap));
 }
@@ -432,9 +449,7 @@ __global__ void k_desc_meta(const uint8_t* __restrict__ desc, DescMeta* __restri
     for (long t = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < n; t += (long)gridDim.x * (blockDim.x >> 6)) {
         const uint8_t* d = desc + t * VO_DESC_LEN;
         int v0 = d[lane], v1 = d[lane + 64];
-        int sum = v0 + v1, sq = v0 * v0 + v1 * v1;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { sum += __shfl_xor(sum, off); sq += __shfl_xor(sq, off); }
+        const int sum = wave_sum(v0 + v1), sq = wave_sum(v0 * v0 + v1 * v1);
         if (lane == 0) { DescMeta m; m.sum = sum; m.inv_norm = sq > 0 ? 1.0f / sqrtf((float)sq) : 0.0f; meta[t] = m; }
     }
 }
@@ -545,12 +560,8 @@ __global__ __launch_bounds__(64) void k_radius_meta(const float* __restrict__ ce
         (first ? geo1 : geo2)[i] = vo_geo4{x, y, r2, 0.0f};
         xmin = xmax = x; ymin = ymax = y; rmax = r2;
     }
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) {
-        xmin = fminf(xmin, __shfl_xor(xmin, off)); xmax = fmaxf(xmax, __shfl_xor(xmax, off));
-        ymin = fminf(ymin, __shfl_xor(ymin, off)); ymax = fmaxf(ymax, __shfl_xor(ymax, off));
-        rmax = fmaxf(rmax, __shfl_xor(rmax, off));
-    }
+    // lanes 32 .. 63 hold the identities, so the wave's extrema are the half-wave's
+    xmin = wave_min(xmin); xmax = wave_max(xmax); ymin = wave_min(ymin); ymax = wave_max(ymax); rmax = wave_max(rmax);
     if (lane == 0) {
         vo_geo4* box = (first ? box1 : box2) + 2 * (size_t)tile;
         box[0] = vo_geo4{xmin, xmax, ymin, ymax};
@@ -710,9 +721,7 @@ __global__ __launch_bounds__(256, 4) void k_match_radius(RadiusSide R, RadiusSid
             tile(buf, jt);
 #endif
         }
-        const float ob = __shfl_xor(best1, 32), os = __shfl_xor(second1, 32);
-        const int oi = __shfl_xor(bidx1, 32);
-        top2c_merge(best1, bidx1, second1, ob, oi, os);
+        top2c_merge_lanes(best1, bidx1, second1, 32);
         if (h == 0 && live) {
             MatchTop2 mt;
             mt.best = best1; mt.idx = bidx1; mt.second = second1; mt.pad = 0;
@@ -824,14 +833,7 @@ __global__ __launch_bounds__(64) void k_match_f32(const float* __restrict__ A, i
             if (ssd < best) { second = best; best = ssd; bidx = j; }
             else if (ssd < second) second = ssd;
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float b2 = __shfl_xor(best, off), s2 = __shfl_xor(second, off);
-            const int i2 = __shfl_xor(bidx, off);
-            const float ns = fminf(fminf(second, s2), fmaxf(best, b2));
-            if (i2 >= 0 && (bidx < 0 || b2 < best || (b2 == best && i2 < bidx))) { best = b2; bidx = i2; }
-            second = ns;
-        }
+        top2s_merge_wave(best, bidx, second);
         if (lane == 0) res[i] = (bidx >= 0 && best <= T && best / second <= max_ratio) ? bidx : -1;
         __syncthreads();
     }
@@ -871,14 +873,7 @@ __global__ __launch_bounds__(64) void k_match_f32_ex(const float* __restrict__ A
             if (ssd < best) { second = best; best = ssd; bidx = j; }
             else if (ssd < second) second = ssd;
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float b2 = __shfl_xor(best, off), s2 = __shfl_xor(second, off);
-            const int i2 = __shfl_xor(bidx, off);
-            const float ns = fminf(fminf(second, s2), fmaxf(best, b2));
-            if (i2 >= 0 && (bidx < 0 || b2 < best || (b2 == best && i2 < bidx))) { best = b2; bidx = i2; }
-            second = ns;
-        }
+        top2s_merge_wave(best, bidx, second);
         if (lane == 0) {
             if (res) res[i] = (bidx >= 0 && best <= T && best / second <= max_ratio) ? bidx : -1;
             if (arg) arg[i] = bidx;

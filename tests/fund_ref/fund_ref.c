@@ -1,7 +1,7 @@
 /* CPU reference of vo_est_fundamental (test infrastructure): include/vo_spec.h's own vo_fund_*
  * functions -- the ones k_fund_msac calls -- around the normative loops: a masked fit's three
- * passes in 64 partials (partial l the used points k = l mod 64 ascending, joined by the tree
- * p[i] = p[i] + p[i + off], off = 32 .. 1), the score in the same 64 partials, and the sequential
+ * passes in 64 partials (partial l the used points k = l mod 64 ascending, joined by
+ * vo_tree_sum), the score in the same 64 partials, and the sequential
  * MSAC loop slot by slot.  Compiled with the oracle's flags (no contraction, no fast-math).
  * x1, x2 [n][2] single 1-based pixels.  Status codes are include/vo.h's. */
 #include <stdint.h>
@@ -20,13 +20,6 @@ enum {
     CN_SWEEPS3, CN_IMPROVED, CN_TIES, CN_REFIT_MODEL, CN_COUNT
 };
 
-static void tree(double (*p)[VO_FUND_NSUM], int m)
-{
-    for (int off = VO_FUND_LANES / 2; off >= 1; off >>= 1)
-        for (int i = 0; i < off; ++i)
-            for (int q = 0; q < m; ++q) p[i][q] = p[i][q] + p[i + off][q];
-}
-
 /* masked Norm8: mask NULL = all -> 1 and F, or 0 (no model) */
 static int fit_masked(const float* x1, const float* x2, int n, const uint8_t* mask, double* F, int* sweeps)
 {
@@ -42,7 +35,7 @@ static int fit_masked(const float* x1, const float* x2, int n, const uint8_t* ma
             p[l][2] = p[l][2] + (double)x2[2 * k]; p[l][3] = p[l][3] + (double)x2[2 * k + 1];
         }
     }
-    tree(p, 4);
+    vo_tree_sum(&p[0][0], VO_FUND_NSUM, 4);
     N1[1] = p[0][0] / (double)m; N1[2] = p[0][1] / (double)m; N2[1] = p[0][2] / (double)m; N2[2] = p[0][3] / (double)m;
     for (int l = 0; l < VO_FUND_LANES; ++l) {
         p[l][0] = 0.0; p[l][1] = 0.0;
@@ -52,7 +45,7 @@ static int fit_masked(const float* x1, const float* x2, int n, const uint8_t* ma
             p[l][1] = p[l][1] + vo_fund_dist((double)x2[2 * k], (double)x2[2 * k + 1], N2[1], N2[2]);
         }
     }
-    tree(p, 2);
+    vo_tree_sum(&p[0][0], VO_FUND_NSUM, 2);
     N1[0] = VO_FUND_SQRT2 / (p[0][0] / (double)m);
     N2[0] = VO_FUND_SQRT2 / (p[0][1] / (double)m);
     if (!vo_fund_finite(N1[0]) || !vo_fund_finite(N2[0])) return 0;
@@ -63,7 +56,7 @@ static int fit_masked(const float* x1, const float* x2, int n, const uint8_t* ma
             vo_fund_row(N1, N2, (double)x1[2 * k], (double)x1[2 * k + 1], (double)x2[2 * k], (double)x2[2 * k + 1], p[l], 1);
         }
     }
-    tree(p, VO_FUND_NSUM);
+    vo_tree_sum(&p[0][0], VO_FUND_NSUM, VO_FUND_NSUM);
     for (int q = 0; q < VO_FUND_NSUM; ++q) W[q] = p[0][q];
     return vo_fund_solve(W, 1, N1, N2, F, sweeps);
 }
@@ -81,8 +74,7 @@ static double score(const double* F, const float* x1, const float* x2, int n, do
             p[l] = p[l] + (e < thr ? e : thr);
         }
     }
-    for (int off = VO_FUND_LANES / 2; off >= 1; off >>= 1)
-        for (int i = 0; i < off; ++i) p[i] = p[i] + p[i + off];
+    vo_tree_sum(p, 1, 1);
     *n_in = cnt;
     return p[0];
 }

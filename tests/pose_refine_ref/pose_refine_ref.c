@@ -1,8 +1,7 @@
 /* CPU reference of vo_refine_pose (test infrastructure): include/vo_spec.h's own vo_refine_*
  * functions -- the ones k_refine_pose calls -- around a pass that sums the points in the normative
- * order (64 partials, partial l the points k = l mod 64 ascending, then the tree
- * p[i] = p[i] + p[i + off], off = 32 .. 1), compiled with the oracle's flags (no contraction, no
- * fast-math).
+ * order (64 partials, partial l the points k = l mod 64 ascending, then vo_tree_sum), compiled with
+ * the oracle's flags (no contraction, no fast-math).
  * img [n][2], world [n][3], use [n] or NULL (= all), K 3x3 and T_in 4x4 row-major ->
  * T_out 4x4, stat = {status, n_used, passes, accepted}, cost = {cost_initial, cost_final}.
  * T_out is T_in by bytes when no step was accepted. */
@@ -21,9 +20,7 @@ static void pass(const double* R, const double* t, const double* z0, const doubl
         for (int k = l; k < n; k += VO_REFINE_LANES)
             cnt += vo_refine_point(R, t, z0, K, world + 3 * k, img + 2 * k, use ? use[k] : 1, p[l], behind);
     }
-    for (int off = VO_REFINE_LANES / 2; off >= 1; off >>= 1)
-        for (int i = 0; i < off; ++i)
-            for (int q = 0; q < VO_REFINE_NSUM; ++q) p[i][q] = p[i][q] + p[i + off][q];
+    vo_tree_sum(&p[0][0], VO_REFINE_NSUM, VO_REFINE_NSUM);
     for (int q = 0; q < VO_REFINE_NSUM; ++q) sums[q] = p[0][q];
     *n_used = cnt;
 }

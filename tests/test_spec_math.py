@@ -150,3 +150,26 @@ def test_pose_trials_needed_branches(oracle):
     # answers 1 there (DESIGN 3.5.2 tells why the fundamental-matrix bound does not).
     assert 1.0 - (1 / 100000) ** 4 == 1.0 and (1 / 100000) ** 4 > 1e-300
     assert oracle.pose_trials_needed(1, 100000, 0.99) == 1
+
+
+def test_tree_sum_is_the_pairwise_tree(oracle):
+    """vo_tree_sum(p, stride, m): 64 partials of m values joined by p[i] = p[i] + p[i + off], off = 32 .. 1,
+    against the same tree in NumPy float64 (elementwise IEEE additions), bit for bit, at m = 1, 28, 45
+    with the partials packed (stride = m) and padded (stride > m; the padding must not be read into
+    the sums).  The values span 12 decades, so the order of the additions shows in the last bits: a
+    left-to-right sum must differ from the tree somewhere, or this test could not tell the two apart."""
+    rng = np.random.default_rng(20261021)
+    differs = 0
+    for m in (1, 28, 45):
+        for stride in (m, m + 3):
+            p = rng.standard_normal((64, stride)) * 10.0 ** rng.integers(-6, 7, (64, stride))
+            q = p[:, :m].copy()
+            for off in (32, 16, 8, 4, 2, 1):
+                q[:off] = q[:off] + q[off:2 * off]
+            got = oracle.tree_sum(p, m)
+            assert got.tobytes() == q[0].tobytes(), (m, stride)
+            seq = np.zeros(m)
+            for l in range(64):
+                seq = seq + p[l, :m]
+            differs += int(np.count_nonzero(seq != got))
+    assert differs > 0
