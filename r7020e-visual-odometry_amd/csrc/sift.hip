@@ -1156,53 +1156,6 @@ __global__ __launch_bounds__(64) void k_ext_inner(const Pyramid* __restrict__ py
 #undef VO_ES_LOAD
 }
 
-// Block-wide exclusive scan of one value per thread (1024 threads).  The candidate compaction
-// (k_seg_count, k_seg_scan, k_seg_emit, k_scan_cands) keeps these bodies instead of wave.h's
-// block_excl_scan / block_sum: with those the four kernels were faster and the 256-frame step
-// 0.6 - 1.7 % slower in three sessions out of three.
-__device__ __forceinline__ uint32_t block_exscan_1024(uint32_t v, uint32_t* sh, uint32_t* total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        uint32_t s = lane < 16 ? sh[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            uint32_t y = __shfl_up(s, o);
-            if (lane >= o) s += y;
-        }
-        if (lane < 16) sh[16 + lane] = s;
-    }
-    __syncthreads();
-    uint32_t before = wid ? sh[16 + wid - 1] : 0;
-    *total = sh[16 + 15];
-    __syncthreads();
-    return before + x - v;
-}
-
-__device__ __forceinline__ uint32_t block_exscan_256(uint32_t v, uint32_t* sh)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int q = 0; q < wid; ++q) before += sh[q];
-    return before + x - v;
-}
-
 // Compaction in (octave, layer, row, column) order, three coalesced passes:
 // per-segment popcounts (1024 words), per-image exclusive scan of segments,
 // then each segment block scans its words and emits candidates.
