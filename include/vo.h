@@ -43,6 +43,9 @@
  *   vo_track_points_batch  Lucas-Kanade with MaxBidirectionalError, between frames or between the cameras
  *   vo_detect_corners /    detectMinEigenFeatures / detectHarrisFeatures(I, MinQuality, FilterSize, ROI):
  *   vo_detect_corners_batch cornerPoints for the tracker, without a scale space
+ *   vo_disparity_sgm /     disparitySGM(I1, I2, DisparityRange = , UniquenessThreshold = ): dense
+ *   vo_disparity_sgm_batch semi-global matching on a census cost
+ *   vo_reconstruct_scene   reconstructScene(disparityMap, reprojectionMatrix): the dense scene
  *   vo_landmarks           new-landmark filter VO.m:145-158 +
  *                          CreateLandmarksFromFeatures.m:1-21
  *   vo_step / vo_step_batch the whole loop body VO.m:70-161 (features stay
@@ -700,6 +703,73 @@ int vo_detect_corners_batch(vo_ctx* ctx, const uint8_t* imgs, int ld, int col_ma
 /* diagnostic: the metric plane of image `image` of the last launching call -> out [rows][cols].
  * VO_ERR_STATE before such a call, VO_ERR_CAPACITY when capacity < rows * cols. */
 int vo_fetch_corner_metric(vo_ctx* ctx, int image, float* out, int capacity);
+
+/* ---- disparitySGM / reconstructScene: dense stereo depth ---- */
+/* disparityMap = disparitySGM(I1, I2, DisparityRange = , UniquenessThreshold = ) on a rectified pair (left
+ * I1, right I2), then xyzPoints = reconstructScene(disparityMap, reprojectionMatrix).  The toolbox's
+ * disparitySGM is closed; the spec chosen here (vo_spec.h vo_sgm_*, DESIGN 3.5.5, shared by the device
+ * and the CPU reference, so both give the same bytes) is Hirschmueller's semi-global matching with the
+ * toolbox's documented parameters, all integers up to the sub-pixel offset:
+ *  - disparities d = min + k, k = 0 .. D - 1, D = max - min;
+ *  - cost: the Hamming distance of 62-bit census words over a 7 x 9 window under replicate [EXT], the
+ *    right image's column x - d clamped to the image;
+ *  - eight paths with penalties p1 (a change of one disparity) and p2 (any other change) [EXT], summed;
+ *  - the winner is the smallest sum, the lowest disparity among equals; with v the smallest sum more
+ *    than one disparity away it is unreliable iff 100 v < (100 + uniqueness_threshold) * its sum (the
+ *    toolbox's documented rule), invalid iff its column x - d lies outside the right image [EXT];
+ *  - a parabola through the winner's neighbours gives the sub-pixel part (f32) [EXT];
+ *  - an unreliable or invalid pixel is NaN, as the toolbox returns it.  No left-right check, no speckle
+ *    filter, no median. */
+#ifndef VO_SGM_GROUP
+#define VO_SGM_GROUP 8            /* pairs a group; vo_spec.h defines it for a translation unit without this header */
+#endif
+
+typedef struct {
+    int32_t disparity_range[2];   /* [min, max]; max - min in 8, 16, .. 128; -1024 <= min < max <= 1024; default 0 128 (DisparityRange) */
+    int32_t uniqueness_threshold; /* 0 .. 100, default 15 (UniquenessThreshold) */
+    int32_t p1, p2;               /* 0 <= p1 <= p2 <= 255, default 10 120 [EXT] */
+} vo_sgm_params;
+
+void vo_default_sgm_params(vo_sgm_params* p);
+
+/* left, right: host images taken as vo_sift_ex takes them (rows x cols the context's; row-major with row
+ * stride ld >= cols, or col_major with column stride ld >= rows); params NULL = the defaults -> disp, single
+ * precision in the input's storage order with stride ld_out (>= cols, or >= rows for col_major; the padding
+ * is left untouched).  VO_ERR_ARG, decided on the host before anything is enqueued and naming the field: a
+ * parameter outside the ranges above.  VO_ERR_STATE while step batches are pending.  The first call that
+ * launches allocates the call's own buffers (census words, the sums S -- 2 * rows * cols * D bytes a pair --
+ * and the staging of a group); a context that never calls allocates and launches nothing.  The loop state,
+ * have_features and every other entry are untouched. */
+int vo_disparity_sgm(vo_ctx* ctx, const uint8_t* left, const uint8_t* right, int rows, int cols, int ld, int col_major,
+                     const vo_sgm_params* params, float* disp, int ld_out);
+
+/* n_pairs >= 1 consecutive pairs (lefts and rights each laid out as vo_track_points_batch takes its images)
+ * -> disp [n_pairs][rows * cols], tightly packed in the input's storage order.  The pairs run in groups of
+ * at most VO_SGM_GROUP, for which the workspace is sized.  Pair f equals the single call, by bytes. */
+int vo_disparity_sgm_batch(vo_ctx* ctx, const uint8_t* lefts, const uint8_t* rights, int ld, int col_major, int n_pairs,
+                           const vo_sgm_params* params, float* disp);
+
+/* the same on device memory: d_lefts, d_rights [B][rows][cols] packed row-major -> d_disp [B][rows * cols]
+ * row-major.  Stream-ordered on the context's stream (vo_stream), not synchronised. */
+int vo_disparity_sgm_batch_dev(vo_ctx* ctx, const uint8_t* d_lefts, const uint8_t* d_rights, int B, const vo_sgm_params* params,
+                               float* d_disp);
+
+/* diagnostic: the sums S [rows][cols][D] of pair `pair` of the last launching call (of its last group: a
+ * pair of an earlier group is VO_ERR_ARG).  VO_ERR_STATE before such a call, VO_ERR_CAPACITY when capacity
+ * < rows * cols * D. */
+int vo_fetch_sgm_cost(vo_ctx* ctx, int pair, uint16_t* S, long capacity);
+
+/* the reprojection matrix Q (row-major 4 x 4, [X Y Z W]' = Q [x y d 1]') of a rectified pair from its 3 x 4
+ * projection matrices (row-major, as VO.m:27-47 reads them): P = [fx 0 cx tx; 0 fy cy 0; 0 0 1 0] with
+ * P1's tx = 0, P2's tx != 0 and equal fx, fy, cy; anything else is VO_ERR_ARG.  With b = -tx2 / fx and
+ * s = fx / fy: Q = [1 0 0 -cx1; 0 s 0 -s cy; 0 0 0 fx; 0 0 1/b -(cx1 - cx2)/b].  Host only, stateless. */
+int vo_reprojection_matrix(const double P1[12], const double P2[12], double Q[16]);
+
+/* xyzPoints = reconstructScene(disparityMap, Q): disp as vo_disparity_sgm returns it (rows x cols the
+ * context's, stride ld) -> xyz, tightly packed: [rows][cols][3] for row-major input, three column-major
+ * planes (MATLAB's rows x cols x 3) for col_major.  Pixel (x, y), 1-based: h = Q [x y d 1]' in f64,
+ * xyz = (float)(h(1:3) / h(4)); a NaN disparity gives three NaNs; nothing is clamped. */
+int vo_reconstruct_scene(vo_ctx* ctx, const float* disp, int rows, int cols, int ld, int col_major, const double Q[16], float* xyz);
 
 /* new-landmark filter (VO.m:145-158) + CreateLandmarksFromFeatures.
  * l_pos/r_pos [S][2] current stereo-matched locations; old_l/old_r [K][2]

@@ -1663,4 +1663,134 @@ VO_HD void vo_corner_location(const float* m, int rows, int cols, int r, int c, 
  * list ascending.  A corner's metric is positive, so its bits order as a u32. */
 VO_HD uint64_t vo_corner_key(float metric, uint32_t index) { return (uint64_t)vo_f32_as_u32(metric) << 32 | (uint64_t)(~index); }
 
+/* ------------------------------------------------------------------------ */
+/* disparitySGM / reconstructScene: dense stereo depth.        */
+/* Shared by k_sgm_census / k_sgm_paths / k_sgm_select / k_reconstruct and    */
+/* the CPU reference (tests/sgm_ref).  Integers up to the sub-pixel offset    */
+/* (one f32 division, one f32 addition); reconstructScene is f64 basic        */
+/* operations in the order written.                                           */
+/*                                                                           */
+/* Disparities searched: d = dmin + k, k = 0 .. D - 1, D = dmax - dmin in     */
+/* 8, 16, .. 128.  Census: 7 rows x 9 columns about the pixel under           */
+/* replicate, one bit per neighbour in raster order, the centre left out,     */
+/* 1 iff neighbour < centre: 62 bits.  C(y, x, k) = popcount(cL(y, x) ^       */
+/* cR(y, clamp(x - (dmin + k)))) in 0 .. 62.  Eight paths r; at a path's      */
+/* first pixel L_r = C, else with m = min_j L_r(p - r, j)                     */
+/*   L_r(p, k) = C + min(L(k), L(k - 1) + P1, L(k + 1) + P1, m + P2) - m,     */
+/* a neighbour outside 0 .. D - 1 absent.  By induction L_r <= 62 + P2 <=     */
+/* 317 (the last argument bounds the minimum by P2 above m), so S = sum_r L_r */
+/* <= 8 * 317 = 2536 fits a uint16_t and every intermediate an int.           */
+/* ------------------------------------------------------------------------ */
+#define VO_SGM_MAX_D 128
+#ifndef VO_SGM_GROUP
+#define VO_SGM_GROUP 8
+#endif
+#define VO_SGM_NDIR 8
+#define VO_SGM_CENSUS_RY 3
+#define VO_SGM_CENSUS_RX 4
+#define VO_SGM_ABSENT 0x3fff      /* an absent neighbour: above every L + P */
+#define VO_NAN_BITS 0x7fc00000u   /* the NaN both entries return */
+
+VO_HD int vo_sgm_clamp(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+/* the direction r of path set q = 0 .. 7 as (dy, dx): q and q ^ 1 are opposite */
+VO_HD void vo_sgm_dir(int q, int* dy, int* dx)
+{
+    const int s = (q & 1) ? -1 : 1;
+    const int h = q >> 1;                      /* 0: along a row, 1: along a column, 2: diagonal, 3: anti-diagonal */
+    *dy = h == 0 ? 0 : s;
+    *dx = h == 0 ? s : (h == 1 ? 0 : (h == 2 ? s : -s));
+}
+
+/* the census word of pixel (y, x) of a tightly packed u8 image */
+VO_HD uint64_t vo_sgm_census(const uint8_t* img, int rows, int cols, int y, int x)
+{
+    const int c = img[(long)y * cols + x];
+    uint64_t w = 0;
+    for (int dy = -VO_SGM_CENSUS_RY; dy <= VO_SGM_CENSUS_RY; ++dy)
+        for (int dx = -VO_SGM_CENSUS_RX; dx <= VO_SGM_CENSUS_RX; ++dx) {
+            if (dy == 0 && dx == 0) continue;
+            const int n = img[(long)vo_sgm_clamp(y + dy, rows) * cols + vo_sgm_clamp(x + dx, cols)];
+            w = (w << 1) | (uint64_t)(n < c ? 1 : 0);
+        }
+    return w;
+}
+
+VO_HD int vo_sgm_popcount(uint64_t w)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popcll(w);
+#else
+    return __builtin_popcountll(w);
+#endif
+}
+
+/* the right image's column that disparity d pairs with column x (clamped: the volume is total) */
+VO_HD int vo_sgm_right_col(int x, int d, int cols) { return vo_sgm_clamp(x - d, cols); }
+
+/* one step of a path at one disparity: c = C(p, k); lk, lm, lp = L_r(p - r, k), (k - 1), (k + 1), the last
+ * two VO_SGM_ABSENT outside 0 .. D - 1; m = min_j L_r(p - r, j) */
+VO_HD int vo_sgm_step(int c, int lk, int lm, int lp, int m, int P1, int P2)
+{
+    int best = lk;
+    if (lm + P1 < best) best = lm + P1;
+    if (lp + P1 < best) best = lp + P1;
+    if (m + P2 < best) best = m + P2;
+    return c + best - m;
+}
+
+/* the disparity of one pixel in column x from its D sums S: the winner (lowest k on ties), the uniqueness
+ * test, the validity of the matched column, the sub-pixel offset.  NaN: unreliable or invalid. */
+VO_HD float vo_sgm_select(const uint16_t* S, int D, int dmin, int x, int cols, int U)
+{
+    int ks = 0;
+    uint32_t V = S[0];
+    for (int k = 1; k < D; ++k) if (S[k] < V) { V = S[k]; ks = k; }
+    uint32_t v = 0xffffu;
+    for (int k = 0; k < D; ++k) if ((k < ks - 1 || k > ks + 1) && S[k] < v) v = S[k];
+    const int d = dmin + ks, xr = x - d;
+    if (100u * v < (100u + (uint32_t)U) * V) return vo_u32_as_f32(VO_NAN_BITS);
+    if (xr < 0 || xr > cols - 1) return vo_u32_as_f32(VO_NAN_BITS);
+    if (ks > 0 && ks < D - 1) {
+        const int a = S[ks - 1], b = S[ks + 1];
+        const int den = 2 * (a - 2 * (int)V + b);
+        /* the lowest k wins a tie, so a > V strictly and den = 2 ((a - V) + (b - V)) > 0 at every interior winner:
+         * the test never fails and the offset lies in (-0.5, +0.5]; it stands for the division's sake */
+        if (den > 0) return (float)d + (float)(a - b) / (float)den;
+    }
+    return (float)d;
+}
+
+/* reconstructScene at pixel (x1, y1), 1-based, x = column; Q row-major 4 x 4 */
+VO_HD void vo_reconstruct_point(const double* Q, int x1, int y1, float disp, float* xyz)
+{
+    if (disp != disp) { xyz[0] = xyz[1] = xyz[2] = vo_u32_as_f32(VO_NAN_BITS); return; }
+    const double x = (double)x1, y = (double)y1, d = (double)disp;
+    double h[4];
+    for (int i = 0; i < 4; ++i) h[i] = ((Q[4 * i] * x + Q[4 * i + 1] * y) + Q[4 * i + 2] * d) + Q[4 * i + 3];
+    for (int i = 0; i < 3; ++i) xyz[i] = (float)(h[i] / h[3]);
+}
+
+/* Q of a rectified pair from its 3 x 4 projection matrices (row-major), host only: 0, or -1 when the pair
+ * is not of the form [fx 0 cx tx; 0 fy cy 0; 0 0 1 0] with P1's tx = 0, P2's tx != 0 and equal fx, fy, cy */
+static inline int vo_reprojection_from_projections(const double* P1, const double* P2, double* Q)
+{
+    static const int zeros[7] = {1, 3, 4, 7, 8, 9, 11};
+    for (int k = 0; k < 12; ++k) if (!(P1[k] == P1[k] && P2[k] == P2[k] && P1[k] - P1[k] == 0.0 && P2[k] - P2[k] == 0.0)) return -1;
+    for (int k = 0; k < 7; ++k) {
+        if (P1[zeros[k]] != 0.0) return -1;
+        if (zeros[k] != 3 && P2[zeros[k]] != 0.0) return -1;
+    }
+    if (P2[3] == 0.0 || P1[10] != 1.0 || P2[10] != 1.0) return -1;
+    if (P1[0] != P2[0] || P1[5] != P2[5] || P1[6] != P2[6] || P1[0] == 0.0 || P1[5] == 0.0) return -1;
+    const double fx = P1[0], fy = P1[5], cy = P1[6], cx1 = P1[2], cx2 = P2[2];
+    const double b = -P2[3] / P2[0], s = fx / fy;
+    for (int k = 0; k < 16; ++k) Q[k] = 0.0;
+    Q[0] = 1.0; Q[3] = -cx1;
+    Q[5] = s; Q[7] = -s * cy;
+    Q[11] = fx;
+    Q[14] = 1.0 / b; Q[15] = -(cx1 - cx2) / b;
+    return 0;
+}
+
 #endif /* VO_SPEC_H */

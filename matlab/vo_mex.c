@@ -51,6 +51,12 @@
  *   [Location, Metric] = vo_mex('corners', I, opts)
  *        detectMinEigenFeatures / detectHarrisFeatures(I, MinQuality = , FilterSize = , ROI = ): vo_detect_corners;
  *        N x 2 single [x y] 1-based, N x 1 single (matlab/detectMinEigenFeatures.m, matlab/detectHarrisFeatures.m)
+ *   disparityMap = vo_mex('disparitysgm', I1, I2, opts)
+ *        disparitySGM(I1, I2, DisparityRange = , UniquenessThreshold = ) of a rectified pair: vo_disparity_sgm;
+ *        rows x cols single, NaN where unreliable (matlab/disparitySGM.m)
+ *   xyz = vo_mex('reconstructscene', disparityMap, Q)
+ *        reconstructScene(disparityMap, reprojectionMatrix): vo_reconstruct_scene; rows x 3 cols single, the
+ *        memory of MATLAB's rows x cols x 3 (matlab/reconstructScene.m reshapes it)
  *   rows = vo_mex('landmarks', features_l, features_r, P1, P2, A)
  *        CreateLandmarksFromFeatures.m:2-18 (the rows before the :20 append)
  *   [rel_A, A, status, nLandmarks] = vo_mex('step', Il, Ir, P1, P2)
@@ -906,6 +912,67 @@ static void cmd_corners(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs
     mxFree(loc); mxFree(met);
 }
 
+/* vo_disparity_sgm / vo_reconstruct_scene through weak references: with a libvo that lacks them the two
+ * commands raise vo:disparitySGM:unavailable after their argument checks and every other command runs as
+ * before */
+extern __typeof__(vo_disparity_sgm) vo_disparity_sgm __attribute__((weak));
+extern __typeof__(vo_default_sgm_params) vo_default_sgm_params __attribute__((weak));
+extern __typeof__(vo_reconstruct_scene) vo_reconstruct_scene __attribute__((weak));
+
+/* disparityMap = vo_mex('disparitysgm', I1, I2, opts)
+ * I1, I2 uint8 images of one size (left, right; rectified); opts (optional) = [min max UniquenessThreshold] or
+ * [min max UniquenessThreshold p1 p2] double.  The images go to libvo as MATLAB holds them and the map is
+ * written into the output array: no copy, no transpose on the host. */
+static void cmd_disparitysgm(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    if (nrhs != 3 && nrhs != 4) need_args(nrhs, 3, "disparitysgm");
+    if (nlhs > 1) mexErrMsgIdAndTxt("vo:badArgument", "disparitysgm returns disparityMap");
+    const mxArray* I1 = prhs[1];
+    const mxArray* I2 = prhs[2];
+    need_real(I1, mxUINT8_CLASS, -1, -1, "I1");
+    need_real(I2, mxUINT8_CLASS, (long)mxGetM(I1), (long)mxGetN(I1), "I2");
+    if (nrhs == 4) {
+        need_real(prhs[3], mxDOUBLE_CLASS, 1, -1, "opts");
+        if (mxGetN(prhs[3]) != 3 && mxGetN(prhs[3]) != 5) mexErrMsgIdAndTxt("vo:badArgument", "opts must be 1 x 3 or 1 x 5");
+    }
+    if (!vo_disparity_sgm || !vo_default_sgm_params)
+        mexErrMsgIdAndTxt("vo:disparitySGM:unavailable", "this libvo has no vo_disparity_sgm: use the toolbox's "
+                          "disparitySGM, or link a newer libvo");
+    vo_sgm_params sp;
+    vo_default_sgm_params(&sp);
+    if (nrhs == 4) {
+        const double* o = mxGetDoubles(prhs[3]);
+        const int n = (int)mxGetN(prhs[3]);
+        int32_t* f[5] = {&sp.disparity_range[0], &sp.disparity_range[1], &sp.uniqueness_threshold, &sp.p1, &sp.p2};
+        for (int k = 0; k < n; ++k)                                   /* not an integer in -2^20 .. 2^20: refused by libvo */
+            *f[k] = (o[k] >= -1048576.0 && o[k] <= 1048576.0 && o[k] == (double)(int32_t)o[k]) ? (int32_t)o[k] : INT32_MIN;
+    }
+    const int rows = (int)mxGetM(I1), cols = (int)mxGetN(I1);
+    need_ctx(rows, cols);
+    plhs[0] = mxCreateNumericMatrix(rows, cols, mxSINGLE_CLASS, mxREAL);
+    check(vo_disparity_sgm(g_ctx, mxGetUint8s(I1), mxGetUint8s(I2), rows, cols, rows, 1, &sp, mxGetSingles(plhs[0]), rows));
+}
+
+/* xyz = vo_mex('reconstructscene', disparityMap, Q)
+ * disparityMap rows x cols single; Q 4 x 4 double with [X Y Z W]' = Q * [x y d 1]' (include/vo.h's).  xyz is
+ * rows x (3 cols) single: the three column-major planes of MATLAB's rows x cols x 3, written in place. */
+static void cmd_reconstructscene(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
+{
+    need_args(nrhs, 3, "reconstructscene");
+    if (nlhs > 1) mexErrMsgIdAndTxt("vo:badArgument", "reconstructscene returns xyzPoints");
+    const mxArray* D = prhs[1];
+    need_real(D, mxSINGLE_CLASS, -1, -1, "disparityMap");
+    double Q[16];
+    to_row_major(prhs[2], Q, 4, 4, "Q");
+    if (!vo_reconstruct_scene)
+        mexErrMsgIdAndTxt("vo:disparitySGM:unavailable", "this libvo has no vo_reconstruct_scene: use the toolbox's "
+                          "reconstructScene, or link a newer libvo");
+    const int rows = (int)mxGetM(D), cols = (int)mxGetN(D);
+    need_ctx(rows, cols);
+    plhs[0] = mxCreateNumericMatrix(rows, (size_t)3 * cols, mxSINGLE_CLASS, mxREAL);
+    check(vo_reconstruct_scene(g_ctx, mxGetSingles(D), rows, cols, rows, 1, Q, mxGetSingles(plhs[0])));
+}
+
 /* CreateLandmarksFromFeatures(features_l, features_r, P1, P2, pose, ~) rows (:2-18): VO.m:145-158
  * has already filtered the points, so libvo's own filter runs against no old points (K = 0). */
 static void cmd_landmarks(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
@@ -984,6 +1051,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     else if (!strcmp(cmd, "fundamental")) cmd_fundamental(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "trackpoints")) cmd_trackpoints(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "corners")) cmd_corners(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "disparitysgm")) cmd_disparitysgm(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "reconstructscene")) cmd_reconstructscene(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks")) cmd_landmarks(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "step")) cmd_step(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "landmarks_all")) cmd_landmarks_all(nlhs, plhs, nrhs, prhs);

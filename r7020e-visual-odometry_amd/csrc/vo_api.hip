@@ -165,6 +165,7 @@ struct vo_ctx {
     FundBuffers fund;                // vo_est_fundamental / vo_est_fundamental_batch (allocated on first use)
     KltBuffers klt;                  // vo_track_points / vo_track_points_batch (allocated on first use)
     CornerBuffers corner;            // vo_detect_corners / vo_detect_corners_batch (allocated on first use)
+    SgmBuffers sgm;                  // vo_disparity_sgm* / vo_reconstruct_scene (allocated on first use)
     int* d_bad = nullptr;
     int* d_mi = nullptr; int* d_mj = nullptr; int* d_mn = nullptr;
     // Pipelined full path (vo_step_submit_dev / vo_step_collect): batch n uses buffer set
@@ -256,6 +257,10 @@ void vo_default_corner_params(vo_corner_params* p)
 {
     p->method = VO_CORNER_MINEIG; p->filter_size = 5; p->min_quality = 0.01f; p->strongest = 0;
     for (int k = 0; k < 4; ++k) p->roi[k] = 0;
+}
+void vo_default_sgm_params(vo_sgm_params* p)
+{
+    p->disparity_range[0] = 0; p->disparity_range[1] = 128; p->uniqueness_threshold = 15; p->p1 = 10; p->p2 = 120;
 }
 
 const char* vo_last_error(const vo_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
@@ -2365,6 +2370,150 @@ int vo_fetch_corner_metric(vo_ctx* c, int image, float* out, int capacity)
     if (!out || capacity < 0 || (size_t)capacity < fs) return fail(c, VO_ERR_CAPACITY, "vo_fetch_corner_metric: %zu floats needed", fs);
     CallScope call(c); if (call.status) return call.status;
     HIPC(c, hipMemcpyAsync(out, cb.metric + (size_t)image * fs, sizeof(float) * fs, hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+// ---- disparitySGM / reconstructScene (vo.h: "dense stereo depth") ---------------------------------
+// -> nullptr when the block is inside the ranges of include/vo.h, else the offending field
+static const char* sgm_params_refusal(const vo_sgm_params& p)
+{
+    const int lo = p.disparity_range[0], hi = p.disparity_range[1];
+    if (lo < -1024 || hi > 1024 || lo >= hi) return "disparity_range (-1024 <= min < max <= 1024)";
+    if ((hi - lo) % 8 != 0 || hi - lo > VO_SGM_MAX_D) return "disparity_range (max - min in 8, 16, .. 128)";
+    if (p.uniqueness_threshold < 0 || p.uniqueness_threshold > 100) return "uniqueness_threshold (0 .. 100)";
+    if (p.p1 < 0 || p.p1 > 255) return "p1 (0 .. 255)";
+    if (p.p2 < p.p1 || p.p2 > 255) return "p2 (p1 .. 255)";
+    return nullptr;
+}
+
+// the host entries: n_pairs pairs in groups of VO_SGM_GROUP through the staging of one group; ld_out is
+// honoured for one pair, a batch's output is tightly packed
+static int sgm_host(vo_ctx* c, const char* who, const uint8_t* lefts, const uint8_t* rights, int ld, int col_major, int n_pairs,
+                    const vo_sgm_params* params, float* disp, int ld_out)
+{
+    if (!c || !lefts || !rights || !disp || n_pairs < 1 || n_pairs > (1 << 19) || (col_major != 0 && col_major != 1) ||
+        ld < (col_major ? c->rows : c->cols) || ld_out < (col_major ? c->rows : c->cols))
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    // every refusal before anything is enqueued
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    vo_sgm_params p;
+    if (params) p = *params; else vo_default_sgm_params(&p);
+    if (const char* field = sgm_params_refusal(p)) return fail(c, VO_ERR_ARG, "%s: parameter out of range: %s", who, field);
+    CallScope call(c); if (call.status) return call.status;
+    SgmBuffers& sb = c->sgm;
+    const int rows = c->rows, cols = c->cols, D = p.disparity_range[1] - p.disparity_range[0];
+    const int G = std::min(n_pairs, VO_SGM_GROUP);
+    {
+        if (G > sb.cap_pairs || D > sb.cap_D || G > sb.cap_io)
+            HIPC(c, hipStreamSynchronize(c->stream));          // the old buffers' last reader (a _batch_dev call is not synchronised)
+        const hipError_t e = sgm_reserve(c->pool, sb, rows, cols, G, D, true);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t fs = (size_t)rows * cols;
+    const int major = col_major ? rows : cols, minor = col_major ? cols : rows;     // the output's contiguous and strided extents
+    for (int g0 = 0; g0 < n_pairs; g0 += VO_SGM_GROUP) {
+        const int g = std::min(VO_SGM_GROUP, n_pairs - g0);
+        uint8_t* d_l = sb.img;
+        uint8_t* d_r = sb.img + (size_t)sb.cap_io * fs;
+        for (int which = 0; which < 2; ++which) {
+            const uint8_t* src = (which ? rights : lefts) + (size_t)g0 * ld * (col_major ? cols : rows);
+            uint8_t* dst = which ? d_r : d_l;
+            if (!col_major && ld == cols) HIPC(c, hipMemcpyAsync(dst, src, fs * g, hipMemcpyHostToDevice, c->stream));
+            else { int rc = stage_images(c, src, ld, col_major, g, dst); if (rc) return rc; }
+        }
+        sgm_launch(sb, d_l, d_r, rows, cols, g, p, col_major, sb.disp, c->stream);
+        sb.last_pairs = g; sb.last_first = g0; sb.last_D = D;
+        if (n_pairs == 1)
+            HIPC(c, hipMemcpy2DAsync(disp, sizeof(float) * ld_out, sb.disp, sizeof(float) * major, sizeof(float) * major, minor,
+                                     hipMemcpyDeviceToHost, c->stream));
+        else
+            HIPC(c, hipMemcpyAsync(disp + (size_t)g0 * fs, sb.disp, sizeof(float) * fs * g, hipMemcpyDeviceToHost, c->stream));
+    }
+    return finish(c);
+}
+
+int vo_disparity_sgm(vo_ctx* c, const uint8_t* left, const uint8_t* right, int rows, int cols, int ld, int col_major,
+                     const vo_sgm_params* params, float* disp, int ld_out)
+{
+    if (!c || rows != c->rows || cols != c->cols) return fail(c, VO_ERR_ARG, "vo_disparity_sgm: bad arguments");
+    return sgm_host(c, "vo_disparity_sgm", left, right, ld, col_major, 1, params, disp, ld_out);
+}
+
+int vo_disparity_sgm_batch(vo_ctx* c, const uint8_t* lefts, const uint8_t* rights, int ld, int col_major, int n_pairs,
+                           const vo_sgm_params* params, float* disp)
+{
+    if (!c) return VO_ERR_ARG;
+    if (n_pairs == 1 && (col_major == 0 || col_major == 1))       // the single call's copy with a tight stride
+        return sgm_host(c, "vo_disparity_sgm_batch", lefts, rights, ld, col_major, 1, params, disp, col_major ? c->rows : c->cols);
+    return sgm_host(c, "vo_disparity_sgm_batch", lefts, rights, ld, col_major, n_pairs, params, disp, 1 << 30);
+}
+
+int vo_disparity_sgm_batch_dev(vo_ctx* c, const uint8_t* d_lefts, const uint8_t* d_rights, int B, const vo_sgm_params* params,
+                               float* d_disp)
+{
+    const char* who = "vo_disparity_sgm_batch_dev";
+    if (!c || !d_lefts || !d_rights || !d_disp || B < 1 || B > (1 << 19)) return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    vo_sgm_params p;
+    if (params) p = *params; else vo_default_sgm_params(&p);
+    if (const char* field = sgm_params_refusal(p)) return fail(c, VO_ERR_ARG, "%s: parameter out of range: %s", who, field);
+    CallScope call(c, false); if (call.status) return call.status;
+    SgmBuffers& sb = c->sgm;
+    const int D = p.disparity_range[1] - p.disparity_range[0];
+    if (std::min(B, VO_SGM_GROUP) > sb.cap_pairs || D > sb.cap_D) {
+        HIPC(c, hipStreamSynchronize(c->stream));              // the old workspace's last reader
+        const hipError_t e = sgm_reserve(c->pool, sb, c->rows, c->cols, std::min(B, VO_SGM_GROUP), D, false);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t fs = (size_t)c->rows * c->cols;
+    for (int g0 = 0; g0 < B; g0 += VO_SGM_GROUP) {
+        const int g = std::min(VO_SGM_GROUP, B - g0);
+        sgm_launch(sb, d_lefts + (size_t)g0 * fs, d_rights + (size_t)g0 * fs, c->rows, c->cols, g, p, 0, d_disp + (size_t)g0 * fs, c->stream);
+        sb.last_pairs = g; sb.last_first = g0; sb.last_D = D;
+    }
+    return launch_status(c);                            // profiling events are collected by vo_kernel_times
+}
+
+int vo_fetch_sgm_cost(vo_ctx* c, int pair, uint16_t* S, long capacity)
+{
+    if (!c || pair < 0) return fail(c, VO_ERR_ARG, "vo_fetch_sgm_cost: bad arguments");
+    const SgmBuffers& sb = c->sgm;
+    if (sb.last_pairs == 0) return fail(c, VO_ERR_STATE, "vo_fetch_sgm_cost: no vo_disparity_sgm call has launched yet");
+    if (pair < sb.last_first || pair >= sb.last_first + sb.last_pairs)
+        return fail(c, VO_ERR_ARG, "vo_fetch_sgm_cost: pair %d outside the last call's last group, pairs %d .. %d", pair, sb.last_first,
+                    sb.last_first + sb.last_pairs - 1);
+    const size_t n = (size_t)c->rows * c->cols * sb.last_D;
+    if (!S || capacity < 0 || (size_t)capacity < n) return fail(c, VO_ERR_CAPACITY, "vo_fetch_sgm_cost: %zu values needed", n);
+    CallScope call(c); if (call.status) return call.status;
+    HIPC(c, hipMemcpyAsync(S, sb.S + (size_t)(pair - sb.last_first) * n, sizeof(uint16_t) * n, hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+int vo_reprojection_matrix(const double P1[12], const double P2[12], double Q[16])
+{
+    if (!P1 || !P2 || !Q) return VO_ERR_ARG;
+    return vo_reprojection_from_projections(P1, P2, Q) ? VO_ERR_ARG : VO_OK;
+}
+
+int vo_reconstruct_scene(vo_ctx* c, const float* disp, int rows, int cols, int ld, int col_major, const double Q[16], float* xyz)
+{
+    const char* who = "vo_reconstruct_scene";
+    if (!c || !disp || !Q || !xyz || rows != c->rows || cols != c->cols || (col_major != 0 && col_major != 1) ||
+        ld < (col_major ? rows : cols))
+        return fail(c, VO_ERR_ARG, "%s: bad arguments", who);
+    if (!c->pending.empty()) return fail(c, VO_ERR_STATE, "asynchronous step batches pending (vo_step_collect first)");
+    CallScope call(c); if (call.status) return call.status;
+    SgmBuffers& sb = c->sgm;
+    {
+        const hipError_t e = reconstruct_reserve(c->pool, sb, rows, cols);
+        if (e != hipSuccess) return fail(c, VO_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    const size_t fs = (size_t)rows * cols;
+    const int major = col_major ? rows : cols, minor = col_major ? cols : rows;
+    HIPC(c, hipMemcpy2DAsync(sb.rin, sizeof(float) * major, disp, sizeof(float) * ld, sizeof(float) * major, minor, hipMemcpyHostToDevice,
+                             c->stream));
+    reconstruct_launch(sb.rin, rows, cols, col_major, Q, sb.xyz, c->stream);
+    HIPC(c, hipMemcpyAsync(xyz, sb.xyz, sizeof(float) * 3 * fs, hipMemcpyDeviceToHost, c->stream));
     return finish(c);
 }
 

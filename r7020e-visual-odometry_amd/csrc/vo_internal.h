@@ -360,4 +360,25 @@ hipError_t corner_reserve(DevPool& pool, CornerBuffers& cb, int rows, int cols, 
 // roi0 = x y w h, 0-based, inside the image
 hipError_t corner_launch(CornerBuffers& cb, int rows, int cols, int n_img, const vo_corner_params& p, const int* roi0, hipStream_t s);
 
+// ---- disparitySGM / reconstructScene (sgm.hip): vo_disparity_sgm[_batch[_dev]], vo_reconstruct_scene ----
+// Buffers of their own, allocated at the first launching call, so the loop's buffer sets are never
+// touched.  The workspace (census words, the sums S) holds one group of at most VO_SGM_GROUP pairs at the
+// largest D seen; img / disp stage the host entries' group; rin / xyz are vo_reconstruct_scene's.
+struct SgmBuffers {
+    int cap_pairs = 0, cap_D = 0, cap_io = 0;
+    int last_pairs = 0, last_first = 0, last_D = 0;   // the last group of the last launching call (vo_fetch_sgm_cost)
+    uint64_t* cen = nullptr;                          // [pair][2][rows][cols]
+    uint16_t* S = nullptr;                            // [pair][rows][cols][D]
+    uint8_t* img = nullptr;                           // [2][cap_io][rows][cols]: lefts, then rights
+    float* disp = nullptr;                            // [cap_io][rows * cols]
+    float* rin = nullptr; float* xyz = nullptr;       // [rows * cols], [3 * rows * cols]
+};
+hipError_t sgm_reserve(DevPool& pool, SgmBuffers& sb, int rows, int cols, int n_group, int D, bool host_io);   // all or nothing
+// k_sgm_census, the four k_sgm_paths launches and k_sgm_select over G <= cap_pairs packed row-major pairs;
+// d_disp [G][rows * cols] in row-major or (col_major) column-major order
+void sgm_launch(SgmBuffers& sb, const uint8_t* d_lefts, const uint8_t* d_rights, int rows, int cols, int G, const vo_sgm_params& p,
+                int col_major, float* d_disp, hipStream_t s);
+hipError_t reconstruct_reserve(DevPool& pool, SgmBuffers& sb, int rows, int cols);
+void reconstruct_launch(const float* d_disp, int rows, int cols, int col_major, const double* Q, float* d_xyz, hipStream_t s);
+
 }  // namespace vo

@@ -78,6 +78,25 @@ __device__ __forceinline__ T wave_min(T v)
     else return wave_tree<false>(v, [](T a, T b) { return a < b ? a : b; });
 }
 
+// The 64-lane shifts by one: lane l gets lane l - 1's value (wave_shift_up; lane 0 gets fill) or lane
+// l + 1's (wave_shift_down; lane 63 gets fill).  4-byte values, one ds_bpermute each, no LDS storage.
+template <typename T>
+__device__ __forceinline__ T wave_shift_up(T v, T fill)
+{
+    static_assert(sizeof(T) == 4, "one register per lane");
+    const int lane = threadIdx.x & 63;
+    const T x = __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(((lane - 1) & 63) << 2, __builtin_bit_cast(int, v)));
+    return lane == 0 ? fill : x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_shift_down(T v, T fill)
+{
+    static_assert(sizeof(T) == 4, "one register per lane");
+    const int lane = threadIdx.x & 63;
+    const T x = __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(((lane + 1) & 63) << 2, __builtin_bit_cast(int, v)));
+    return lane == 63 ? fill : x;
+}
+
 // inclusive prefix sum over the lanes (int, uint32_t): lane l gets x[0] + .. + x[l], lane 63 the
 // wave's total.  DPP row shifts within the rows of 16, then the row broadcasts.
 template <typename T>

@@ -15,6 +15,7 @@ running on the MI355X through libvo.so:
     estimateFundamentalMatrix              after matchFeatures (est_fundamental, est_fundamental_batch)
     vision.PointTracker                    pyramidal KLT between frames or cameras (track_points, PointTracker)
     detectMinEigenFeatures / detectHarrisFeatures   cornerPoints for the tracker (detect_corners, detect_corners_batch)
+    disparitySGM / reconstructScene        dense stereo depth (disparity_sgm, disparity_sgm_batch, reconstruct_scene)
     CreateLandmarksFromFeatures           CreateLandmarksFromFeatures.m:1-21
     VisualOdometry.step                    the VO.m loop body (VO.m:70-161)
 
@@ -101,6 +102,12 @@ class CornerParams(C.Structure):
                 ("roi", C.c_int32 * 4)]
 
 
+class SgmParams(C.Structure):
+    """vo_sgm_params: DisparityRange [min, max] (max - min in 8, 16, .. 128), UniquenessThreshold (0 .. 100) and the
+    path penalties p1 <= p2 (0 .. 255)."""
+    _fields_ = [("disparity_range", C.c_int32 * 2), ("uniqueness_threshold", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32)]
+
+
 class RefineStats(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_used", C.c_int32), ("passes", C.c_int32), ("accepted", C.c_int32),
                 ("cost_initial", C.c_double), ("cost_final", C.c_double)]
@@ -155,6 +162,7 @@ KLT_INFO_DTYPE = np.dtype([("status", "u1"), ("stop", "u1"), ("iterations", "u1"
 KLT_MAX_COORD = 1048576.0
 
 VO_CORNER_MINEIG, VO_CORNER_HARRIS = 0, 1
+VO_SGM_GROUP, VO_SGM_MAX_D = 8, 128
 
 # exported symbols (tests check the library exports every one)
 EXPORTS = [
@@ -176,6 +184,8 @@ EXPORTS = [
     "vo_default_fund_params", "vo_est_fundamental", "vo_est_fundamental_batch",
     "vo_default_klt_params", "vo_track_points", "vo_track_points_batch", "vo_fetch_klt_level",
     "vo_default_corner_params", "vo_detect_corners", "vo_detect_corners_batch", "vo_fetch_corner_metric",
+    "vo_default_sgm_params", "vo_disparity_sgm", "vo_disparity_sgm_batch", "vo_disparity_sgm_batch_dev", "vo_fetch_sgm_cost",
+    "vo_reprojection_matrix", "vo_reconstruct_scene",
 ]
 
 _libs: dict = {}
@@ -279,6 +289,16 @@ def load_library(path: str | os.PathLike | None = None):
         L.vo_detect_corners_batch.argtypes = [vp, P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(CornerParams), P(C.c_float),
                                               P(C.c_float), C.c_int, P(C.c_int32), P(C.c_int32)]
         L.vo_fetch_corner_metric.argtypes = [vp, C.c_int, P(C.c_float), C.c_int]
+    if hasattr(L, "vo_disparity_sgm"):       # (absent from an older library timed beside this one)
+        L.vo_default_sgm_params.argtypes = [P(SgmParams)]
+        L.vo_default_sgm_params.restype = None
+        L.vo_disparity_sgm.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, P(SgmParams), P(C.c_float),
+                                       C.c_int]
+        L.vo_disparity_sgm_batch.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, C.c_int, C.c_int, P(SgmParams), P(C.c_float)]
+        L.vo_disparity_sgm_batch_dev.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, P(SgmParams), C.c_void_p]
+        L.vo_fetch_sgm_cost.argtypes = [vp, C.c_int, P(C.c_uint16), C.c_long]
+        L.vo_reprojection_matrix.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double)]
+        L.vo_reconstruct_scene.argtypes = [vp, P(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_double), P(C.c_float)]
     L.vo_landmarks.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int, P(C.c_float), P(C.c_float), C.c_int,
                                P(C.c_double), P(C.c_double), C.c_int, P(C.c_int)]
     L.vo_step.argtypes = [vp, P(C.c_uint8), P(C.c_uint8), C.c_int, P(StepOut)]
@@ -510,6 +530,66 @@ def check_corner_params(p: CornerParams, rows: int, cols: int, max_keypoints: in
         bad = "roi (x y w h, 1-based, inside the image)"
     if bad:
         raise VOError(VO_ERR_ARG, f"detect_corners: parameter out of range: {bad}")
+
+
+def default_sgm_params(**overrides) -> SgmParams:
+    """vo_default_sgm_params (DisparityRange [0 128], UniquenessThreshold 15, p1 10, p2 120), with any field
+    overridden by keyword (disparity_range: (min, max)).  Host only: no library, no device."""
+    p = SgmParams((C.c_int32 * 2)(0, 128), 15, 10, 120)
+    for k, v in overrides.items():
+        if k not in dict(SgmParams._fields_):
+            raise VOError(VO_ERR_ARG, f"default_sgm_params: no field {k}")
+        if k == "disparity_range":
+            v = (C.c_int32 * 2)(*(int(e) for e in v))
+        setattr(p, k, v)
+    return p
+
+
+def check_sgm_params(p: SgmParams, who: str = "disparity_sgm") -> None:
+    """vo_disparity_sgm's parameter ranges (include/vo.h), checked on the host: VOError(VO_ERR_ARG) naming the
+    offending field."""
+    lo, hi = p.disparity_range
+    bad = None
+    if lo < -1024 or hi > 1024 or lo >= hi:
+        bad = "disparity_range (-1024 <= min < max <= 1024)"
+    elif (hi - lo) % 8 != 0 or hi - lo > VO_SGM_MAX_D:
+        bad = "disparity_range (max - min in 8, 16, .. 128)"
+    elif not 0 <= p.uniqueness_threshold <= 100:
+        bad = "uniqueness_threshold (0 .. 100)"
+    elif not 0 <= p.p1 <= 255:
+        bad = "p1 (0 .. 255)"
+    elif not p.p1 <= p.p2 <= 255:
+        bad = "p2 (p1 .. 255)"
+    if bad:
+        raise VOError(VO_ERR_ARG, f"{who}: parameter out of range: {bad}")
+
+
+def reprojection_matrix(P1, P2) -> np.ndarray:
+    """vo_reprojection_matrix: Q [4, 4] float64 of a rectified pair from its 3 x 4 projection matrices (the
+    rectified pairs VO.m:27-47 reads); VOError(VO_ERR_ARG) for any other pair."""
+    a = np.ascontiguousarray(np.asarray(P1, np.float64).reshape(-1))
+    b = np.ascontiguousarray(np.asarray(P2, np.float64).reshape(-1))
+    if a.size != 12 or b.size != 12:
+        raise VOError(VO_ERR_ARG, "reprojection_matrix: two 3 x 4 projection matrices")
+    Q = np.zeros(16, np.float64)
+    if load_library().vo_reprojection_matrix(_p(a, C.c_double), _p(b, C.c_double), _p(Q, C.c_double)) != VO_OK:
+        raise VOError(VO_ERR_ARG, "reprojection_matrix: not a rectified pair [fx 0 cx tx; 0 fy cy 0; 0 0 1 0] with equal fx, fy, cy, "
+                                  "P1's tx = 0 and P2's tx != 0")
+    return Q.reshape(4, 4)
+
+
+def _image_view(img, who: str):
+    """A 2-D uint8 image as the image entries take it, without a copy where its storage allows:
+    -> (img, ld, col_major)."""
+    img = np.asarray(img, np.uint8)
+    if img.ndim != 2:
+        raise VOError(VO_ERR_ARG, f"{who}: a 2-D uint8 image")
+    rows, cols = img.shape
+    if rows > 1 and img.strides[0] == 1 and img.strides[1] >= rows:
+        return img, img.strides[1], 1
+    if img.strides[1] == 1 and img.strides[0] >= cols:
+        return img, img.strides[0], 0
+    return np.ascontiguousarray(img), cols, 0
 
 
 def _refine_stats(s: RefineStats) -> np.ndarray:
@@ -1153,6 +1233,83 @@ class Context:
         self._check(self.lib.vo_fetch_corner_metric(self.h, image, _p(out, C.c_float), out.size))
         return out
 
+    # ---- disparitySGM / reconstructScene ----
+    def disparity_sgm(self, left: np.ndarray, right: np.ndarray, params: SgmParams | None = None) -> np.ndarray:
+        """disparityMap = disparitySGM(I1, I2) of one rectified pair (vo_disparity_sgm) -> [rows, cols] float32, NaN
+        where the match is unreliable or falls outside the right image.  The images go through as they lie (see
+        sift), the second in the first's storage order; the map has that order too."""
+        left, ld, col_major = _image_view(left, "disparity_sgm")
+        right = np.asarray(right, np.uint8)
+        if right.shape != left.shape:
+            raise VOError(VO_ERR_ARG, "disparity_sgm: two images of one size")
+        rows, cols = left.shape
+        if col_major:
+            right = np.asfortranarray(right)
+            ld_r = rows
+        else:
+            right = np.ascontiguousarray(right)
+            ld_r = cols
+        if ld_r != ld:                                     # one stride for both: pack the first as well
+            left = np.asfortranarray(left) if col_major else np.ascontiguousarray(left)
+            ld = ld_r
+        p = params if params is not None else default_sgm_params()
+        check_sgm_params(p)
+        out = np.zeros((rows, cols), np.float32, order="F" if col_major else "C")
+        self._check(self.lib.vo_disparity_sgm(self.h, _p(left, C.c_uint8), _p(right, C.c_uint8), rows, cols, ld, col_major, C.byref(p),
+                                              _p(out, C.c_float), rows if col_major else cols))
+        return out
+
+    def disparity_sgm_batch(self, lefts: np.ndarray, rights: np.ndarray, params: SgmParams | None = None) -> np.ndarray:
+        """vo_disparity_sgm_batch: lefts, rights [n_pairs, rows, cols] -> [n_pairs, rows, cols] float32; the pairs
+        run in groups of VO_SGM_GROUP."""
+        lefts, rights = np.ascontiguousarray(lefts, np.uint8), np.ascontiguousarray(rights, np.uint8)
+        if lefts.ndim != 3 or lefts.shape != rights.shape or lefts.shape[0] < 1:
+            raise VOError(VO_ERR_ARG, "disparity_sgm_batch: lefts, rights [n_pairs, rows, cols]")
+        p = params if params is not None else default_sgm_params()
+        check_sgm_params(p, "disparity_sgm_batch")
+        out = np.zeros(lefts.shape, np.float32)
+        self._check(self.lib.vo_disparity_sgm_batch(self.h, _p(lefts, C.c_uint8), _p(rights, C.c_uint8), lefts.shape[2], 0,
+                                                    lefts.shape[0], C.byref(p), _p(out, C.c_float)))
+        return out
+
+    def disparity_sgm_batch_dev(self, d_lefts: int, d_rights: int, B: int, d_disp: int, params: SgmParams | None = None) -> None:
+        """vo_disparity_sgm_batch_dev: B tightly packed row-major device pairs at d_lefts, d_rights -> float32 maps
+        at d_disp (device pointers), stream-ordered on the context's stream (synchronise before reading)."""
+        p = params if params is not None else default_sgm_params()
+        check_sgm_params(p, "disparity_sgm_batch_dev")
+        self._check(self.lib.vo_disparity_sgm_batch_dev(self.h, C.c_void_p(d_lefts or None), C.c_void_p(d_rights or None), B, C.byref(p),
+                                                        C.c_void_p(d_disp or None)))
+
+    def fetch_sgm_cost(self, pair: int, D: int) -> np.ndarray:
+        """Diagnostic (vo_fetch_sgm_cost): the summed path costs S [rows, cols, D] uint16 of pair `pair` of the last
+        disparity_sgm* call (of its last group of VO_SGM_GROUP pairs); D = that call's max - min."""
+        out = np.zeros((self.rows, self.cols, int(D)), np.uint16)
+        self._check(self.lib.vo_fetch_sgm_cost(self.h, pair, _p(out, C.c_uint16), out.size))
+        return out
+
+    def reconstruct_scene(self, disp: np.ndarray, Q) -> np.ndarray:
+        """xyzPoints = reconstructScene(disparityMap, Q) (vo_reconstruct_scene) -> [rows, cols, 3] float32, in the
+        map's storage order (a Fortran-ordered map gives a Fortran-ordered rows x cols x 3 array, as MATLAB holds
+        it); NaN where the disparity is NaN."""
+        disp = np.asarray(disp, np.float32)
+        if disp.ndim != 2:
+            raise VOError(VO_ERR_ARG, "reconstruct_scene: a 2-D float32 disparity map")
+        rows, cols = disp.shape
+        if rows > 1 and disp.strides[0] == 4 and disp.strides[1] >= 4 * rows and disp.strides[1] % 4 == 0:
+            col_major, ld = 1, disp.strides[1] // 4
+        elif disp.strides[1] == 4 and disp.strides[0] >= 4 * cols and disp.strides[0] % 4 == 0:
+            col_major, ld = 0, disp.strides[0] // 4
+        else:
+            disp = np.ascontiguousarray(disp)
+            col_major, ld = 0, cols
+        q = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(-1))
+        if q.size != 16:
+            raise VOError(VO_ERR_ARG, "reconstruct_scene: Q is 4 x 4")
+        out = np.zeros((rows, cols, 3), np.float32, order="F" if col_major else "C")
+        self._check(self.lib.vo_reconstruct_scene(self.h, _p(disp, C.c_float), rows, cols, ld, col_major, _p(q, C.c_double),
+                                                  _p(out, C.c_float)))
+        return out
+
     # ---- new-landmark filter + CreateLandmarksFromFeatures ----
     def landmarks(self, l_pos, r_pos, old_l, old_r, pose) -> np.ndarray:
         a = [np.ascontiguousarray(x, np.float32).reshape(-1, 2) for x in (l_pos, r_pos, old_l, old_r)]
@@ -1511,3 +1668,21 @@ def detectHarrisFeatures(I, MinQuality: float = 0.01, FilterSize: int = 5, ROI=N
     """detectHarrisFeatures(I, MinQuality = , FilterSize = , ROI = ) -> (Location, Metric): Harris-Stephens corners,
     det - 0.04 trace^2 of the same smoothed gradient matrix."""
     return _detect_corners(I, VO_CORNER_HARRIS, MinQuality, FilterSize, ROI)
+
+
+def disparitySGM(I1, I2, DisparityRange=(0, 128), UniquenessThreshold: int = 15):
+    """disparityMap = disparitySGM(I1, I2, DisparityRange = , UniquenessThreshold = ) of a rectified pair: semi-global
+    matching on a census cost -> [rows, cols] float32, NaN where unreliable."""
+    I1, I2 = np.asarray(I1), np.asarray(I2)
+    if I1.ndim != 2 or I1.dtype != np.uint8 or I2.shape != I1.shape or I2.dtype != np.uint8:
+        raise VOError(VO_ERR_ARG, "two 2-D uint8 images of one size")
+    p = default_sgm_params(disparity_range=DisparityRange, uniqueness_threshold=int(UniquenessThreshold))
+    return _default_ctx(*I1.shape).disparity_sgm(I1, I2, p)
+
+
+def reconstructScene(disparityMap, reprojectionMatrix):
+    """xyzPoints = reconstructScene(disparityMap, reprojectionMatrix) -> [rows, cols, 3] float32."""
+    d = np.asarray(disparityMap, np.float32)
+    if d.ndim != 2:
+        raise VOError(VO_ERR_ARG, "a 2-D disparity map")
+    return _default_ctx(*d.shape).reconstruct_scene(d, reprojectionMatrix)
